@@ -10,19 +10,21 @@ InfoNCE over the global batch, hand-written backward through both encoders, grad
 ~133 M parameters.  Per-GPU batch is 1024 (global batch 1024 at N=1 = the configuration the metric is quoted on;
 weak scaling for N>1: 8192 global at N=8 = BASELINE config 5).  fp32 storage and arithmetic everywhere; the large
 contractions run in split-bf16 (three bf16 MFMAs per product, fp32 accumulate, ~2^-16 relative; `--precision fp32` =
-exact fp32 MFMA, measured beside it as `other_precision`).  Synthetic data resident in HBM before the timed region,
+exact fp32 MFMA, measured beside it as `other_precision` with --full).  Synthetic data resident in HBM before the timed region,
 seeded random-init weights.
-The two encoders run on two HIP streams (contrastive.JointContrastiveTrainer); the per-kernel profile behind `roofline` is
-taken over two extra single-stream steps after the timed region (see the comment there), `precision_check` compares the
-split-bf16 forward and backward with the exact-fp32 ones on the bench batch (free-running, and with the fp32 forward's ReLU /
-max-pool decisions imposed on the split-bf16 backward).
+The two encoders run on two HIP streams (contrastive.JointContrastiveTrainer).
+A plain run sets up, warms up, times the --steps steps and prints the line; `--dump-outputs DIR` also writes what the last timed
+step computed (`dump_outputs`).  Everything else runs only with `--full`: the per-kernel profile behind `roofline` is taken over two
+extra single-stream steps after the timed region (see the comment there), `precision_check` compares the split-bf16 forward and
+backward with the exact-fp32 ones on the bench batch (free-running, and with the fp32 forward's ReLU / max-pool decisions imposed on
+the split-bf16 backward), `other_precision`, the side measurements (`secondary`), `cotangent_norm` and `cpu_baseline`.
 The timed steps train a model with LIVE gradients: BatchNorm statistics are calibrated on a sample batch (synthetic weights then
 map different images to different embeddings, like a trained checkpoint), the learning rate keeps the 133 M-parameter model in the
 first, descending phase of contrastive training for the whole run, and the line carries the loss trace, the norm of the loss
-gradient w.r.t. the embeddings before and after the timed region (`cotangent_norm`) and per-step times (`step_ms`); the run
-refuses to print a number measured on collapsed embeddings (cotangents fallen to < 2 % of their initial norm, or all embeddings
-parallel; round 2's collapsed run sat at 4e-4 of it).
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+gradient w.r.t. the embeddings before and after the timed region (`cotangent_norm`, with --full) and per-step times (`step_ms`);
+the run refuses to print a number measured on collapsed embeddings (a loss trace pinned at ln(global batch); with --full also
+cotangents fallen to < 2 % of their initial norm, or all embeddings parallel; round 2's collapsed run sat at 4e-4 of it).
+Rank 0 prints ONE JSON line (contract in the task statement); with --full it carries `roofline` and `cpu_baseline` objects.
 """
 from __future__ import annotations
 
@@ -76,7 +78,7 @@ def usable_cores() -> int:
     return max(1, min(n, int(os.environ.get("CXRK_CPU_THREADS", "64"))))
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -97,7 +99,15 @@ def parse():
     ap.add_argument("--precision", default=os.environ.get("CXRK_PRECISION", "split_bf16"), choices=["split_bf16", "fp32"],
                     help="contraction precision of the headline number (the other one is measured too, on fewer steps)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the measurement in the other precision")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: precision check, other precision, side measurements, cotangent "
+                         "norms, roofline profile and CPU baseline (the --no-* options above switch single legs off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_secondary = args.no_roofline = args.no_cpu_baseline = True
+    return args
 
 
 def cpu_baseline(batch: int, seq_len: int, image_size: int, tau: float, steps: int = 3):
@@ -219,6 +229,29 @@ def cotangent_norms(trainer, images, ids, mask):
         return float((n.sum(0).pow(2).sum() - b) / (b * b - b))
     return {"loss": float(loss), "dL_dI": float(gi.norm()), "dL_dT": float(gt.norm()), "mean_offdiag_cos_image": offdiag(ie),
             "mean_offdiag_cos_text": offdiag(te)}
+
+
+DUMP_SAMPLE = 1 << 21   # positions of the flat parameter / gradient buffers that --dump-outputs writes (8 MB each in float32)
+DUMP_SEED = 1234
+
+
+def dump_outputs(out_dir: str, loss: torch.Tensor, flat_p: torch.Tensor, flat_g: torch.Tensor) -> dict:
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files in `out_dir`: `loss` (the step's return
+    value, shape [1]), and, since the ~133 M trained parameters (532 MB) exceed the 64 MB budget, the same DUMP_SAMPLE seeded
+    positions of the updated flat parameter buffer (`params_sample`) and of the gradient the step applied (`grads_sample`, the part
+    a wrong kernel changes: at lr 1e-6 the parameters barely move).  Returns {name: shape}."""
+    import numpy as np
+    n = flat_p.numel()
+    idx = torch.randint(n, (min(DUMP_SAMPLE, n),), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+    idx = idx.to(flat_p.device)
+    arrays = {"loss": loss.detach().reshape(1), "params_sample": flat_p[idx], "grads_sample": flat_g[idx]}
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return shapes
 
 
 def secondary_metrics(args, dev, trainer, images, ids, mask, step_ms):
@@ -421,8 +454,10 @@ def main():
         log(f"precision check: {precision_check}")
 
     log(f"models + {NB} synthetic batches resident on the GPU; warm-up")
-    cot_before = cotangent_norms(trainer, images, ids, mask)
-    log(f"before the first step: {cot_before}")
+    cot_before = None
+    if args.full:
+        cot_before = cotangent_norms(trainer, images, ids, mask)
+        log(f"before the first step: {cot_before}")
     loss = None
     losses = []
     warm_ms = []
@@ -453,8 +488,13 @@ def main():
     losses += [float(x) for x in step_losses]
     log(f"timed region: {args.steps} steps in {dt:.2f} s; loss {losses[0]:.4f} -> {losses[-1]:.4f}; "
         f"per step {' '.join(f'{x:.1f}' for x in step_ms)} ms")
-    cot_after = cotangent_norms(trainer, images, ids, mask)
-    log(f"after the timed region: {cot_after}")
+    if args.dump_outputs and rank == 0:   # before anything below moves the weights on
+        shapes = dump_outputs(args.dump_outputs, step_losses[-1], trainer.optimizer.flat_p, trainer.optimizer.flat_g)
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {shapes}")
+    cot_after = None
+    if args.full:
+        cot_after = cotangent_norms(trainer, images, ids, mask)
+        log(f"after the timed region: {cot_after}")
     import math
     ln_b = math.log(world * B)
     # collapsed embeddings (all parallel: uniform logits, loss = ln(global batch) EXACTLY and staying there, cotangents -> 0) must
@@ -546,13 +586,15 @@ def main():
             "final_loss": final_loss, "loss_trace": [round(x, 5) for x in losses], "ln_global_batch": round(ln_b, 5),
             "lr": args.lr, "step_ms": [round(x, 2) for x in step_ms], "warmup_step_ms": [round(x, 1) for x in warm_ms],
             "first_timed_step_ms": round(step_ms[0], 2), "steady_state_ms": round(sorted(step_ms)[len(step_ms) // 2], 2),
-            "cotangent_norm": {"before_first_step": cot_before, "after_timed_region": cot_after,
-                               "note": "norm of dL/d(embeddings) = what both encoders' backward passes are fed; 0 for a collapsed model"},
             "loss_note": "BatchNorm statistics calibrated on a sample batch, Adam at --lr: the run stays in the first, descending phase of "
                          "contrastive training (loss above ln(global batch) and falling, embeddings not parallel, cotangents O(1e-2..1)); "
-                         "bench.py exits with an error instead of a number when the embeddings collapse (cotangent norm < 2 % of the initial one)",
+                         "bench.py exits with an error instead of a number when the embeddings collapse (loss pinned at ln(global batch); "
+                         "with --full: cotangent norm < 2 % of the initial one)",
             "model_tflops_per_s": FLOP_PER_PAIR_STEP * world * B * args.steps / dt / 1e12,
         }
+        if args.full:
+            out["cotangent_norm"] = {"before_first_step": cot_before, "after_timed_region": cot_after,
+                                     "note": "norm of dL/d(embeddings) = what both encoders' backward passes are fed; 0 for a collapsed model"}
         if prof:
             summ = K.profiler.summary()
             if summ:

@@ -32,3 +32,37 @@ def test_plain_command_spawns_the_ranks_and_fails_loudly():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=env, capture_output=True, text=True,
                        timeout=600)
     assert r.returncode != 0
+
+
+def test_plain_run_times_the_steps_only_and_full_restores_the_rest():
+    sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (5, 2, False, None)
+    assert a.no_secondary and a.no_roofline and a.no_cpu_baseline
+    f = bench.parse(["--full"])
+    assert f.full and not (f.no_secondary or f.no_roofline or f.no_cpu_baseline)
+    g = bench.parse(["--full", "--no-cpu-baseline", "--dump-outputs", "out"])
+    assert g.no_cpu_baseline and not g.no_secondary and g.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample_within_budget(tmp_path):
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    assert 2 * bench.DUMP_SAMPLE * 4 + 4 <= 64 << 20                  # params + grads samples + loss, float32
+    n = 3 * bench.DUMP_SAMPLE
+    flat_p = torch.arange(n, dtype=torch.float32)
+    flat_g = -torch.arange(n, dtype=torch.float32) / n
+    shapes = bench.dump_outputs(str(tmp_path / "a"), torch.tensor(6.93), flat_p, flat_g)
+    bench.dump_outputs(str(tmp_path / "b"), torch.tensor(6.93), flat_p, flat_g)
+    assert shapes == {"loss": [1], "params_sample": [bench.DUMP_SAMPLE], "grads_sample": [bench.DUMP_SAMPLE]}
+    for name in shapes:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, b)        # same positions in every run
+    p = np.load(tmp_path / "a" / "params_sample.npy")
+    g = np.load(tmp_path / "a" / "grads_sample.npy")
+    assert np.all(np.diff(p) >= 0) and p.max() > 0.9 * n              # spread over the whole buffer
+    np.testing.assert_array_equal(g, -p / n)                          # gradient sampled at the parameters' positions
+    assert np.load(tmp_path / "a" / "loss.npy")[0] == np.float32(6.93)
