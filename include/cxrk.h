@@ -215,6 +215,44 @@ int cxrk_attn_fwd(const float* qkv, const long* mask, int B, int L, int nH, int 
 size_t cxrk_attn_bwd_ws_bytes(int B, int L, int nH, int dH);
 int cxrk_attn_bwd(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH, void* dqkv,
                   long dqkvplane, float* ws, size_t ws_bytes, hipStream_t stream);
+/* ---- dropout (train mode, HF BertModel's four sites; opt-in through CXRBertModel.enable_dropout_) ----
+ * Every entry below takes the dropout descriptor (seed, counter, layer, site, row_offset, p), 0 <= p < 1, layer < 64,
+ * site: 0 = embeddings, 1 = attention probabilities, 2 = attention output, 3 = FFN output.  Keep rule (csrc/dropout.h):
+ *   Philox4x32-10, key = (seed & 0xffffffff, seed >> 32),
+ *   counter = (c >> 2, n, t | h << 16, (counter & 0xffffff) << 8 | layer << 2 | site), draw = output word c & 3,
+ *   keep iff draw >= floor(float(p) * 2^32 + 0.5); kept values are scaled by 1 / (1 - p).
+ * n = row_offset + the sequence index within the call, t = token (the query for site 1), c = column (the key for site 1),
+ * h = head (0 for the hidden sites).  The masks are regenerated in the backward, never stored.
+ * dropout_mask:       keep[N][nH][L][C] (uint8) of one site; hidden sites: nH = 1, C = H (the [N*L, H] activation).
+ * embed_ln_fwd_drop:  y = keep * s * LayerNorm(...); xhat / rstd are those of the LayerNorm.
+ * residual_ln_fwd_drop: y = LayerNorm(keep * s * x + res); res fp32 (resplane = 0) or planes (resplane > 0), row stride res_ld
+ *                     (0: H); rows_per_seq = tokens per sequence of the tensor (L, or 1 for the CLS rows of the last layer).
+ * residual_ln_bwd_drop: mode 1 (y = LN(drop(x) + res)): dx = LN'(dy) + dx_add (the residual path), dxm = keep * s * dx in the same
+ *                     format (the dense output's gradient), dxsum = column sums of dxm; mode 2 (y = drop(LN(x))): dy is masked on
+ *                     load, dxm must be NULL.
+ * attn_fwd_drop:      ctx = (keep * s o P) V; probs stay undropped.  attn_bwd_drop: dV = (keep * s o P)^T dO,
+ *                     dP = keep * s o (dO V^T), dS = P o (dP - rowsum(dP o P)) / sqrt(d).
+ */
+int cxrk_dropout_mask(unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p, int N, int L, int nH,
+                      int C, unsigned char* keep, hipStream_t stream);
+int cxrk_embed_ln_fwd_drop(const long* ids, const float* word, const float* pos, const float* type, const float* gamma,
+                           const float* beta, float eps, long T, int L, int H, void* y, long yplane, float* xhat, float* rstd,
+                           unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                           hipStream_t stream);
+int cxrk_residual_ln_fwd_drop(const float* x, const void* res, long resplane, long res_ld, const float* gamma, const float* beta,
+                              float eps, long rows, int H, int rows_per_seq, void* y, long yplane, float* xhat, float* rstd,
+                              unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                              hipStream_t stream);
+int cxrk_residual_ln_bwd_drop(const float* dy, const float* xhat, const float* rstd, const float* gamma, long rows, int H,
+                              int rows_per_seq, int mode, const float* dx_add, void* dx, void* dxm, long dxplane, float* dgamma,
+                              float* dbeta, int accumulate, float* dxsum, int dxsum_accumulate, float* ws, size_t ws_bytes,
+                              unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                              hipStream_t stream);
+int cxrk_attn_fwd_drop(const float* qkv, const long* mask, int B, int L, int nH, int dH, void* ctx, long ctxplane, float* probs,
+                       unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p, hipStream_t stream);
+int cxrk_attn_bwd_drop(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH, void* dqkv,
+                       long dqkvplane, float* ws, size_t ws_bytes, unsigned long long seed, unsigned counter, int layer, int site,
+                       long row_offset, float p, hipStream_t stream);
 size_t cxrk_embed_bwd_ws_bytes(long T, int H);
 int cxrk_embed_bwd(const long* ids, const float* dx, long T, int H, float* dword, float* ws, size_t ws_bytes, hipStream_t stream);
 /* dx = dy * gelu'(pre): the erf-GELU between dense_to_hidden and LayerNorm of BertProjectionHead (modelling_cxrbert.py:45-46). */

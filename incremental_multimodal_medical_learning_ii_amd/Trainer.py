@@ -544,10 +544,13 @@ class Trainer:
     # ------------------------------------------------------------------------------------------------ hot loops
     def _set_mode(self, train: bool):
         """adapters follow the loop (`Trainer.py:533-535,779-782`); in joint mode the encoders stay in eval mode throughout —
-        BatchNorm on running statistics, dropout off: the only mode the HIP path implements (parameters still get gradients)"""
+        BatchNorm on running statistics, dropout off (parameters still get gradients) -- except a text model that opted in to dropout
+        (`CXRBertModel.enable_dropout_`, drivers `--text-dropout`): it trains in train mode and scores in eval mode"""
         for m in (self.image_adapter, self.text_adapter):
             if m is not None:
                 m.train(train)
+        if self._joint is not None and getattr(self.bert_encoder.model, "dropout_enabled", False):
+            self.bert_encoder.model.train(train)
 
     def _shard(self, n: int):
         """this rank's contiguous row range of a global batch of n rows (tensor_split boundaries)"""

@@ -7,13 +7,14 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint32, c_uint64, c_void_p
 from typing import Dict, List, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcxrk.so")
 
 P, I, L, F, Z = c_void_p, c_int, c_long, c_float, c_size_t
+DROP = [c_uint64, c_uint32, I, I, L, F]   # dropout descriptor: seed, counter, layer, site, row_offset, p
 
 # name -> (restype, argtypes).  Must list every symbol of include/cxrk.h (tests/test_cabi.py checks it).
 SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
@@ -62,6 +63,12 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_attn_fwd": (I, [P, P, I, I, I, I, P, L, P, P]),
     "cxrk_attn_bwd_ws_bytes": (Z, [I, I, I, I]),
     "cxrk_attn_bwd": (I, [P, P, P, I, I, I, I, P, L, P, Z, P]),
+    "cxrk_dropout_mask": (I, DROP + [I, I, I, I, P, P]),
+    "cxrk_embed_ln_fwd_drop": (I, [P, P, P, P, P, P, F, L, I, I, P, L, P, P] + DROP + [P]),
+    "cxrk_residual_ln_fwd_drop": (I, [P, P, L, L, P, P, F, L, I, I, P, L, P, P] + DROP + [P]),
+    "cxrk_residual_ln_bwd_drop": (I, [P, P, P, P, L, I, I, I, P, P, P, L, P, P, I, P, I, P, Z] + DROP + [P]),
+    "cxrk_attn_fwd_drop": (I, [P, P, I, I, I, I, P, L, P] + DROP + [P]),
+    "cxrk_attn_bwd_drop": (I, [P, P, P, I, I, I, I, P, L, P, Z] + DROP + [P]),
     "cxrk_embed_bwd_ws_bytes": (Z, [L, I]),
     "cxrk_embed_bwd": (I, [P, P, L, I, P, P, Z, P]),
     "cxrk_gelu_bwd": (I, [P, P, L, P, P]),

@@ -46,11 +46,32 @@ class JointContrastiveTrainer:
         else:
             raise ValueError(f"optim must be 'adam' or 'sgd', got {optim!r}")
         text_model.prepare_()
-        self.world = 1
+        self.world, self.rank = 1, 0
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             self.world = dist.get_world_size(group)
+            self.rank = dist.get_rank(group)
+        self._dropout_synced = None
+        self.sync_dropout_state()
         self._spans = self.reduce_spans(inamed, tparams) if self.world > 1 else {}
+
+    def sync_dropout_state(self) -> None:
+        """Text dropout under data parallelism: every rank takes rank 0's (seed, counter), so that with the row offset of
+        `forward_loss` the masks of a sharded step are those of the single-process step on the global batch.  Runs at construction
+        and at the start of every `step`; it communicates only when the text model's dropout stream was (re)seeded or assigned since
+        the last time (`enable_dropout_` / `dropout_state` on every rank, in the same program order)."""
+        tm = self.text_model
+        version = getattr(tm, "_dropout_version", None)
+        if self.world == 1 or not getattr(tm, "dropout_enabled", False) or version == self._dropout_synced:
+            return
+        import torch.distributed as dist
+        seed, counter = tm.dropout_state
+        dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
+        t = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed, counter], dtype=torch.int64, device=dev)
+        dist.broadcast(t, src=0 if self.group is None else dist.get_global_rank(self.group, 0), group=self.group)
+        s, c = (int(v) for v in t.cpu())
+        tm.dropout_state = (s & (2 ** 64 - 1), c)
+        self._dropout_synced = tm._dropout_version
 
     def reduce_spans(self, inamed=None, tparams=None) -> dict:
         """{tag: (lo, hi)} element ranges of the flat gradient buffer that become complete together during `backward()`, in the
@@ -73,7 +94,10 @@ class JointContrastiveTrainer:
     def forward_loss(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
         """The two encoders are independent up to the loss, so the text encoder runs on a second HIP stream: the tail of one
         encoder's launch (its last, partly filled round of workgroups) overlaps the head of the other's.  Autograd replays
-        each encoder's backward on the stream its forward ran on and joins them again before `backward()` returns."""
+        each encoder's backward on the stream its forward ran on and joins them again before `backward()` returns.
+        Text dropout masks are keyed by the global sequence index: this rank's shard starts at rank * local rows (the shards are
+        equal and contiguous, gathered in rank order)."""
+        self.text_model.dropout_row_offset = self.rank * int(input_ids.shape[0])
         if not (self.two_streams and images.is_cuda):
             img = self.image_model(images)
             txt = self.text_model.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
@@ -101,6 +125,7 @@ class JointContrastiveTrainer:
         contribution was accumulated.  A rank that raises inside `backward()` after a range was started leaves its peers inside that
         collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog)."""
         self.optimizer.zero_grad()
+        self.sync_dropout_state()
         if self.world > 1 and self._spans:
             works, fired = [], []
 

@@ -3,9 +3,12 @@
 //
 // Reference semantics: HuggingFace BertForMaskedLM as configured by
 // health_multimodal/text/model/configuration_cxrbert.py:11-22 and used at modelling_cxrbert.py:87-99
-// (post-LN encoder, LayerNorm eps 1e-12, additive key mask, softmax(QK^T/sqrt(d)) V, dropout inactive).
+// (post-LN encoder, LayerNorm eps 1e-12, additive key mask, softmax(QK^T/sqrt(d)) V).
+// Dropout (train mode, opt-in): the LayerNorm and attention kernels take a DROP template flag; the DROP = false instantiations
+// are the eval-mode kernels, unchanged.  Masks come from dropout.h (counter-based, regenerated in the backward, never stored).
 #include "cxrk.h"
 #include "cxrk_common.h"
+#include "dropout.h"
 
 using namespace cxrk;
 
@@ -63,14 +66,30 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 // H % 8 == 0: a lane owns 8 consecutive columns (lane + 64*i)*8.. -> 16-byte accesses; y is written as fp32 or as split-bf16
 // planes (yp: hi plane, lo plane yplane elements behind), the format the next GEMM consumes in split-bf16 mode.
 constexpr int LN_MAXV8 = LN_MAXV / 8;
-template <bool EMBED>
+// dropout operands of the LayerNorm forward (DROP instantiations only): the keep rule, and the residual of y = LN(drop(x) + res)
+// as fp32 (res, row stride res_ld) or as planes (resp)
+struct LnFwdDrop {
+  DropKey dk;
+  const unsigned short* resp;
+  long resplane, res_ld;
+};
+// keep factors of the 8 columns c8*8.. of one row
+__device__ __forceinline__ void drop_factors8(const DropKey& dk, int c8, unsigned n, unsigned t, float (&f)[8]) {
+  float a[4], b[4];
+  drop_factors4(dk, 2 * c8, n, t, a); drop_factors4(dk, 2 * c8 + 1, n, t, b);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) { f[q] = a[q]; f[q + 4] = b[q]; }
+}
+// DROP, EMBED:  y = keep * s * LN(word + pos + type)  (BertEmbeddings.dropout); xhat / rstd are those of the LayerNorm.
+// DROP, !EMBED: y = LN(keep * s * x + res)             (BertSelfOutput / BertOutput: the dense output is dropped, then the residual)
+template <bool EMBED, bool DROP = false>
 __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                           const long* __restrict__ ids, const float* __restrict__ word,
                                                           const float* __restrict__ pos, const float* __restrict__ type,
                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
                                                           float eps, long rows, int H, int L, float* __restrict__ y,
                                                           unsigned short* __restrict__ yp, long yplane,
-                                                          float* __restrict__ xhat, float* __restrict__ rstd_out) {
+                                                          float* __restrict__ xhat, float* __restrict__ rstd_out, LnFwdDrop dr) {
   const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int lane = threadIdx.x & 63;
@@ -78,7 +97,9 @@ __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float* __restric
   float v[LN_MAXV8][8];
   float s = 0.f;
   const float* xr = EMBED ? word + ids[row] * H : x + row * H;
-  const float* rr = EMBED ? pos + (row % L) * H : (res ? res + row * H : nullptr);
+  const float* rr = EMBED ? pos + (row % L) * H : (res ? res + row * (DROP ? dr.res_ld : (long)H) : nullptr);
+  unsigned dn = 0, dt = 0;
+  if constexpr (DROP) drop_row(dr.dk, row, dn, dt);
   auto ld8 = [](const float* p, float (&o)[8]) {
     const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
     o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
@@ -90,6 +111,14 @@ __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float* __restric
     for (int q = 0; q < 8; ++q) v[i][q] = 0.f;
     if (c8 < H8) {
       ld8(xr + c8 * 8, v[i]);
+      if constexpr (DROP && !EMBED) {
+        float f[8]; drop_factors8(dr.dk, c8, dn, dt, f);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) v[i][q] *= f[q];
+        if (dr.resp) { float t[8]; planes_load8(dr.resp, dr.resplane, row * dr.res_ld + c8 * 8, t);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) v[i][q] += t[q]; }
+      }
       if (rr) { float t[8]; ld8(rr + c8 * 8, t);
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[i][q] += t[q]; }
@@ -117,6 +146,11 @@ __global__ __launch_bounds__(256) void ln_fwd_vec8_kernel(const float* __restric
       ld8(gamma + c8 * 8, g); ld8(beta + c8 * 8, b);
 #pragma unroll
       for (int q = 0; q < 8; ++q) { v[i][q] *= rs; o[q] = v[i][q] * g[q] + b[q]; }
+      if constexpr (DROP && EMBED) {
+        float f[8]; drop_factors8(dr.dk, c8, dn, dt, f);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) o[q] *= f[q];
+      }
       if (xhat) {
         *reinterpret_cast<float4*>(xhat + row * H + c8 * 8) = make_float4(v[i][0], v[i][1], v[i][2], v[i][3]);
         *reinterpret_cast<float4*>(xhat + row * H + c8 * 8 + 4) = make_float4(v[i][4], v[i][5], v[i][6], v[i][7]);
@@ -178,11 +212,23 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ d
 }
 // H % 4 == 0: a lane owns float4 columns (lane + 64*i)*4..+3 -> 16-byte loads / stores, a quarter of the instructions.
 constexpr int LN_MAXV4 = LN_MAXV / 4;
+// dropout modes of the LayerNorm backward
+//   LNB_DROP_RES:  y = LN(drop(x) + res).  dx (the gradient of the sum, + dx_add) is the residual path; dxm = keep * s * dx, in the
+//                  same format, is the gradient of the dense output x; the column sums (np = 3) are those of dxm (the dense bias).
+//   LNB_DROP_DY:   y = drop(LN(x)) (the embeddings): dy is masked on load.
+enum { LNB_PLAIN = 0, LNB_DROP_RES = 1, LNB_DROP_DY = 2 };
+struct LnBwdDrop {
+  DropKey dk;
+  float* dxm;
+  unsigned short* dxmp;
+};
+template <int DM = LNB_PLAIN>
 __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const float* __restrict__ dy, const float* __restrict__ xhat,
                                                          const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                          long rows, int H, int rows_per, float* __restrict__ dx,
                                                          unsigned short* __restrict__ dxp, long dxplane,
-                                                         const float* __restrict__ dx_add, float* __restrict__ part, int np) {
+                                                         const float* __restrict__ dx_add, float* __restrict__ part, int np,
+                                                         LnBwdDrop dr) {
   // np = 2: partials of dgamma, dbeta; np = 3: also the column sums of the OUTPUT (the bias gradient of the dense layer that
   // produced this LayerNorm's input: its dy is exactly what this kernel writes, so the separate column-sum pass over it goes away)
   __shared__ float sh[3][4][64 * LN_MAXV];
@@ -201,11 +247,16 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const float* __restrict
   for (long row = r0 + w; row < r1; row += 4) {
     float4 g[LN_MAXV4], xh[LN_MAXV4];
     float s1 = 0.f, s2 = 0.f;
+    unsigned dn = 0, dt = 0;
+    if constexpr (DM != LNB_PLAIN) drop_row(dr.dk, row, dn, dt);
 #pragma unroll
     for (int i = 0; i < LN_MAXV4; ++i) {
       const int c4 = lane + i * 64;
       float4 d = z4, x_ = z4;
       if (c4 < H4) { d = *reinterpret_cast<const float4*>(dy + row * H + c4 * 4); x_ = *reinterpret_cast<const float4*>(xhat + row * H + c4 * 4); }
+      if constexpr (DM == LNB_DROP_DY) {
+        if (c4 < H4) { float f[4]; drop_factors4(dr.dk, c4, dn, dt, f); d.x *= f[0]; d.y *= f[1]; d.z *= f[2]; d.w *= f[3]; }
+      }
       xh[i] = x_;
       g[i] = make_float4(d.x * gm[i].x, d.y * gm[i].y, d.z * gm[i].z, d.w * gm[i].w);
       dg[i].x += d.x * x_.x; dg[i].y += d.y * x_.y; dg[i].z += d.z * x_.z; dg[i].w += d.w * x_.w;
@@ -222,9 +273,19 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const float* __restrict
         float4 o = make_float4(rs * (g[i].x - s1 - xh[i].x * s2), rs * (g[i].y - s1 - xh[i].y * s2),
                                rs * (g[i].z - s1 - xh[i].z * s2), rs * (g[i].w - s1 - xh[i].w * s2));
         if (dx_add) { const float4 a = *reinterpret_cast<const float4*>(dx_add + row * H + c4 * 4); o.x += a.x; o.y += a.y; o.z += a.z; o.w += a.w; }
-        ds[i].x += o.x; ds[i].y += o.y; ds[i].z += o.z; ds[i].w += o.w;
-        if (dxp) { const float ov[4] = {o.x, o.y, o.z, o.w}; planes_store4(dxp, dxplane, row * H + c4 * 4, ov); }
-        else *reinterpret_cast<float4*>(dx + row * H + c4 * 4) = o;
+        if constexpr (DM == LNB_DROP_RES) {
+          if (dxp) { const float ov[4] = {o.x, o.y, o.z, o.w}; planes_store4(dxp, dxplane, row * H + c4 * 4, ov); }
+          else *reinterpret_cast<float4*>(dx + row * H + c4 * 4) = o;
+          float f[4]; drop_factors4(dr.dk, c4, dn, dt, f);
+          o.x *= f[0]; o.y *= f[1]; o.z *= f[2]; o.w *= f[3];
+          ds[i].x += o.x; ds[i].y += o.y; ds[i].z += o.z; ds[i].w += o.w;
+          if (dr.dxmp) { const float ov[4] = {o.x, o.y, o.z, o.w}; planes_store4(dr.dxmp, dxplane, row * H + c4 * 4, ov); }
+          else *reinterpret_cast<float4*>(dr.dxm + row * H + c4 * 4) = o;
+        } else {
+          ds[i].x += o.x; ds[i].y += o.y; ds[i].z += o.z; ds[i].w += o.w;
+          if (dxp) { const float ov[4] = {o.x, o.y, o.z, o.w}; planes_store4(dxp, dxplane, row * H + c4 * 4, ov); }
+          else *reinterpret_cast<float4*>(dx + row * H + c4 * 4) = o;
+        }
       }
     }
   }
@@ -293,10 +354,22 @@ __device__ __forceinline__ void dot2x2(const float* X, const float* Y, int ALD, 
   }
 }
 
+// keep factors of the attention probabilities P[t][4*g..4*g+3] of (sequence n, head hd), applied to an LDS row segment:
+// prow[j - j0] holds key j (j0 = the first key of the segment, a multiple of 4; g = the absolute key group)
+__device__ __forceinline__ void drop_prob_row4(const DropKey& dk, float* prow, int j0, int g, int L, unsigned n, int t, int hd) {
+  float f[4];
+  drop_factors4(dk, (unsigned)g, n, (unsigned)t | ((unsigned)hd << 16), f);
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (4 * g + q < L) prow[4 * g + q - j0] *= f[q];
+}
+
+// DROP: ctx = (keep * s o P) V (BertSelfAttention.dropout on the probabilities); the saved probs stay undropped.
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ qkv, const long* __restrict__ mask, int L,
                                                        int nH, int dH, float scale, float* __restrict__ ctx,
                                                        unsigned short* __restrict__ ctxp, long ctxplane,
-                                                       float* __restrict__ probs) {
+                                                       float* __restrict__ probs, DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ALD = dH + 4;   // 16-byte aligned rows
   float* Qs = smem; float* Ks = Qs + L * ALD; float* Vs = Ks + L * ALD; float* Ps = Vs + L * ALD;  // Ps[L][L+1]
@@ -347,6 +420,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
     }
   }
   __syncthreads();
+  if constexpr (DROP) {
+    const int nj4 = (L + 3) / 4;
+    for (int e = threadIdx.x; e < L * nj4; e += 256)
+      drop_prob_row4(dk, Ps + (e / nj4) * LP, 0, e % nj4, L, (unsigned)(dk.row_offset + b), e / nj4, hd);
+    __syncthreads();
+  }
   const long obase = (long)b * L * (nH * dH) + hd * dH;
   float* out = ctx + obase;
   for (int blk = threadIdx.x; blk < nb * d4; blk += 256) {
@@ -369,13 +448,17 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
 }
 
 // dV = P^T dO ; dP = dO V^T ; dS = P o (dP - rowsum(dP o P)) ; dQ = scale * dS K ; dK = scale * dS^T Q
+// DROP: dV = Pd^T dO and dP = keep * s o (dO V^T), Pd = keep * s o P (kept in a third LDS matrix); dS as above with the undropped P.
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ probs,
                                                        const float* __restrict__ dctx, int L, int nH, int dH, float scale,
-                                                       float* __restrict__ dqkv, unsigned short* __restrict__ dqkvp, long dqkvplane) {
+                                                       float* __restrict__ dqkv, unsigned short* __restrict__ dqkvp, long dqkvplane,
+                                                       DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ALD = dH + 4;
   float* Qs = smem; float* Ks = Qs + L * ALD; float* Vs = Ks + L * ALD; float* Os = Vs + L * ALD;
   float* Ps = Os + L * ALD; float* Ds = Ps + L * (L + 1);  // Ps = P, Ds = dS
+  float* Pv = DROP ? Ds + L * (L + 1) : Ps;                // the probabilities that multiplied V in the forward
   const int b = blockIdx.x / nH, hd = blockIdx.x % nH;
   const int ld = 3 * nH * dH;
   const int d4 = dH / 4;
@@ -402,6 +485,20 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
     Ds[i0 * LP + j0] = o[0][0]; Ds[i0 * LP + j1] = o[0][1]; Ds[i1 * LP + j0] = o[1][0]; Ds[i1 * LP + j1] = o[1][1];
   }
   __syncthreads();
+  if constexpr (DROP) {
+    const int nj4 = (L + 3) / 4;
+    for (int e = threadIdx.x; e < L * nj4; e += 256) {
+      const int row = e / nj4, g = e % nj4;
+      float f[4];
+      drop_factors4(dk, (unsigned)g, (unsigned)(dk.row_offset + b), (unsigned)row | ((unsigned)hd << 16), f);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int j = 4 * g + q;
+        if (j < L) { Ds[row * LP + j] *= f[q]; Pv[row * LP + j] = Ps[row * LP + j] * f[q]; }
+      }
+    }
+    __syncthreads();
+  }
   {
     const int row = threadIdx.x >> 2, sub = threadIdx.x & 3;
     if (row < L) {
@@ -429,7 +526,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
       const float4 oj = *reinterpret_cast<const float4*>(Os + j * ALD + c * 4);
       fma4(q0, Ds[i0 * LP + j], kj); fma4(q1, Ds[i1 * LP + j], kj);   // dQ[i] = sum_j dS[i][j] K[j]
       fma4(k0, Ds[j * LP + i0], qj); fma4(k1, Ds[j * LP + i1], qj);   // dK[i] = sum_j dS[j][i] Q[j]
-      fma4(v0, Ps[j * LP + i0], oj); fma4(v1, Ps[j * LP + i1], oj);   // dV[i] = sum_j P[j][i] dO[j]
+      fma4(v0, Pv[j * LP + i0], oj); fma4(v1, Pv[j * LP + i1], oj);   // dV[i] = sum_j P[j][i] dO[j]
     }
     const long o0 = (long)i0 * ld + c * 4;
     put(o0, q0); put(o0 + nH * dH, k0); put(o0 + 2 * nH * dH, v0);
@@ -470,9 +567,11 @@ __device__ __forceinline__ void dot1x8(const float* X, const float* Y, int ALD, 
   }
 }
 
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const float* __restrict__ qkv, const long* __restrict__ mask, int L, int nH,
                                                             int dH, float scale, float* __restrict__ ctx,
-                                                            unsigned short* __restrict__ ctxp, long ctxplane, float* __restrict__ probs) {
+                                                            unsigned short* __restrict__ ctxp, long ctxplane, float* __restrict__ probs,
+                                                            DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ALD = dH + 4, d4 = dH / 4, LP = L + 1;
   float* Qs = smem; float* Ts = Qs + TQ * ALD; float* Ps = Ts + TK * ALD;     // Ps[TQ][L + 1]
@@ -512,6 +611,11 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const float* __restr
       if (probs && q0 + i < L) probs[(((long)b * nH + hd) * L + q0 + i) * L + j] = pv;
     }
   }
+  if constexpr (DROP) {   // the row's 8 lanes mask it in groups of 4 keys (the value loop below starts with a barrier)
+    __syncthreads();
+    if (q0 + i < L)
+      for (int g = sub; 4 * g < L; g += 8) drop_prob_row4(dk, Ps + i * LP, 0, g, L, (unsigned)(dk.row_offset + b), q0 + i, hd);
+  }
   float4 acc[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};   // columns 4*sub.. and 4*(sub + 8)..
   for (int k0 = 0; k0 < L; k0 += TK) {
     __syncthreads();                                            // softmax done / previous value tile consumed
@@ -536,11 +640,25 @@ __global__ __launch_bounds__(256) void attn_fwd_long_kernel(const float* __restr
   }
 }
 
+// keep factors of the [TQ][TK] probability tile at (q0, k0) of (sequence n, head hd) -> F[TQ][TK + 1] (rows >= L: zero)
+__device__ __forceinline__ void drop_tile(const DropKey& dk, float* F, int q0, int k0, int L, unsigned n, int hd) {
+  constexpr int G = TK / 4;
+  for (int e = threadIdx.x; e < TQ * G; e += 256) {
+    const int ii = e / G, g = e % G;
+    float f[4] = {0.f, 0.f, 0.f, 0.f};
+    if (q0 + ii < L) drop_factors4(dk, (unsigned)(k0 / 4 + g), n, (unsigned)(q0 + ii) | ((unsigned)hd << 16), f);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) F[ii * (TK + 1) + 4 * g + q] = f[q];
+  }
+}
+
 // query-tile pass of the backward: dS rows -> ws [B][nH][L][L], dQ
+// DROP: dP = keep * s o (dO V^T); the factors of each tile are staged in Ds before it holds dS.
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_long_q_kernel(const float* __restrict__ qkv, const float* __restrict__ probs,
                                                               const float* __restrict__ dctx, int L, int nH, int dH, float scale,
                                                               float* __restrict__ dS, float* __restrict__ dqkv,
-                                                              unsigned short* __restrict__ dqkvp, long dqkvplane) {
+                                                              unsigned short* __restrict__ dqkvp, long dqkvplane, DropKey dk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ALD = dH + 4, d4 = dH / 4, DP = TK + 1;
   float* Os = smem; float* Ks = Os + TQ * ALD; float* Vs = Ks + TK * ALD; float* Ds = Vs + TK * ALD;   // Ds[TQ][TK + 1]
@@ -561,12 +679,14 @@ __global__ __launch_bounds__(256) void attn_bwd_long_q_kernel(const float* __res
   for (int k0 = 0; k0 < L; k0 += TK) {
     __syncthreads();
     load_rows(Vs, base + 2 * nH * dH, ld, k0, TK, L, d4, ALD);
+    if constexpr (DROP) drop_tile(dk, Ds, q0, k0, L, (unsigned)(dk.row_offset + b), hd);
     __syncthreads();
     float o[8];
     dot1x8(Os, Vs, ALD, d4, i, sub, o);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const int j = k0 + sub + 8 * c;
+      if constexpr (DROP) o[c] *= Ds[i * DP + sub + 8 * c];
       if (rowok && j < L) t = fmaf(pb[(long)(q0 + i) * L + j], o[c], t);
     }
   }
@@ -577,12 +697,14 @@ __global__ __launch_bounds__(256) void attn_bwd_long_q_kernel(const float* __res
     __syncthreads();
     load_rows(Ks, base + nH * dH, ld, k0, TK, L, d4, ALD);
     load_rows(Vs, base + 2 * nH * dH, ld, k0, TK, L, d4, ALD);
+    if constexpr (DROP) drop_tile(dk, Ds, q0, k0, L, (unsigned)(dk.row_offset + b), hd);
     __syncthreads();
     float o[8];
     dot1x8(Os, Vs, ALD, d4, i, sub, o);
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
       const int jl = sub + 8 * c, j = k0 + jl;
+      if constexpr (DROP) o[c] *= Ds[i * DP + jl];   // read by the thread that overwrites it below
       float v = 0.f;
       if (rowok && j < L) {
         v = pb[(long)(q0 + i) * L + j] * (o[c] - t) * scale;
@@ -610,10 +732,12 @@ __global__ __launch_bounds__(256) void attn_bwd_long_q_kernel(const float* __res
 }
 
 // key-tile pass of the backward: dK_j = sum_i dS_ij Q_i, dV_j = sum_i P_ij dO_i (query tiles in ascending order)
+// DROP: dV_j = sum_i (keep * s * P)_ij dO_i
+template <bool DROP = false>
 __global__ __launch_bounds__(256) void attn_bwd_long_kv_kernel(const float* __restrict__ qkv, const float* __restrict__ probs,
                                                                const float* __restrict__ dS, const float* __restrict__ dctx, int L,
                                                                int nH, int dH, float* __restrict__ dqkv,
-                                                               unsigned short* __restrict__ dqkvp, long dqkvplane) {
+                                                               unsigned short* __restrict__ dqkvp, long dqkvplane, DropKey dkey) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int ALD = dH + 4, d4 = dH / 4, DP = TK + 1;
   float* Qs = smem; float* Os = Qs + TQ * ALD; float* Pt = Os + TQ * ALD; float* Dt = Pt + TQ * DP;   // Pt, Dt: [TQ][TK + 1]
@@ -639,6 +763,13 @@ __global__ __launch_bounds__(256) void attn_bwd_long_kv_kernel(const float* __re
       const long o = (long)(q0 + ii) * L + k0 + jj;
       Pt[ii * DP + jj] = ok ? pb[o] : 0.f;
       Dt[ii * DP + jj] = ok ? dsb[o] : 0.f;
+    }
+    if constexpr (DROP) {   // P -> keep * s * P, four keys per draw
+      __syncthreads();
+      for (int e = threadIdx.x; e < TQ * TK / 4; e += 256) {
+        const int ii = e / (TK / 4), g = e % (TK / 4);
+        if (q0 + ii < L) drop_prob_row4(dkey, Pt + ii * DP, k0, k0 / 4 + g, L, (unsigned)(dkey.row_offset + b), q0 + ii, hd);
+      }
     }
     __syncthreads();
     for (int ii = 0; ii < TQ; ++ii) {
@@ -723,7 +854,7 @@ extern "C" int cxrk_embed_ln_fwd(const long* ids, const float* word, const float
   if (v8)
     hipLaunchKernelGGL((ln_fwd_vec8_kernel<true>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, stream, nullptr, nullptr, ids, word, pos,
                        type, gamma, beta, eps, T, H, L, yplane ? nullptr : static_cast<float*>(y),
-                       yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd);
+                       yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, LnFwdDrop{});
   else
     hipLaunchKernelGGL((ln_fwd_kernel<true>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, stream, nullptr, nullptr, ids, word,
                        pos, type, gamma, beta, eps, T, H, L, static_cast<float*>(y), xhat, rstd);
@@ -739,7 +870,7 @@ extern "C" int cxrk_residual_ln_fwd(const float* x, const float* res, const floa
   if (v8)
     hipLaunchKernelGGL((ln_fwd_vec8_kernel<false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, res, nullptr, nullptr,
                        nullptr, nullptr, gamma, beta, eps, rows, H, 1, yplane ? nullptr : static_cast<float*>(y),
-                       yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd);
+                       yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, LnFwdDrop{});
   else
     hipLaunchKernelGGL((ln_fwd_kernel<false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, res, nullptr, nullptr,
                        nullptr, nullptr, gamma, beta, eps, rows, H, 1, static_cast<float*>(y), xhat, rstd);
@@ -770,7 +901,8 @@ extern "C" int cxrk_residual_ln_bwd(const float* dy, const float* xhat, const fl
                    (dxplane % 4) == 0;
   if ((dxp || dxsum) && !vec) return CXRK_ERR_ARG;
   if (vec)
-    hipLaunchKernelGGL(ln_bwd_vec_kernel, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp, dxplane, dx_add, ws, np);
+    hipLaunchKernelGGL(ln_bwd_vec_kernel<>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp, dxplane, dx_add, ws, np,
+                       LnBwdDrop{});
   else
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dx_add, ws);
   CXRK_LAUNCH_CHECK();
@@ -791,24 +923,24 @@ extern "C" int cxrk_attn_fwd(const float* qkv, const long* mask, int B, int L, i
     const size_t shl = (size_t)((TQ + TK) * ALD + TQ * (L + 1)) * sizeof(float);
     static bool attr_long = false;
     if (!attr_long) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(((TQ + TK) * (AD + 4) + TQ * (ALONG + 1)) * sizeof(float)));
       attr_long = true;
     }
-    hipLaunchKernelGGL(attn_fwd_long_kernel, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shl, stream, qkv, mask, L, nH, dH,
-                       1.0f / sqrtf((float)dH), ctx, ctxp, ctxplane, probs);
+    hipLaunchKernelGGL(attn_fwd_long_kernel<>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shl, stream, qkv, mask, L, nH, dH,
+                       1.0f / sqrtf((float)dH), ctx, ctxp, ctxplane, probs, DropKey{});
     CXRK_LAUNCH_CHECK();
     return CXRK_OK;
   }
   const size_t sh = (size_t)(3 * L * ALD + L * (L + 1)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)((3 * AL * (AD + 4) + AL * (AL + 1)) * sizeof(float)));
     attr_set = true;
   }
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, mask, L, nH, dH,
-                     1.0f / sqrtf((float)dH), ctx, ctxp, ctxplane, probs);
+  hipLaunchKernelGGL(attn_fwd_kernel<>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, mask, L, nH, dH,
+                     1.0f / sqrtf((float)dH), ctx, ctxp, ctxplane, probs, DropKey{});
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }
@@ -832,23 +964,211 @@ extern "C" int cxrk_attn_bwd(const float* qkv, const float* probs, const float* 
     const float scale = 1.0f / sqrtf((float)dH);
     const size_t shq = (size_t)((TQ + 2 * TK) * ALD + TQ * (TK + 1)) * sizeof(float);
     const size_t shk = (size_t)(2 * TQ * ALD + 2 * TQ * (TK + 1)) * sizeof(float);
-    hipLaunchKernelGGL(attn_bwd_long_q_kernel, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L, nH,
-                       dH, scale, ws, dqkv, dqkvp, dqkvplane);
+    hipLaunchKernelGGL(attn_bwd_long_q_kernel<>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L, nH,
+                       dH, scale, ws, dqkv, dqkvp, dqkvplane, DropKey{});
     CXRK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_bwd_long_kv_kernel, dim3((unsigned)(B * nH * ceil_div(L, TK))), dim3(256), shk, stream, qkv, probs, ws, dctx, L,
-                       nH, dH, dqkv, dqkvp, dqkvplane);
+    hipLaunchKernelGGL(attn_bwd_long_kv_kernel<>, dim3((unsigned)(B * nH * ceil_div(L, TK))), dim3(256), shk, stream, qkv, probs, ws, dctx, L,
+                       nH, dH, dqkv, dqkvp, dqkvplane, DropKey{});
     CXRK_LAUNCH_CHECK();
     return CXRK_OK;
   }
   const size_t sh = (size_t)(4 * L * ALD + 2 * L * (L + 1)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize,
                         (int)((4 * AL * (AD + 4) + 2 * AL * (AL + 1)) * sizeof(float)));
     attr_set = true;
   }
-  hipLaunchKernelGGL(attn_bwd_kernel, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, probs, dctx, L, nH, dH,
-                     1.0f / sqrtf((float)dH), dqkv, dqkvp, dqkvplane);
+  hipLaunchKernelGGL(attn_bwd_kernel<>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, probs, dctx, L, nH, dH,
+                     1.0f / sqrtf((float)dH), dqkv, dqkvp, dqkvplane, DropKey{});
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+// ---- dropout (train mode): the DROP instantiations of the kernels above and the mask generator --------------------------------
+namespace {
+
+__global__ __launch_bounds__(256) void dropout_mask_kernel(DropKey dk, int N, int L, int nH, int C, unsigned char* __restrict__ keep) {
+  // logical shape [N][nH][L][C]; one thread per 4 columns (one Philox block)
+  const int C4 = (C + 3) / 4;
+  const long total = (long)N * nH * L * C4;
+  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
+    const int g = (int)(e % C4);
+    const long r = e / C4;                  // ((n * nH + h) * L + t)
+    const int t = (int)(r % L), h = (int)((r / L) % nH), n = (int)(r / ((long)L * nH));
+    float f[4];
+    drop_factors4(dk, (unsigned)g, (unsigned)(dk.row_offset + n), (unsigned)t | ((unsigned)h << 16), f);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (4 * g + q < C) keep[r * C + 4 * g + q] = f[q] != 0.f;
+  }
+}
+
+}  // namespace
+
+static int make_drop(unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p, int rows_per_seq,
+                     DropKey& d) {
+  if (!(p >= 0.f && p < 1.f) || layer < 0 || layer > 63 || site < 0 || site > 3 || row_offset < 0 || rows_per_seq < 1) return CXRK_ERR_ARG;
+  d.k0 = (unsigned)(seed & 0xffffffffull);
+  d.k1 = (unsigned)(seed >> 32);
+  d.c3 = ((counter & 0xffffffu) << 8) | ((unsigned)layer << 2) | (unsigned)site;
+  d.thresh = (unsigned)floor((double)p * 4294967296.0 + 0.5);
+  d.scale = 1.0f / (1.0f - p);
+  d.row_offset = row_offset;
+  d.rows_per_seq = rows_per_seq;
+  return CXRK_OK;
+}
+#define CXRK_MAKE_DROP(rps, d)                                                              \
+  DropKey d;                                                                                \
+  if (make_drop(seed, counter, layer, site, row_offset, p, (rps), d) != CXRK_OK) return CXRK_ERR_ARG
+
+extern "C" int cxrk_dropout_mask(unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p, int N, int L,
+                                 int nH, int C, unsigned char* keep, hipStream_t stream) {
+  CXRK_CHECK_ARG(keep && N > 0 && L > 0 && nH > 0 && nH < 65536 && L < 65536 && C > 0);
+  CXRK_MAKE_DROP(1, dk);
+  long nb = ((long)N * nH * L * ((C + 3) / 4) + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  hipLaunchKernelGGL(dropout_mask_kernel, dim3((unsigned)nb), dim3(256), 0, stream, dk, N, L, nH, C, keep);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_embed_ln_fwd_drop(const long* ids, const float* word, const float* pos, const float* type, const float* gamma,
+                                      const float* beta, float eps, long T, int L, int H, void* y, long yplane, float* xhat, float* rstd,
+                                      unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                                      hipStream_t stream) {
+  CXRK_CHECK_ARG(ids && word && pos && type && gamma && beta && y && T > 0 && L > 0 && H > 0 && H <= 64 * LN_MAXV && yplane >= 0);
+  if (!(ln_vec8_ok(H, word, pos, type, gamma, beta, y) && aligned16(xhat) && (yplane % 8) == 0)) return CXRK_ERR_UNSUPPORTED;
+  LnFwdDrop dr{};
+  if (make_drop(seed, counter, layer, site, row_offset, p, L, dr.dk) != CXRK_OK) return CXRK_ERR_ARG;
+  hipLaunchKernelGGL((ln_fwd_vec8_kernel<true, true>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, stream, nullptr, nullptr, ids, word, pos,
+                     type, gamma, beta, eps, T, H, L, yplane ? nullptr : static_cast<float*>(y),
+                     yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, dr);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_residual_ln_fwd_drop(const float* x, const void* res, long resplane, long res_ld, const float* gamma, const float* beta,
+                                         float eps, long rows, int H, int rows_per_seq, void* y, long yplane, float* xhat, float* rstd,
+                                         unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                                         hipStream_t stream) {
+  CXRK_CHECK_ARG(x && gamma && beta && y && rows > 0 && H > 0 && H <= 64 * LN_MAXV && yplane >= 0 && resplane >= 0 && res_ld >= 0);
+  if (!(ln_vec8_ok(H, x, res, gamma, beta, y, xhat) && (yplane % 8) == 0 && (resplane % 8) == 0 && (res_ld % 8) == 0))
+    return CXRK_ERR_UNSUPPORTED;
+  LnFwdDrop dr{};
+  if (make_drop(seed, counter, layer, site, row_offset, p, rows_per_seq, dr.dk) != CXRK_OK) return CXRK_ERR_ARG;
+  dr.resp = resplane ? static_cast<const unsigned short*>(res) : nullptr;
+  dr.resplane = resplane;
+  dr.res_ld = res_ld ? res_ld : H;
+  hipLaunchKernelGGL((ln_fwd_vec8_kernel<false, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x,
+                     resplane ? nullptr : static_cast<const float*>(res), nullptr, nullptr, nullptr, nullptr, gamma, beta, eps, rows, H, 1,
+                     yplane ? nullptr : static_cast<float*>(y), yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, dr);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_residual_ln_bwd_drop(const float* dy, const float* xhat, const float* rstd, const float* gamma, long rows, int H,
+                                         int rows_per_seq, int mode, const float* dx_add, void* dxv, void* dxmv, long dxplane, float* dgamma,
+                                         float* dbeta, int accumulate, float* dxsum, int dxsum_accumulate, float* ws, size_t ws_bytes,
+                                         unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                                         hipStream_t stream) {
+  CXRK_CHECK_ARG(dy && xhat && rstd && gamma && dxv && dgamma && dbeta && rows > 0 && H > 0 && H <= 64 * LN_MAXV && dxplane >= 0 &&
+                 (mode == LNB_DROP_RES || mode == LNB_DROP_DY) && ((mode == LNB_DROP_RES) == (dxmv != nullptr)));
+  int nb = ln_bwd_blocks(rows);
+  if (ws == nullptr || ws_bytes < (size_t)nb * 3 * H * sizeof(float)) return CXRK_ERR_WS;
+  const bool vec = (H % 4 == 0) && aligned16(dy) && aligned16(xhat) && aligned16(gamma) && aligned16(dxv) && (!dxmv || aligned16(dxmv)) &&
+                   (!dx_add || aligned16(dx_add)) && (dxplane % 4) == 0;
+  if (!vec) return CXRK_ERR_UNSUPPORTED;
+  LnBwdDrop dr{};
+  if (make_drop(seed, counter, layer, site, row_offset, p, rows_per_seq, dr.dk) != CXRK_OK) return CXRK_ERR_ARG;
+  dr.dxm = dxplane ? nullptr : static_cast<float*>(dxmv);
+  dr.dxmp = dxplane ? static_cast<unsigned short*>(dxmv) : nullptr;
+  float* dx = dxplane ? nullptr : static_cast<float*>(dxv);
+  unsigned short* dxp = dxplane ? static_cast<unsigned short*>(dxv) : nullptr;
+  const int np = dxsum ? 3 : 2;
+  const int rows_per = (int)((rows + nb - 1) / nb);
+  nb = (int)((rows + rows_per - 1) / rows_per);
+  if (mode == LNB_DROP_RES)
+    hipLaunchKernelGGL(ln_bwd_vec_kernel<LNB_DROP_RES>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp,
+                       dxplane, dx_add, ws, np, dr);
+  else
+    hipLaunchKernelGGL(ln_bwd_vec_kernel<LNB_DROP_DY>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp,
+                       dxplane, dx_add, ws, np, dr);
+  CXRK_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ln_bwd_final_kernel, dim3(ceil_div(H, 64), np), dim3(1024), 0, stream, ws, nb, np, H, dgamma, dbeta, accumulate, dxsum,
+                     dxsum_accumulate);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_attn_fwd_drop(const float* qkv, const long* mask, int B, int L, int nH, int dH, void* ctxv, long ctxplane, float* probs,
+                                  unsigned long long seed, unsigned counter, int layer, int site, long row_offset, float p,
+                                  hipStream_t stream) {
+  CXRK_CHECK_ARG(qkv && ctxv && B > 0 && nH > 0 && nH < 65536 && aligned16(qkv) && aligned16(ctxv) && ctxplane >= 0 && (ctxplane % 4) == 0);
+  CXRK_MAKE_DROP(1, dk);
+  float* ctx = ctxplane ? nullptr : static_cast<float*>(ctxv);
+  unsigned short* ctxp = ctxplane ? static_cast<unsigned short*>(ctxv) : nullptr;
+  if (dH > AD || dH < 4 || (dH % 4) != 0 || L > ALONG || L < 1) return CXRK_ERR_UNSUPPORTED;
+  const int ALD = dH + 4;
+  const float scale = 1.0f / sqrtf((float)dH);
+  if (L > AL) {
+    const size_t shl = (size_t)((TQ + TK) * ALD + TQ * (L + 1)) * sizeof(float);
+    static bool attr_long = false;
+    if (!attr_long) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(((TQ + TK) * (AD + 4) + TQ * (ALONG + 1)) * sizeof(float)));
+      attr_long = true;
+    }
+    hipLaunchKernelGGL(attn_fwd_long_kernel<true>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shl, stream, qkv, mask, L, nH, dH,
+                       scale, ctx, ctxp, ctxplane, probs, dk);
+    CXRK_LAUNCH_CHECK();
+    return CXRK_OK;
+  }
+  const size_t sh = (size_t)(3 * L * ALD + L * (L + 1)) * sizeof(float);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((3 * AL * (AD + 4) + AL * (AL + 1)) * sizeof(float)));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, mask, L, nH, dH, scale, ctx, ctxp, ctxplane,
+                     probs, dk);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_attn_bwd_drop(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH, void* dqkvv,
+                                  long dqkvplane, float* ws, size_t ws_bytes, unsigned long long seed, unsigned counter, int layer, int site,
+                                  long row_offset, float p, hipStream_t stream) {
+  CXRK_CHECK_ARG(qkv && probs && dctx && dqkvv && B > 0 && nH > 0 && nH < 65536 && aligned16(qkv) && aligned16(dctx) && aligned16(dqkvv) &&
+                 dqkvplane >= 0 && (dqkvplane % 4) == 0);
+  CXRK_MAKE_DROP(1, dk);
+  float* dqkv = dqkvplane ? nullptr : static_cast<float*>(dqkvv);
+  unsigned short* dqkvp = dqkvplane ? static_cast<unsigned short*>(dqkvv) : nullptr;
+  if (dH > AD || dH < 4 || (dH % 4) != 0 || L > ALONG || L < 1) return CXRK_ERR_UNSUPPORTED;
+  const int ALD = dH + 4;
+  const float scale = 1.0f / sqrtf((float)dH);
+  if (L > AL) {
+    if (ws == nullptr || ws_bytes < cxrk_attn_bwd_ws_bytes(B, L, nH, dH)) return CXRK_ERR_WS;
+    const size_t shq = (size_t)((TQ + 2 * TK) * ALD + TQ * (TK + 1)) * sizeof(float);
+    const size_t shk = (size_t)(2 * TQ * ALD + 2 * TQ * (TK + 1)) * sizeof(float);
+    hipLaunchKernelGGL(attn_bwd_long_q_kernel<true>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L,
+                       nH, dH, scale, ws, dqkv, dqkvp, dqkvplane, dk);
+    CXRK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(attn_bwd_long_kv_kernel<true>, dim3((unsigned)(B * nH * ceil_div(L, TK))), dim3(256), shk, stream, qkv, probs, ws, dctx,
+                       L, nH, dH, dqkv, dqkvp, dqkvplane, dk);
+    CXRK_LAUNCH_CHECK();
+    return CXRK_OK;
+  }
+  const size_t sh = (size_t)(4 * L * ALD + 3 * L * (L + 1)) * sizeof(float);   // + the dropped probabilities
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((4 * AL * (AD + 4) + 3 * AL * (AL + 1)) * sizeof(float)));
+    attr_set = true;
+  }
+  hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, probs, dctx, L, nH, dH, scale, dqkv, dqkvp,
+                     dqkvplane, dk);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }

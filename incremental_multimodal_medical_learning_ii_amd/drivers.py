@@ -73,6 +73,8 @@ def _joint_models(args, device):
         engine = T.TextInferenceEngine(T.SyntheticTokenizer(2048), tm.eval().to(device))
     else:
         engine = T.get_cxr_bert_inference(args.pretrained_text, device="cuda")
+    if getattr(args, "text_dropout", False):   # HF train-mode dropout in the training loop (Trainer._set_mode), eval for scoring
+        engine.model.enable_dropout_()
     return im, engine
 
 
@@ -227,12 +229,17 @@ def make_parser():
     ap.add_argument("--image-size", type=int, default=224)
     ap.add_argument("--seq-len", type=int, default=32)
     ap.add_argument("--small-text", action="store_true", help="--joint: a 2-layer text model instead of the 12-layer CXR-BERT (quick runs)")
+    ap.add_argument("--text-dropout", action="store_true",
+                    help="--joint: train the text model in train mode with HF dropout (CXRBertModel.enable_dropout_); default: eval mode")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
 
 def main(argv=None):
     args = make_parser().parse_args(argv)
+    if args.text_dropout and not args.joint:
+        raise SystemExit("--text-dropout trains the text encoder in-loop and needs --joint (the adapter schedules use frozen "
+                         "pre-computed text embeddings)")
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)
     if int(os.environ.get("RANK", "0")) == 0:

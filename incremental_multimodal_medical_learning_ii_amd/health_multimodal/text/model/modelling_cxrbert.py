@@ -70,6 +70,62 @@ class CXRBertModel(BertForMaskedLM):
         # optional callable(tag): handed to every grad-enabled encode call made while it is set and called by THAT call's backward
         # when its parameter gradients are complete (text_encoder.encode); set and cleared by the data-parallel trainer per step
         self.grad_ready_hook = None
+        # train-mode dropout: None until `enable_dropout_`; then [seed, call counter]
+        self._dropout: Optional[List[int]] = None
+        # bumped whenever the stream is (re)seeded or assigned, so a data-parallel trainer knows when to re-broadcast rank 0's state
+        self._dropout_version = 0
+        # global sequence index of this process's first row (data parallel: rank * local rows; set by the joint trainer)
+        self.dropout_row_offset = 0
+
+    # ------------------------------------------------------------------ dropout
+    def enable_dropout_(self, seed: Optional[int] = None) -> "CXRBertModel":
+        """Opt in to HF dropout in train mode (p = config.hidden_dropout_prob / attention_probs_dropout_prob at BertModel's four
+        sites).  Masks are counter-based (include/cxrk.h, "dropout"): keyed by (seed, call counter, layer, site, global sequence
+        index, token, column).  seed=None draws one 64-bit seed from torch's default CPU generator (`torch.manual_seed` makes it
+        repeatable).  Each train-mode forward uses the current (seed, counter) and then advances the counter; the kernels key the
+        masks by the low 24 bits of the counter, so the mask stream of one seed repeats after 2^24 train-mode calls (re-seed before).
+        Data parallel: `contrastive.JointContrastiveTrainer` gives every rank rank 0's (seed, counter) -- at construction, and again
+        at the next step whenever this method or the `dropout_state` setter has been called since -- so the ranks may seed
+        differently."""
+        if seed is None:
+            w = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64)
+            seed = (int(w[0]) << 32) | int(w[1])
+        self._dropout = [int(seed) & (2 ** 64 - 1), 0]
+        self._dropout_version += 1
+        return self
+
+    @property
+    def dropout_enabled(self) -> bool:
+        return self._dropout is not None
+
+    @property
+    def dropout_state(self) -> Optional[Tuple[int, int]]:
+        """(seed, call counter) of the next train-mode forward; None before `enable_dropout_`.  Assign a pair to resume a stream
+        (only on a model that opted in with `enable_dropout_`).  Counters that differ by a multiple of 2^24 give the same masks."""
+        return None if self._dropout is None else (self._dropout[0], self._dropout[1])
+
+    @dropout_state.setter
+    def dropout_state(self, state: Tuple[int, int]) -> None:
+        if self._dropout is None:
+            raise RuntimeError("dropout_state: this model has not opted in to dropout; call enable_dropout_(seed) first")
+        seed, counter = state
+        if int(counter) < 0:
+            raise ValueError("dropout_state: the call counter must be >= 0")
+        self._dropout = [int(seed) & (2 ** 64 - 1), int(counter)]
+        self._dropout_version += 1
+
+    def _dropout_probs(self) -> Tuple[float, float]:
+        cfg = self.config
+        return float(getattr(cfg, "hidden_dropout_prob", 0.0) or 0.0), float(getattr(cfg, "attention_probs_dropout_prob", 0.0) or 0.0)
+
+    def _next_dropout(self) -> Optional[TE.Dropout]:
+        """the dropout descriptor of this call (advancing the counter), or None when the call has eval semantics"""
+        ph, pa = self._dropout_probs()
+        if not self.training or self._dropout is None or (ph <= 0 and pa <= 0):
+            return None
+        seed, counter = self._dropout
+        self._dropout[1] = counter + 1
+        return TE.Dropout(seed, counter, self.dropout_row_offset, ph, pa)
 
     # ------------------------------------------------------------------ parameter plumbing
     def _hot_params(self) -> List[nn.Parameter]:
@@ -88,12 +144,14 @@ class CXRBertModel(BertForMaskedLM):
         return self
 
     def _check_mode(self) -> None:
-        """Dropout is not implemented; the reference only ever runs the text model in eval mode
-        (text/inference_engine.py:63 asserts it).  Refuse rather than silently skip the dropout of a training-mode model."""
-        cfg = self.config
-        if self.training and (getattr(cfg, "hidden_dropout_prob", 0.0) > 0 or getattr(cfg, "attention_probs_dropout_prob", 0.0) > 0):
-            raise NotImplementedError("CXRBertModel is in training mode with dropout > 0, which the HIP path does not implement; "
-                                      "call .eval() (parameters still receive gradients) or set the dropout probabilities to 0")
+        """Dropout is opt-in (`enable_dropout_`); the reference only ever runs the text model in eval mode
+        (text/inference_engine.py:63 asserts it).  Refuse rather than silently skip the dropout of a training-mode model that did
+        not opt in."""
+        ph, pa = self._dropout_probs()
+        if self.training and (ph > 0 or pa > 0) and self._dropout is None:
+            raise NotImplementedError("CXRBertModel is in training mode with dropout > 0 but dropout was not enabled; call "
+                                      ".enable_dropout_(seed) for HF train-mode dropout, .eval() (parameters still receive gradients), "
+                                      "or set the dropout probabilities to 0")
 
     def _encode(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor], cls_only: bool = False, want_last: bool = True):
         if not input_ids.is_cuda:
@@ -106,7 +164,7 @@ class CXRBertModel(BertForMaskedLM):
             raise NotImplementedError(f"hidden_act={cfg.hidden_act!r}: only erf-GELU (CXR-BERT) is implemented")
         return TE.encode(self._hot_params(), input_ids, attention_mask, cfg.num_hidden_layers,
                          cfg.num_attention_heads, cfg.layer_norm_eps, cls_only, want_last,
-                         on_grads_ready=self.grad_ready_hook if torch.is_grad_enabled() else None)
+                         on_grads_ready=self.grad_ready_hook if torch.is_grad_enabled() else None, dropout=self._next_dropout())
 
     @torch.no_grad()
     def _mlm_logits(self, last_hidden: torch.Tensor) -> torch.Tensor:

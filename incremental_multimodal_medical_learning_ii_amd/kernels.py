@@ -6,7 +6,7 @@ falls back to torch arithmetic.
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
 import torch
 
@@ -842,7 +842,32 @@ def _new_out(rows, cols, device, planes: bool):
     return o, o.data_ptr(), 0
 
 
-def embed_ln_fwd(ids, word, pos, type_row, gamma, beta, eps, L, out_planes: bool = False):
+class Drop(NamedTuple):
+    """Dropout descriptor of one site of one call (include/cxrk.h, "dropout"): the keep mask is a pure function of these values and
+    of the element's (sequence, token, head, column)."""
+    seed: int
+    counter: int
+    layer: int
+    site: int
+    row_offset: int
+    p: float
+
+    def args(self):
+        return (self.seed & (2 ** 64 - 1), self.counter & 0xFFFFFFFF, self.layer, self.site, self.row_offset, float(self.p))
+
+
+DROP_EMBED, DROP_ATTN_PROBS, DROP_ATTN_OUT, DROP_FFN_OUT = 0, 1, 2, 3
+
+
+def dropout_mask(drop: Drop, N: int, L: int, C: int, nH: int = 1, device="cuda") -> torch.Tensor:
+    """uint8 keep mask [N, nH, L, C] of one site (hidden sites: nH = 1, C = H, i.e. the [N*L, H] activation)."""
+    keep = torch.empty(N, nH, L, C, dtype=torch.uint8, device=device)
+    check(_lib.load().cxrk_dropout_mask(*drop.args(), N, L, nH, C, _p(keep), _stream()), "cxrk_dropout_mask")
+    return keep
+
+
+def embed_ln_fwd(ids, word, pos, type_row, gamma, beta, eps, L, out_planes: bool = False, drop: Optional[Drop] = None):
+    """drop: y = keep * s * LayerNorm(...) (BertEmbeddings.dropout); xhat / rstd stay those of the LayerNorm."""
     lib = _lib.load()
     _chk(ids, "embed.ids", torch.int64)
     ids = ids.contiguous()
@@ -851,17 +876,38 @@ def embed_ln_fwd(ids, word, pos, type_row, gamma, beta, eps, L, out_planes: bool
     y, yp, ypl = _new_out(T, H, word.device, out_planes)
     xhat = torch.empty(T, H, dtype=torch.float32, device=word.device)
     rstd = torch.empty(T, dtype=torch.float32, device=word.device)
+    if drop is not None:
+        check(lib.cxrk_embed_ln_fwd_drop(_p(ids), _p(_chk(word, "embed.word")), _p(pos), _p(type_row), _p(gamma), _p(beta),
+                                         float(eps), T, L, H, yp, ypl, _p(xhat), _p(rstd), *drop.args(), _stream()),
+              "cxrk_embed_ln_fwd_drop")
+        return y, xhat, rstd
     check(lib.cxrk_embed_ln_fwd(_p(ids), _p(_chk(word, "embed.word")), _p(pos), _p(type_row), _p(gamma), _p(beta),
                                 float(eps), T, L, H, yp, ypl, _p(xhat), _p(rstd), _stream()), "cxrk_embed_ln_fwd")
     return y, xhat, rstd
 
 
-def residual_ln_fwd(x, res, gamma, beta, eps, save: bool = True, out_planes: bool = False):
+def residual_ln_fwd(x, res, gamma, beta, eps, save: bool = True, out_planes: bool = False, drop: Optional[Drop] = None,
+                    rows_per_seq: int = 1):
+    """y = LayerNorm(x + res); with `drop`: y = LayerNorm(keep * s * x + res), `res` fp32 or Planes (rows may be strided, e.g. the
+    CLS rows), `rows_per_seq` = rows of x per sequence (L, or 1 for CLS rows)."""
     lib = _lib.load()
     rows, H = x.shape
     y, yp, ypl = _new_out(rows, H, x.device, out_planes)
     xhat = torch.empty_like(x) if save else None
     rstd = torch.empty(rows, dtype=torch.float32, device=x.device) if save else None
+    if drop is not None:
+        if res is None:
+            raise ValueError("residual_ln_fwd(drop=...): the residual is required")
+        if isinstance(res, Planes):
+            rp, rld, rpl = _pl2d(res, "ln.res")
+        else:
+            _chk(res, "ln.res")
+            if res.stride(1) != 1:
+                raise ValueError("ln.res: columns must be contiguous")
+            rp, rld, rpl = res.data_ptr(), res.stride(0), 0
+        check(lib.cxrk_residual_ln_fwd_drop(_p(_chk(x, "ln.x")), rp, rpl, rld, _p(gamma), _p(beta), float(eps), rows, H, int(rows_per_seq),
+                                            yp, ypl, _p(xhat), _p(rstd), *drop.args(), _stream()), "cxrk_residual_ln_fwd_drop")
+        return y, xhat, rstd
     check(lib.cxrk_residual_ln_fwd(_p(_chk(x, "ln.x")), _p(res), _p(gamma), _p(beta), float(eps), rows, H, yp, ypl,
                                    _p(xhat), _p(rstd), _stream()), "cxrk_residual_ln_fwd")
     return y, xhat, rstd
@@ -887,22 +933,50 @@ def residual_ln_bwd(dy, xhat, rstd, gamma, dgamma, dbeta, dx_add=None, accumulat
     return dx
 
 
-def attn_fwd(qkv, mask, B, L, nH, dH, save_probs: bool = True, out_planes: bool = False):
+def residual_ln_bwd_drop(dy, xhat, rstd, gamma, dgamma, dbeta, drop: Drop, rows_per_seq: int, accumulate: bool = False,
+                         out_planes: bool = False, dxsum=None, dxsum_accumulate: bool = False, mask_dy: bool = False):
+    """Backward of y = LayerNorm(keep * s * x + res): returns (dsum, dxm) -- dsum = the gradient of the sum (the residual path), dxm =
+    keep * s * dsum (the dense output's gradient), both fp32 or both Planes; `dxsum` receives the column sums of dxm.
+    mask_dy: backward of y = keep * s * LayerNorm(x) instead (the embeddings): returns (dx, None)."""
+    lib = _lib.load()
+    rows, H = dy.shape
+    dx, dxp, dxpl = _new_out(rows, H, dy.device, out_planes)
+    dxm, dxmp = (None, None) if mask_dy else _new_out(rows, H, dy.device, out_planes)[:2]
+    wsb = lib.cxrk_residual_ln_bwd_ws_bytes(rows, H)
+    ws = workspace(wsb, dy.device)
+    check(lib.cxrk_residual_ln_bwd_drop(_p(_chk(dy, "ln.dy")), _p(xhat), _p(rstd), _p(gamma), rows, H, int(rows_per_seq),
+                                        2 if mask_dy else 1, None, dxp, dxmp, dxpl, _p(dgamma), _p(dbeta), int(accumulate), _p(dxsum),
+                                        int(dxsum_accumulate), _p(ws), ws.numel() * 4, *drop.args(), _stream()),
+          "cxrk_residual_ln_bwd_drop")
+    return dx, dxm
+
+
+def attn_fwd(qkv, mask, B, L, nH, dH, save_probs: bool = True, out_planes: bool = False, drop: Optional[Drop] = None):
+    """drop: ctx = (keep * s o P) V; the saved probs stay undropped."""
     lib = _lib.load()
     ctx, cp, cpl = _new_out(B * L, nH * dH, qkv.device, out_planes)
     probs = torch.empty(B, nH, L, L, dtype=torch.float32, device=qkv.device) if save_probs else None
     if mask is not None:
         _chk(mask, "attn.mask", torch.int64)
+    if drop is not None:
+        check(lib.cxrk_attn_fwd_drop(_p(_chk(qkv, "attn.qkv")), _p(mask), B, L, nH, dH, cp, cpl, _p(probs), *drop.args(), _stream()),
+              f"cxrk_attn_fwd_drop(B={B},L={L},nH={nH},dH={dH})")
+        return ctx, probs
     check(lib.cxrk_attn_fwd(_p(_chk(qkv, "attn.qkv")), _p(mask), B, L, nH, dH, cp, cpl, _p(probs), _stream()),
           f"cxrk_attn_fwd(B={B},L={L},nH={nH},dH={dH})")
     return ctx, probs
 
 
-def attn_bwd(qkv, probs, dctx, B, L, nH, dH, out_planes: bool = False):
+def attn_bwd(qkv, probs, dctx, B, L, nH, dH, out_planes: bool = False, drop: Optional[Drop] = None):
     lib = _lib.load()
     dqkv, dp, dpl = _new_out(qkv.shape[0], qkv.shape[1], qkv.device, out_planes)
     wsb = lib.cxrk_attn_bwd_ws_bytes(B, L, nH, dH)        # the dS matrix of the tiled form (L > 64); 0 otherwise
     ws = workspace(wsb, qkv.device) if wsb else None
+    if drop is not None:
+        check(lib.cxrk_attn_bwd_drop(_p(qkv), _p(probs), _p(_chk(dctx, "attn.dctx")), B, L, nH, dH, dp, dpl, _p(ws),
+                                     ws.numel() * 4 if ws is not None else 0, *drop.args(), _stream()),
+              f"cxrk_attn_bwd_drop(B={B},L={L},nH={nH},dH={dH})")
+        return dqkv
     check(lib.cxrk_attn_bwd(_p(qkv), _p(probs), _p(_chk(dctx, "attn.dctx")), B, L, nH, dH, dp, dpl, _p(ws),
                             ws.numel() * 4 if ws is not None else 0, _stream()), f"cxrk_attn_bwd(B={B},L={L},nH={nH},dH={dH})")
     return dqkv

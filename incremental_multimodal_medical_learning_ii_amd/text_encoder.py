@@ -2,8 +2,13 @@
 
 Arithmetic follows HuggingFace `BertForMaskedLM` as the reference drives it
 (`health_multimodal/text/model/modelling_cxrbert.py:87-99`: `hidden_states[-1][:, 0, :]` -> `BertProjectionHead`,
-`:43-49`), post-LN, erf-GELU, LayerNorm eps = config.layer_norm_eps (1e-12), additive key mask, dropout inactive.
+`:43-49`), post-LN, erf-GELU, LayerNorm eps = config.layer_norm_eps (1e-12), additive key mask.
 The MLM head the reference computes and discards on this path (`:87-95`) is not computed here.
+
+Dropout (train mode, opt-in: `CXRBertModel.enable_dropout_`): a `Dropout` descriptor (seed, call counter, row offset, the two
+probabilities) switches on HF BertModel's four dropout sites -- embeddings, attention probabilities, attention output, FFN output --
+inside the LayerNorm / attention kernels (include/cxrk.h, "dropout").  Without a descriptor the eval-mode path runs unchanged.
+Masks are regenerated in the backward from the same descriptor, never stored.
 
 Q, K and V projections run as ONE [3H, H] GEMM per layer: `fuse_qkv_` re-points the three nn.Parameter tensors
 of a layer at consecutive slices of one buffer (state-dict names and values unchanged).
@@ -76,6 +81,23 @@ def fuse_qkv_(q: torch.nn.Parameter, k: torch.nn.Parameter, v: torch.nn.Paramete
     v.data = buf[2 * h:3 * h].view(v.shape)
 
 
+class Dropout:
+    """Dropout of one encoder call: keep masks are keyed by (seed, counter, layer, site, row_offset + sequence, token, column)."""
+    __slots__ = ("seed", "counter", "row_offset", "p_hidden", "p_attn")
+
+    def __init__(self, seed: int, counter: int, row_offset: int, p_hidden: float, p_attn: float):
+        self.seed, self.counter, self.row_offset = int(seed), int(counter), int(row_offset)
+        self.p_hidden, self.p_attn = float(p_hidden), float(p_attn)
+
+    def site(self, layer: int, site: int) -> Optional[K.Drop]:
+        p = self.p_attn if site == K.DROP_ATTN_PROBS else self.p_hidden
+        return K.Drop(self.seed, self.counter, layer, site, self.row_offset, p) if p > 0 else None
+
+
+def _site(drop: Optional[Dropout], layer: int, site: int) -> Optional[K.Drop]:
+    return drop.site(layer, site) if drop is not None else None
+
+
 def _planes_mode() -> bool:
     return _lib.get_precision() == "split_bf16"
 
@@ -135,11 +157,13 @@ def _weights(p: Sequence[torch.Tensor], n_layers: int, pl: bool):
 
 
 def _forward(p: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.Tensor], n_layers: int, n_heads: int,
-             eps: float, save: bool, cls_only: bool = False):
+             eps: float, save: bool, cls_only: bool = False, drop: Optional[Dropout] = None):
     """cls_only: the caller consumes only the projected CLS embedding (`get_projected_text_embeddings`,
     modelling_cxrbert.py:117-141 -> `hidden_states[-1][:, 0, :]`).  Everything in the LAST layer after the attention is
     row-wise, so it runs on the N CLS rows instead of N*L tokens (output projection, both LayerNorms, the FFN: 75 % of that
-    layer's GEMM work); the returned `last` is then [N, H] (the CLS rows)."""
+    layer's GEMM work); the returned `last` is then [N, H] (the CLS rows).
+    drop: train-mode dropout (None: eval semantics).  At the attention-output and FFN-output sites the GEMM then leaves the residual
+    to the LayerNorm kernel, LN(keep * s * dense + residual); the CLS rows draw the same masks as in the full path."""
     N, L = ids.shape
     word, pos, typ, eg, eb = p[0:5]
     H = word.shape[1]
@@ -148,23 +172,31 @@ def _forward(p: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.
         raise ValueError(f"sequence length {L} exceeds max_position_embeddings {pos.shape[0]}")
     pl = _planes_mode()
     wl, (wdh_w, wdo_w), bq = _weights(p, n_layers, pl)
-    x, xhat0, rstd0 = K.embed_ln_fwd(ids.reshape(-1), word, pos, typ[0], eg, eb, eps, L, out_planes=pl)
+    x, xhat0, rstd0 = K.embed_ln_fwd(ids.reshape(-1), word, pos, typ[0], eg, eb, eps, L, out_planes=pl, drop=_site(drop, 0, K.DROP_EMBED))
     saved: List[_Saved] = []
     for i in range(n_layers):
         (wq, bqi, wk, bk, wv, bv, wo, bo, g1, b1, wi, bi, wo2, bo2, g2, b2) = p[5 + 16 * i: 5 + 16 * (i + 1)]
         wqkv_w, wo_w, wi_w, wo2_w = wl[i]
         qkv = _lin(x, wqkv_w, bq[i], pl)                                   # fp32: only the attention kernel reads it
-        ctx, probs = K.attn_fwd(qkv, mask, N, L, n_heads, dH, save_probs=save, out_planes=pl)
+        ctx, probs = K.attn_fwd(qkv, mask, N, L, n_heads, dH, save_probs=save, out_planes=pl, drop=_site(drop, i, K.DROP_ATTN_PROBS))
         rows_cls = cls_only and i == n_layers - 1
-        if rows_cls:   # row 0 of every sequence: [N, H] views with row stride L*H
-            t1 = _lin(_cls_rows(ctx, N, L, H), wo_w, bo, pl, residual=_cls_rows(x, N, L, H))
+        rps = 1 if rows_cls else L                                         # rows per sequence of the row-wise part
+        d_ao, d_fo = _site(drop, i, K.DROP_ATTN_OUT), _site(drop, i, K.DROP_FFN_OUT)
+        ctx_r, x_r = (_cls_rows(ctx, N, L, H), _cls_rows(x, N, L, H)) if rows_cls else (ctx, x)   # CLS rows: row stride L*H
+        if d_ao is None:
+            t1 = _lin(ctx_r, wo_w, bo, pl, residual=x_r)
+            a, xhat1, rstd1 = K.residual_ln_fwd(t1, None, g1, b1, eps, save=save, out_planes=pl)
         else:
-            t1 = _lin(ctx, wo_w, bo, pl, residual=x)
-        a, xhat1, rstd1 = K.residual_ln_fwd(t1, None, g1, b1, eps, save=save, out_planes=pl)
+            t1 = _lin(ctx_r, wo_w, bo, pl)
+            a, xhat1, rstd1 = K.residual_ln_fwd(t1, x_r, g1, b1, eps, save=save, out_planes=pl, drop=d_ao, rows_per_seq=rps)
         u_pre = torch.empty(t1.shape[0], wi.shape[0], dtype=torch.float32, device=t1.device) if save else None
         u = _lin(a, wi_w, bi, pl, act=K.ACT_GELU, preact_out=u_pre, out_planes=True)
-        t2 = _lin(u, wo2_w, bo2, pl, residual=a)
-        xn, xhat2, rstd2 = K.residual_ln_fwd(t2, None, g2, b2, eps, save=save, out_planes=pl)
+        if d_fo is None:
+            t2 = _lin(u, wo2_w, bo2, pl, residual=a)
+            xn, xhat2, rstd2 = K.residual_ln_fwd(t2, None, g2, b2, eps, save=save, out_planes=pl)
+        else:
+            t2 = _lin(u, wo2_w, bo2, pl)
+            xn, xhat2, rstd2 = K.residual_ln_fwd(t2, a, g2, b2, eps, save=save, out_planes=pl, drop=d_fo, rows_per_seq=rps)
         if save:
             s = _Saved()
             s.x, s.qkv, s.probs, s.ctx, s.xhat1, s.rstd1, s.a, s.u_pre, s.u, s.xhat2, s.rstd2 = \
@@ -177,7 +209,7 @@ def _forward(p: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.
     h1 = _lin(cls, wdh_w, bdh, pl, act=K.ACT_GELU, preact_out=h1_pre)     # fp32: LayerNorm input
     h2, xhat_h, rstd_h = K.residual_ln_fwd(h1, None, gh, bh, 1e-12, out_planes=pl)
     proj = _lin(h2, wdo_w, bdo, pl)
-    return proj, x, (xhat0, rstd0, saved, h1_pre, h2, xhat_h, rstd_h, wl, (wdh_w, wdo_w), pl)
+    return proj, x, (xhat0, rstd0, saved, h1_pre, h2, xhat_h, rstd_h, wl, (wdh_w, wdo_w), pl, drop)
 
 
 def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_heads: int, state, last, dproj, dlast,
@@ -185,7 +217,7 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
     """Writes every parameter gradient through `sink` (same order as `p`).  `last` is the final hidden state [T,H]
     ([N,H], the CLS rows, when cls_only: the last layer's row-wise part then runs on those rows only)."""
     N, L = ids.shape
-    xhat0, rstd0, saved, h1_pre, h2, xhat_h, rstd_h, wl, (wdh_w, wdo_w), pl = state
+    xhat0, rstd0, saved, h1_pre, h2, xhat_h, rstd_h, wl, (wdh_w, wdo_w), pl, drop = state
     word, pos, typ, eg, eb = p[0:5]
     H = word.shape[1]
     T = N * L
@@ -240,6 +272,19 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
             bg, bacc = sink.dst(jbias)
             return K.residual_ln_bwd(dy, xhat, rstd, gamma, dg, db, accumulate=a1, out_planes=pl, dxsum=bg, dxsum_accumulate=bacc)
 
+        def ln_bwd_res(dy, xhat, rstd, gamma, jg, jbias, d):
+            """(gradient of the residual sum, gradient of the dense output): one tensor without dropout at this site; with it, the
+            second is keep * s * the first, and the dense bias gradient is its column sum"""
+            if d is None:
+                g = ln_bwd(dy, xhat, rstd, gamma, jg, jbias)
+                return g, g
+            (dg, a1), (db, a2) = sink.dst(jg), sink.dst(jg + 1)
+            if a1 != a2:
+                (dg, a1), (db, a2) = sink.dst(jg, True), sink.dst(jg + 1, True)
+            bg, bacc = sink.dst(jbias)
+            return K.residual_ln_bwd_drop(dy, xhat, rstd, gamma, dg, db, d, rps, accumulate=a1, out_planes=pl, dxsum=bg,
+                                          dxsum_accumulate=bacc)
+
         def wb(dy, x_in, jw, bias: bool = True):   # weight (+ bias) gradient of a dense layer
             g, acc = sink.dst(jw)
             _wgrad(dy, x_in, g, acc, pl)
@@ -247,7 +292,9 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
                 g, acc = sink.dst(jw + 1)
                 K.colsum(dy, g, accumulate=acc)
 
-        dt2 = ln_bwd(dx, s.xhat2, s.rstd2, g2, o + 14, o + 13)
+        rows_cls = cls_only and i == n_layers - 1
+        rps = 1 if rows_cls else L
+        dsum2, dt2 = ln_bwd_res(dx, s.xhat2, s.rstd2, g2, o + 14, o + 13, _site(drop, i, K.DROP_FFN_OUT))
         wb(dt2, s.u, o + 12, bias=False)
         if pl:   # the FFN-up bias gradient = column sums of du, reduced in the epilogue that writes du
             bg, bacc = sink.dst(o + 11)
@@ -256,9 +303,8 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
         else:
             du = _dgrad(dt2, wo2_w, pl, aux=s.u_pre, auxmode=K.AUX_GELU_GRAD, out_planes=True)
             wb(du, s.a, o + 10)
-        da = _dgrad(du, wi_w, pl, residual=dt2)
-        dt1 = ln_bwd(da, s.xhat1, s.rstd1, g1, o + 8, o + 7)
-        rows_cls = cls_only and i == n_layers - 1
+        da = _dgrad(du, wi_w, pl, residual=dsum2)
+        dsum1, dt1 = ln_bwd_res(da, s.xhat1, s.rstd1, g1, o + 8, o + 7, _site(drop, i, K.DROP_ATTN_OUT))
         if rows_cls:   # dt1 holds the CLS rows only: its context rows are row 0 of every sequence, all other rows get no gradient
             wb(dt1, _cls_rows(s.ctx, N, L, H), o + 6, bias=False)
             dctx = torch.zeros(T, H, dtype=torch.float32, device=dev)
@@ -266,7 +312,7 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
         else:
             wb(dt1, s.ctx, o + 6, bias=False)
             dctx = _dgrad(dt1, wo_w, pl)
-        dqkv = K.attn_bwd(s.qkv, s.probs, dctx, N, L, n_heads, H // n_heads, out_planes=pl)
+        dqkv = K.attn_bwd(s.qkv, s.probs, dctx, N, L, n_heads, H // n_heads, out_planes=pl, drop=_site(drop, i, K.DROP_ATTN_PROBS))
         # fused q/k/v gradients: one [3H, H] GEMM into the three (adjacent) .grad slices when they are adjacent too
         gq = [getattr(sink.params[o + j], "grad", None) for j in (0, 2, 4)]
         gb = [getattr(sink.params[o + j], "grad", None) for j in (1, 3, 5)]
@@ -285,17 +331,21 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
         if rows_cls:   # the residual branch x -> t1 exists for the CLS rows only
             dx = _dgrad(dqkv, wqkv_w, pl)
             if pl:
-                K.planes_add_rows(dt1, dx.view(N, L * H)[:, :H])
+                K.planes_add_rows(dsum1, dx.view(N, L * H)[:, :H])
             else:
-                dx.view(N, L * H)[:, :H].add_(dt1)
+                dx.view(N, L * H)[:, :H].add_(dsum1)
         else:
-            dx = _dgrad(dqkv, wqkv_w, pl, residual=dt1)
+            dx = _dgrad(dqkv, wqkv_w, pl, residual=dsum1)
         saved[i] = None  # free this layer's activations early
 
     (deg, a1), (deb, a2) = sink.dst(3), sink.dst(4)
     if a1 != a2:
         (deg, a1), (deb, a2) = sink.dst(3, True), sink.dst(4, True)
-    demb = K.residual_ln_bwd(dx, xhat0, rstd0, eg, deg, deb, accumulate=a1)
+    d_emb = _site(drop, 0, K.DROP_EMBED)
+    if d_emb is None:
+        demb = K.residual_ln_bwd(dx, xhat0, rstd0, eg, deg, deb, accumulate=a1)
+    else:   # dy of the embedding LayerNorm = keep * s * dx
+        demb, _ = K.residual_ln_bwd_drop(dx, xhat0, rstd0, eg, deg, deb, d_emb, L, accumulate=a1, mask_dy=True)
     if need[0]:
         dword, _ = sink.dst(0, zero=True)
         K.embed_bwd(ids.reshape(-1), demb, dword)
@@ -312,12 +362,12 @@ class CXRBertEncodeFn(torch.autograd.Function):
     CLS rows when cls_only; an empty tensor when the caller does not want it)."""
 
     @staticmethod
-    def forward(ctx, ids, mask, n_layers, n_heads, eps, cls_only, want_last, on_grads_ready, *params):
+    def forward(ctx, ids, mask, n_layers, n_heads, eps, cls_only, want_last, on_grads_ready, drop, *params):
         ctx.set_materialize_grads(False)
         ctx.on_grads_ready = on_grads_ready
         save = any(t.requires_grad for t in params)
         p = [t.detach() for t in params]
-        proj, last, state = _forward(p, ids, mask, n_layers, n_heads, eps, save, cls_only)
+        proj, last, state = _forward(p, ids, mask, n_layers, n_heads, eps, save, cls_only, drop)   # state keeps (seed, counter)
         if save:
             ctx.state = state
             ctx.cfg = (n_layers, n_heads, cls_only)
@@ -345,19 +395,22 @@ class CXRBertEncodeFn(torch.autograd.Function):
         hook = ctx.on_grads_ready
         if hook is not None and all(r is None for r in res):
             hook("text")   # every gradient of this encoder already sits in its `.grad` view: the data-parallel step starts reducing them now
-        return (None, None, None, None, None, None, None, None) + res
+        return (None, None, None, None, None, None, None, None, None) + res
 
 
 def encode(params: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.Tensor], n_layers: int,
            n_heads: int, eps: float = 1e-12, cls_only: bool = False, want_last: bool = True,
-           on_grads_ready=None) -> Tuple[torch.Tensor, torch.Tensor]:
+           on_grads_ready=None, dropout: Optional[Dropout] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """`on_grads_ready(tag)`: optional callable bound to THIS call (it travels on the autograd node, not in a module global); the
     backward calls it with "text" on the stream it runs on once every parameter gradient of the call has been written in place
-    (`gradsink`).  contrastive.JointContrastiveTrainer starts the encoder's gradient all-reduce from it."""
+    (`gradsink`).  contrastive.JointContrastiveTrainer starts the encoder's gradient all-reduce from it.
+    `dropout`: train-mode dropout of this call (None, or both probabilities 0: eval semantics, the kernel sequence of eval mode)."""
     if ids.dtype != torch.int64:
         ids = ids.to(torch.int64)
     if mask is not None and mask.dtype != torch.int64:
         mask = mask.to(torch.int64)
     ids = ids.contiguous()
     mask = mask.contiguous() if mask is not None else None
-    return CXRBertEncodeFn.apply(ids, mask, n_layers, n_heads, eps, bool(cls_only), bool(want_last), on_grads_ready, *params)
+    if dropout is not None and dropout.p_hidden <= 0 and dropout.p_attn <= 0:
+        dropout = None
+    return CXRBertEncodeFn.apply(ids, mask, n_layers, n_heads, eps, bool(cls_only), bool(want_last), on_grads_ready, dropout, *params)
