@@ -845,21 +845,35 @@ static bool ln_vec8_ok(int H, const void* a, const void* b, const void* c, const
   return (H % 8) == 0 && aligned16(a) && aligned16(b) && aligned16(c) && aligned16(d) && aligned16(e) && aligned16(f);
 }
 
+// ---- host launchers: one per kernel family, shared by an eval entry point and its `_drop` twin.  DROP selects the dropout
+// instantiations; the eval entries pass an empty key.  The entries check their arguments (and build the key) before they call.
+
+// LayerNorm forward over `rows` rows (EMBED: of the embedding sum).  !v8: the scalar kernel (eval entries only; the dropout
+// entries refuse such a call).
+template <bool EMBED, bool DROP>
+static int launch_ln_fwd(const float* x, const float* res, const long* ids, const float* word, const float* pos, const float* type,
+                         const float* gamma, const float* beta, float eps, long rows, int H, int L, void* y, long yplane, float* xhat,
+                         float* rstd, bool v8, const LnFwdDrop& dr, hipStream_t stream) {
+  const dim3 grid((unsigned)((rows + 3) / 4));
+  if (v8 || DROP)
+    hipLaunchKernelGGL((ln_fwd_vec8_kernel<EMBED, DROP>), grid, dim3(256), 0, stream, x, res, ids, word, pos, type, gamma, beta, eps, rows, H,
+                       L, yplane ? nullptr : static_cast<float*>(y), yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd,
+                       dr);
+  else
+    hipLaunchKernelGGL((ln_fwd_kernel<EMBED>), grid, dim3(256), 0, stream, x, res, ids, word, pos, type, gamma, beta, eps, rows, H, L,
+                       static_cast<float*>(y), xhat, rstd);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
 extern "C" int cxrk_embed_ln_fwd(const long* ids, const float* word, const float* pos, const float* type,
                                  const float* gamma, const float* beta, float eps, long T, int L, int H, void* y, long yplane,
                                  float* xhat, float* rstd, hipStream_t stream) {
   CXRK_CHECK_ARG(ids && word && pos && type && gamma && beta && y && T > 0 && L > 0 && H > 0 && H <= 64 * LN_MAXV && yplane >= 0);
   const bool v8 = ln_vec8_ok(H, word, pos, type, gamma, beta, y) && aligned16(xhat) && (yplane % 8) == 0;
   if (yplane > 0 && !v8) return CXRK_ERR_ARG;
-  if (v8)
-    hipLaunchKernelGGL((ln_fwd_vec8_kernel<true>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, stream, nullptr, nullptr, ids, word, pos,
-                       type, gamma, beta, eps, T, H, L, yplane ? nullptr : static_cast<float*>(y),
-                       yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, LnFwdDrop{});
-  else
-    hipLaunchKernelGGL((ln_fwd_kernel<true>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, stream, nullptr, nullptr, ids, word,
-                       pos, type, gamma, beta, eps, T, H, L, static_cast<float*>(y), xhat, rstd);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return launch_ln_fwd<true, false>(nullptr, nullptr, ids, word, pos, type, gamma, beta, eps, T, H, L, y, yplane, xhat, rstd, v8,
+                                    LnFwdDrop{}, stream);
 }
 
 extern "C" int cxrk_residual_ln_fwd(const float* x, const float* res, const float* gamma, const float* beta, float eps,
@@ -867,15 +881,8 @@ extern "C" int cxrk_residual_ln_fwd(const float* x, const float* res, const floa
   CXRK_CHECK_ARG(x && gamma && beta && y && rows > 0 && H > 0 && H <= 64 * LN_MAXV && yplane >= 0);
   const bool v8 = ln_vec8_ok(H, x, res, gamma, beta, y, xhat) && (yplane % 8) == 0;
   if (yplane > 0 && !v8) return CXRK_ERR_ARG;
-  if (v8)
-    hipLaunchKernelGGL((ln_fwd_vec8_kernel<false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, res, nullptr, nullptr,
-                       nullptr, nullptr, gamma, beta, eps, rows, H, 1, yplane ? nullptr : static_cast<float*>(y),
-                       yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, LnFwdDrop{});
-  else
-    hipLaunchKernelGGL((ln_fwd_kernel<false>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x, res, nullptr, nullptr,
-                       nullptr, nullptr, gamma, beta, eps, rows, H, 1, static_cast<float*>(y), xhat, rstd);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return launch_ln_fwd<false, false>(x, res, nullptr, nullptr, nullptr, nullptr, gamma, beta, eps, rows, H, 1, y, yplane, xhat, rstd, v8,
+                                     LnFwdDrop{}, stream);
 }
 
 static int ln_bwd_blocks(long rows) {
@@ -886,23 +893,26 @@ static int ln_bwd_blocks(long rows) {
 }
 extern "C" size_t cxrk_residual_ln_bwd_ws_bytes(long rows, int H) { return (size_t)ln_bwd_blocks(rows) * 3 * H * sizeof(float); }
 
-extern "C" int cxrk_residual_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, long rows,
-                                    int H, const float* dx_add, void* dxv, long dxplane, float* dgamma, float* dbeta, int accumulate,
-                                    float* dxsum, int dxsum_accumulate, float* ws, size_t ws_bytes, hipStream_t stream) {
-  CXRK_CHECK_ARG(dy && xhat && rstd && gamma && dxv && dgamma && dbeta && rows > 0 && H > 0 && H <= 64 * LN_MAXV && dxplane >= 0);
+static bool ln_bwd_vec_ok(int H, const float* dy, const float* xhat, const float* gamma, const void* dxv, const float* dx_add, long dxplane) {
+  return (H % 4 == 0) && aligned16(dy) && aligned16(xhat) && aligned16(gamma) && aligned16(dxv) && (!dx_add || aligned16(dx_add)) &&
+         (dxplane % 4) == 0;
+}
+
+// LayerNorm backward: per-block partial sums into `ws` (the caller has checked its size), then the final reduction.  !vec: the scalar
+// kernel (LNB_PLAIN only; the dropout entry refuses such a call).
+template <int DM>
+static int launch_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, long rows, int H, const float* dx_add,
+                         void* dxv, long dxplane, float* dgamma, float* dbeta, int accumulate, float* dxsum, int dxsum_accumulate, float* ws,
+                         bool vec, const LnBwdDrop& dr, hipStream_t stream) {
   float* dx = dxplane ? nullptr : static_cast<float*>(dxv);
   unsigned short* dxp = dxplane ? static_cast<unsigned short*>(dxv) : nullptr;
   int nb = ln_bwd_blocks(rows);
-  if (ws == nullptr || ws_bytes < (size_t)nb * 3 * H * sizeof(float)) return CXRK_ERR_WS;
   const int np = dxsum ? 3 : 2;
   const int rows_per = (int)((rows + nb - 1) / nb);
   nb = (int)((rows + rows_per - 1) / rows_per);
-  const bool vec = (H % 4 == 0) && aligned16(dy) && aligned16(xhat) && aligned16(gamma) && aligned16(dxv) && (!dx_add || aligned16(dx_add)) &&
-                   (dxplane % 4) == 0;
-  if ((dxp || dxsum) && !vec) return CXRK_ERR_ARG;
-  if (vec)
-    hipLaunchKernelGGL(ln_bwd_vec_kernel<>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp, dxplane, dx_add, ws, np,
-                       LnBwdDrop{});
+  if (vec || DM != LNB_PLAIN)
+    hipLaunchKernelGGL(ln_bwd_vec_kernel<DM>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp, dxplane, dx_add,
+                       ws, np, dr);
   else
     hipLaunchKernelGGL(ln_bwd_kernel, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dx_add, ws);
   CXRK_LAUNCH_CHECK();
@@ -912,37 +922,56 @@ extern "C" int cxrk_residual_ln_bwd(const float* dy, const float* xhat, const fl
   return CXRK_OK;
 }
 
-extern "C" int cxrk_attn_fwd(const float* qkv, const long* mask, int B, int L, int nH, int dH, void* ctxv, long ctxplane, float* probs,
-                             hipStream_t stream) {
-  CXRK_CHECK_ARG(qkv && ctxv && B > 0 && nH > 0 && aligned16(qkv) && aligned16(ctxv) && ctxplane >= 0 && (ctxplane % 4) == 0);
+extern "C" int cxrk_residual_ln_bwd(const float* dy, const float* xhat, const float* rstd, const float* gamma, long rows,
+                                    int H, const float* dx_add, void* dxv, long dxplane, float* dgamma, float* dbeta, int accumulate,
+                                    float* dxsum, int dxsum_accumulate, float* ws, size_t ws_bytes, hipStream_t stream) {
+  CXRK_CHECK_ARG(dy && xhat && rstd && gamma && dxv && dgamma && dbeta && rows > 0 && H > 0 && H <= 64 * LN_MAXV && dxplane >= 0);
+  if (ws == nullptr || ws_bytes < cxrk_residual_ln_bwd_ws_bytes(rows, H)) return CXRK_ERR_WS;
+  const bool vec = ln_bwd_vec_ok(H, dy, xhat, gamma, dxv, dx_add, dxplane);
+  if ((dxplane || dxsum) && !vec) return CXRK_ERR_ARG;
+  return launch_ln_bwd<LNB_PLAIN>(dy, xhat, rstd, gamma, rows, H, dx_add, dxv, dxplane, dgamma, dbeta, accumulate, dxsum, dxsum_accumulate, ws,
+                                  vec, LnBwdDrop{}, stream);
+}
+
+// Attention forward.  L <= AL: one workgroup per (sequence, head); longer: the tiled form, one per (sequence, head, 32 queries).
+template <bool DROP>
+static int launch_attn_fwd(const float* qkv, const long* mask, int B, int L, int nH, int dH, void* ctxv, long ctxplane, float* probs,
+                           const DropKey& dk, hipStream_t stream) {
   float* ctx = ctxplane ? nullptr : static_cast<float*>(ctxv);
   unsigned short* ctxp = ctxplane ? static_cast<unsigned short*>(ctxv) : nullptr;
   if (dH > AD || dH < 4 || (dH % 4) != 0 || L > ALONG || L < 1) return CXRK_ERR_UNSUPPORTED;
   const int ALD = dH + 4;
-  if (L > AL) {   // tiled form: one workgroup per (sequence, head, 32 queries)
+  const float scale = 1.0f / sqrtf((float)dH);
+  if (L > AL) {
     const size_t shl = (size_t)((TQ + TK) * ALD + TQ * (L + 1)) * sizeof(float);
     static bool attr_long = false;
     if (!attr_long) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize,
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)(((TQ + TK) * (AD + 4) + TQ * (ALONG + 1)) * sizeof(float)));
       attr_long = true;
     }
-    hipLaunchKernelGGL(attn_fwd_long_kernel<>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shl, stream, qkv, mask, L, nH, dH,
-                       1.0f / sqrtf((float)dH), ctx, ctxp, ctxplane, probs, DropKey{});
+    hipLaunchKernelGGL(attn_fwd_long_kernel<DROP>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shl, stream, qkv, mask, L, nH, dH,
+                       scale, ctx, ctxp, ctxplane, probs, dk);
     CXRK_LAUNCH_CHECK();
     return CXRK_OK;
   }
   const size_t sh = (size_t)(3 * L * ALD + L * (L + 1)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)((3 * AL * (AD + 4) + AL * (AL + 1)) * sizeof(float)));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((3 * AL * (AD + 4) + AL * (AL + 1)) * sizeof(float)));
     attr_set = true;
   }
-  hipLaunchKernelGGL(attn_fwd_kernel<>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, mask, L, nH, dH,
-                     1.0f / sqrtf((float)dH), ctx, ctxp, ctxplane, probs, DropKey{});
+  hipLaunchKernelGGL(attn_fwd_kernel<DROP>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, mask, L, nH, dH, scale, ctx, ctxp, ctxplane,
+                     probs, dk);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
+}
+
+extern "C" int cxrk_attn_fwd(const float* qkv, const long* mask, int B, int L, int nH, int dH, void* ctxv, long ctxplane, float* probs,
+                             hipStream_t stream) {
+  CXRK_CHECK_ARG(qkv && ctxv && B > 0 && nH > 0 && aligned16(qkv) && aligned16(ctxv) && ctxplane >= 0 && (ctxplane % 4) == 0);
+  return launch_attn_fwd<false>(qkv, mask, B, L, nH, dH, ctxv, ctxplane, probs, DropKey{}, stream);
 }
 
 // workspace of cxrk_attn_bwd: the dS matrix of the tiled form (L > 64); nothing for short sequences
@@ -951,38 +980,46 @@ extern "C" size_t cxrk_attn_bwd_ws_bytes(int B, int L, int nH, int dH) {
   return L > AL ? (size_t)B * nH * L * L * sizeof(float) : 0;
 }
 
-extern "C" int cxrk_attn_bwd(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH,
-                             void* dqkvv, long dqkvplane, float* ws, size_t ws_bytes, hipStream_t stream) {
-  CXRK_CHECK_ARG(qkv && probs && dctx && dqkvv && B > 0 && nH > 0 && aligned16(qkv) && aligned16(dctx) && aligned16(dqkvv) && dqkvplane >= 0 &&
-                 (dqkvplane % 4) == 0);
+// Attention backward; the short form keeps the dropped probabilities in LDS as well (DROP: 3 probability planes, else 2).
+template <bool DROP>
+static int launch_attn_bwd(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH, void* dqkvv, long dqkvplane,
+                           float* ws, size_t ws_bytes, const DropKey& dk, hipStream_t stream) {
   float* dqkv = dqkvplane ? nullptr : static_cast<float*>(dqkvv);
   unsigned short* dqkvp = dqkvplane ? static_cast<unsigned short*>(dqkvv) : nullptr;
   if (dH > AD || dH < 4 || (dH % 4) != 0 || L > ALONG || L < 1) return CXRK_ERR_UNSUPPORTED;
   const int ALD = dH + 4;
+  const float scale = 1.0f / sqrtf((float)dH);
   if (L > AL) {
     if (ws == nullptr || ws_bytes < cxrk_attn_bwd_ws_bytes(B, L, nH, dH)) return CXRK_ERR_WS;
-    const float scale = 1.0f / sqrtf((float)dH);
     const size_t shq = (size_t)((TQ + 2 * TK) * ALD + TQ * (TK + 1)) * sizeof(float);
     const size_t shk = (size_t)(2 * TQ * ALD + 2 * TQ * (TK + 1)) * sizeof(float);
-    hipLaunchKernelGGL(attn_bwd_long_q_kernel<>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L, nH,
-                       dH, scale, ws, dqkv, dqkvp, dqkvplane, DropKey{});
+    hipLaunchKernelGGL(attn_bwd_long_q_kernel<DROP>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L,
+                       nH, dH, scale, ws, dqkv, dqkvp, dqkvplane, dk);
     CXRK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_bwd_long_kv_kernel<>, dim3((unsigned)(B * nH * ceil_div(L, TK))), dim3(256), shk, stream, qkv, probs, ws, dctx, L,
-                       nH, dH, dqkv, dqkvp, dqkvplane, DropKey{});
+    hipLaunchKernelGGL(attn_bwd_long_kv_kernel<DROP>, dim3((unsigned)(B * nH * ceil_div(L, TK))), dim3(256), shk, stream, qkv, probs, ws, dctx,
+                       L, nH, dH, dqkv, dqkvp, dqkvplane, dk);
     CXRK_LAUNCH_CHECK();
     return CXRK_OK;
   }
-  const size_t sh = (size_t)(4 * L * ALD + 2 * L * (L + 1)) * sizeof(float);
+  constexpr int NP = DROP ? 3 : 2;
+  const size_t sh = (size_t)(4 * L * ALD + NP * L * (L + 1)) * sizeof(float);
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                        (int)((4 * AL * (AD + 4) + 2 * AL * (AL + 1)) * sizeof(float)));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)((4 * AL * (AD + 4) + NP * AL * (AL + 1)) * sizeof(float)));
     attr_set = true;
   }
-  hipLaunchKernelGGL(attn_bwd_kernel<>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, probs, dctx, L, nH, dH,
-                     1.0f / sqrtf((float)dH), dqkv, dqkvp, dqkvplane, DropKey{});
+  hipLaunchKernelGGL(attn_bwd_kernel<DROP>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, probs, dctx, L, nH, dH, scale, dqkv, dqkvp,
+                     dqkvplane, dk);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
+}
+
+extern "C" int cxrk_attn_bwd(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH,
+                             void* dqkvv, long dqkvplane, float* ws, size_t ws_bytes, hipStream_t stream) {
+  CXRK_CHECK_ARG(qkv && probs && dctx && dqkvv && B > 0 && nH > 0 && aligned16(qkv) && aligned16(dctx) && aligned16(dqkvv) && dqkvplane >= 0 &&
+                 (dqkvplane % 4) == 0);
+  return launch_attn_bwd<false>(qkv, probs, dctx, B, L, nH, dH, dqkvv, dqkvplane, ws, ws_bytes, DropKey{}, stream);
 }
 
 // ---- dropout (train mode): the DROP instantiations of the kernels above and the mask generator --------------------------------
@@ -1041,11 +1078,7 @@ extern "C" int cxrk_embed_ln_fwd_drop(const long* ids, const float* word, const 
   if (!(ln_vec8_ok(H, word, pos, type, gamma, beta, y) && aligned16(xhat) && (yplane % 8) == 0)) return CXRK_ERR_UNSUPPORTED;
   LnFwdDrop dr{};
   if (make_drop(seed, counter, layer, site, row_offset, p, L, dr.dk) != CXRK_OK) return CXRK_ERR_ARG;
-  hipLaunchKernelGGL((ln_fwd_vec8_kernel<true, true>), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, stream, nullptr, nullptr, ids, word, pos,
-                     type, gamma, beta, eps, T, H, L, yplane ? nullptr : static_cast<float*>(y),
-                     yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, dr);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return launch_ln_fwd<true, true>(nullptr, nullptr, ids, word, pos, type, gamma, beta, eps, T, H, L, y, yplane, xhat, rstd, true, dr, stream);
 }
 
 extern "C" int cxrk_residual_ln_fwd_drop(const float* x, const void* res, long resplane, long res_ld, const float* gamma, const float* beta,
@@ -1060,11 +1093,8 @@ extern "C" int cxrk_residual_ln_fwd_drop(const float* x, const void* res, long r
   dr.resp = resplane ? static_cast<const unsigned short*>(res) : nullptr;
   dr.resplane = resplane;
   dr.res_ld = res_ld ? res_ld : H;
-  hipLaunchKernelGGL((ln_fwd_vec8_kernel<false, true>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, stream, x,
-                     resplane ? nullptr : static_cast<const float*>(res), nullptr, nullptr, nullptr, nullptr, gamma, beta, eps, rows, H, 1,
-                     yplane ? nullptr : static_cast<float*>(y), yplane ? static_cast<unsigned short*>(y) : nullptr, yplane, xhat, rstd, dr);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return launch_ln_fwd<false, true>(x, resplane ? nullptr : static_cast<const float*>(res), nullptr, nullptr, nullptr, nullptr, gamma, beta,
+                                    eps, rows, H, 1, y, yplane, xhat, rstd, true, dr, stream);
 }
 
 extern "C" int cxrk_residual_ln_bwd_drop(const float* dy, const float* xhat, const float* rstd, const float* gamma, long rows, int H,
@@ -1074,31 +1104,17 @@ extern "C" int cxrk_residual_ln_bwd_drop(const float* dy, const float* xhat, con
                                          hipStream_t stream) {
   CXRK_CHECK_ARG(dy && xhat && rstd && gamma && dxv && dgamma && dbeta && rows > 0 && H > 0 && H <= 64 * LN_MAXV && dxplane >= 0 &&
                  (mode == LNB_DROP_RES || mode == LNB_DROP_DY) && ((mode == LNB_DROP_RES) == (dxmv != nullptr)));
-  int nb = ln_bwd_blocks(rows);
-  if (ws == nullptr || ws_bytes < (size_t)nb * 3 * H * sizeof(float)) return CXRK_ERR_WS;
-  const bool vec = (H % 4 == 0) && aligned16(dy) && aligned16(xhat) && aligned16(gamma) && aligned16(dxv) && (!dxmv || aligned16(dxmv)) &&
-                   (!dx_add || aligned16(dx_add)) && (dxplane % 4) == 0;
-  if (!vec) return CXRK_ERR_UNSUPPORTED;
+  if (ws == nullptr || ws_bytes < cxrk_residual_ln_bwd_ws_bytes(rows, H)) return CXRK_ERR_WS;
+  if (!(ln_bwd_vec_ok(H, dy, xhat, gamma, dxv, dx_add, dxplane) && (!dxmv || aligned16(dxmv)))) return CXRK_ERR_UNSUPPORTED;
   LnBwdDrop dr{};
   if (make_drop(seed, counter, layer, site, row_offset, p, rows_per_seq, dr.dk) != CXRK_OK) return CXRK_ERR_ARG;
   dr.dxm = dxplane ? nullptr : static_cast<float*>(dxmv);
   dr.dxmp = dxplane ? static_cast<unsigned short*>(dxmv) : nullptr;
-  float* dx = dxplane ? nullptr : static_cast<float*>(dxv);
-  unsigned short* dxp = dxplane ? static_cast<unsigned short*>(dxv) : nullptr;
-  const int np = dxsum ? 3 : 2;
-  const int rows_per = (int)((rows + nb - 1) / nb);
-  nb = (int)((rows + rows_per - 1) / rows_per);
-  if (mode == LNB_DROP_RES)
-    hipLaunchKernelGGL(ln_bwd_vec_kernel<LNB_DROP_RES>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp,
-                       dxplane, dx_add, ws, np, dr);
-  else
-    hipLaunchKernelGGL(ln_bwd_vec_kernel<LNB_DROP_DY>, dim3(nb), dim3(256), 0, stream, dy, xhat, rstd, gamma, rows, H, rows_per, dx, dxp,
-                       dxplane, dx_add, ws, np, dr);
-  CXRK_LAUNCH_CHECK();
-  hipLaunchKernelGGL(ln_bwd_final_kernel, dim3(ceil_div(H, 64), np), dim3(1024), 0, stream, ws, nb, np, H, dgamma, dbeta, accumulate, dxsum,
-                     dxsum_accumulate);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return mode == LNB_DROP_RES
+             ? launch_ln_bwd<LNB_DROP_RES>(dy, xhat, rstd, gamma, rows, H, dx_add, dxv, dxplane, dgamma, dbeta, accumulate, dxsum,
+                                           dxsum_accumulate, ws, true, dr, stream)
+             : launch_ln_bwd<LNB_DROP_DY>(dy, xhat, rstd, gamma, rows, H, dx_add, dxv, dxplane, dgamma, dbeta, accumulate, dxsum,
+                                          dxsum_accumulate, ws, true, dr, stream);
 }
 
 extern "C" int cxrk_attn_fwd_drop(const float* qkv, const long* mask, int B, int L, int nH, int dH, void* ctxv, long ctxplane, float* probs,
@@ -1106,35 +1122,7 @@ extern "C" int cxrk_attn_fwd_drop(const float* qkv, const long* mask, int B, int
                                   hipStream_t stream) {
   CXRK_CHECK_ARG(qkv && ctxv && B > 0 && nH > 0 && nH < 65536 && aligned16(qkv) && aligned16(ctxv) && ctxplane >= 0 && (ctxplane % 4) == 0);
   CXRK_MAKE_DROP(1, dk);
-  float* ctx = ctxplane ? nullptr : static_cast<float*>(ctxv);
-  unsigned short* ctxp = ctxplane ? static_cast<unsigned short*>(ctxv) : nullptr;
-  if (dH > AD || dH < 4 || (dH % 4) != 0 || L > ALONG || L < 1) return CXRK_ERR_UNSUPPORTED;
-  const int ALD = dH + 4;
-  const float scale = 1.0f / sqrtf((float)dH);
-  if (L > AL) {
-    const size_t shl = (size_t)((TQ + TK) * ALD + TQ * (L + 1)) * sizeof(float);
-    static bool attr_long = false;
-    if (!attr_long) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_long_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)(((TQ + TK) * (AD + 4) + TQ * (ALONG + 1)) * sizeof(float)));
-      attr_long = true;
-    }
-    hipLaunchKernelGGL(attn_fwd_long_kernel<true>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shl, stream, qkv, mask, L, nH, dH,
-                       scale, ctx, ctxp, ctxplane, probs, dk);
-    CXRK_LAUNCH_CHECK();
-    return CXRK_OK;
-  }
-  const size_t sh = (size_t)(3 * L * ALD + L * (L + 1)) * sizeof(float);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((3 * AL * (AD + 4) + AL * (AL + 1)) * sizeof(float)));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(attn_fwd_kernel<true>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, mask, L, nH, dH, scale, ctx, ctxp, ctxplane,
-                     probs, dk);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return launch_attn_fwd<true>(qkv, mask, B, L, nH, dH, ctxv, ctxplane, probs, dk, stream);
 }
 
 extern "C" int cxrk_attn_bwd_drop(const float* qkv, const float* probs, const float* dctx, int B, int L, int nH, int dH, void* dqkvv,
@@ -1143,32 +1131,5 @@ extern "C" int cxrk_attn_bwd_drop(const float* qkv, const float* probs, const fl
   CXRK_CHECK_ARG(qkv && probs && dctx && dqkvv && B > 0 && nH > 0 && nH < 65536 && aligned16(qkv) && aligned16(dctx) && aligned16(dqkvv) &&
                  dqkvplane >= 0 && (dqkvplane % 4) == 0);
   CXRK_MAKE_DROP(1, dk);
-  float* dqkv = dqkvplane ? nullptr : static_cast<float*>(dqkvv);
-  unsigned short* dqkvp = dqkvplane ? static_cast<unsigned short*>(dqkvv) : nullptr;
-  if (dH > AD || dH < 4 || (dH % 4) != 0 || L > ALONG || L < 1) return CXRK_ERR_UNSUPPORTED;
-  const int ALD = dH + 4;
-  const float scale = 1.0f / sqrtf((float)dH);
-  if (L > AL) {
-    if (ws == nullptr || ws_bytes < cxrk_attn_bwd_ws_bytes(B, L, nH, dH)) return CXRK_ERR_WS;
-    const size_t shq = (size_t)((TQ + 2 * TK) * ALD + TQ * (TK + 1)) * sizeof(float);
-    const size_t shk = (size_t)(2 * TQ * ALD + 2 * TQ * (TK + 1)) * sizeof(float);
-    hipLaunchKernelGGL(attn_bwd_long_q_kernel<true>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L,
-                       nH, dH, scale, ws, dqkv, dqkvp, dqkvplane, dk);
-    CXRK_LAUNCH_CHECK();
-    hipLaunchKernelGGL(attn_bwd_long_kv_kernel<true>, dim3((unsigned)(B * nH * ceil_div(L, TK))), dim3(256), shk, stream, qkv, probs, ws, dctx,
-                       L, nH, dH, dqkv, dqkvp, dqkvplane, dk);
-    CXRK_LAUNCH_CHECK();
-    return CXRK_OK;
-  }
-  const size_t sh = (size_t)(4 * L * ALD + 3 * L * (L + 1)) * sizeof(float);   // + the dropped probabilities
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)((4 * AL * (AD + 4) + 3 * AL * (AL + 1)) * sizeof(float)));
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3((unsigned)(B * nH)), dim3(256), sh, stream, qkv, probs, dctx, L, nH, dH, scale, dqkv, dqkvp,
-                     dqkvplane, dk);
-  CXRK_LAUNCH_CHECK();
-  return CXRK_OK;
+  return launch_attn_bwd<true>(qkv, probs, dctx, B, L, nH, dH, dqkvv, dqkvplane, ws, ws_bytes, dk, stream);
 }

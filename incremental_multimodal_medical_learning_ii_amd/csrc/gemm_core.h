@@ -18,10 +18,6 @@
 #include "cxrk_common.h"
 #include <cstdlib>
 
-#ifndef CXRK_ABL
-#define CXRK_ABL 0  // ablation switch for scripts/tune_gemm.hip only; the library is always built with 0
-#endif
-
 namespace cxrk {
 
 constexpr int BK = 32;
@@ -179,7 +175,6 @@ __device__ __forceinline__ void gemm_epilogue64_f32(f32x16 (&acc)[2][2], const E
         if (!live[u]) continue;
         const long row = rows[u];
         float v[4] = {ep.alpha * v4.x + bv.x, ep.alpha * v4.y + bv.y, ep.alpha * v4.z + bv.z, ep.alpha * v4.w + bv.w};
-        if ((CXRK_ABL == 5 || CXRK_ABL == 6) && v[0] != 12345.678f) continue;  // ablation: drop the epilogue traffic
         if (ep.vec) {
           if (ep.R) { v[0] += pr[u].x; v[1] += pr[u].y; v[2] += pr[u].z; v[3] += pr[u].w; }
           if (ep.C2) *reinterpret_cast<float4*>(ep.C2 + row * ep.ldc2 + col) = make_float4(v[0], v[1], v[2], v[3]);
@@ -251,43 +246,29 @@ __device__ __forceinline__ void gemm_epilogue(f32x16 (&acc)[2][2], const EpiPara
 // XCD-aware tile mapping (speed only, never correctness).  Workgroups are dealt round-robin over the 8 XCDs, so blocks b
 // and b+8 share an L2.  Bijective remap (cdna_hip_programming.md T1): XCD x owns a contiguous chunk of the tile list, so
 // every XCD gets work even when there are fewer than 8 M panels.  Inside the list the tiles are ordered in column chunks
-// of CXRK_GN N-tiles, M-panel-major inside a chunk: the blocks an XCD runs at the same time then share a few B panels
-// (they stay in its 4 MiB L2) while the A panels stream through, each re-read CXRK_GN times back to back.
-#ifndef CXRK_GN
-#define CXRK_GN 8   // 0 = one chunk = plain M-panel-major order; 8: +3..7 % on the BERT GEMMs (N = 2304 / 3072) over 0
-#endif
+// of TILE_GN N-tiles, M-panel-major inside a chunk: the blocks an XCD runs at the same time then share a few B panels
+// (they stay in its 4 MiB L2) while the A panels stream through, each re-read TILE_GN times back to back.
+constexpr int TILE_GN = 8;   // +3..7 % on the BERT GEMMs (N = 2304 / 3072) over one chunk = plain M-panel-major order
 // Split-K launches (nz > 1 slabs): the grid is ONE list of nz * nMt * nNt workgroups, slab-major, and the XCD remap runs over the
 // whole list, so an XCD owns ~1/8 of it = whole slabs (or a contiguous run of tiles of one slab).  All tiles of a slab read the
 // same K-range of both operands: kept on one XCD, that range is fetched into ONE L2 instead of all eight.  (Round 2 remapped
 // inside each slab only — every XCD then held tiles of every slab, and the weight-gradient launches moved 2-3x their algorithmic
 // bytes through the fabric: profiles/r02_z_pmc_hbm_traffic.txt.)
-#ifndef CXRK_SLAB_MAJOR
-#define CXRK_SLAB_MAJOR 1   // 0 = round 2's order (tile list remapped per slab, slabs interleaved over the XCDs), for A/B measurements
-#endif
 __device__ __forceinline__ void tile_coords(int nMt, int nNt, int nz, int& mt, int& nt, int& z) {
   const int per = nMt * nNt;
-  int wgid;
-  if (CXRK_SLAB_MAJOR || nz == 1) {
-    const int nwg = per * nz;
-    const int b = blockIdx.x;
-    const int xcd = b & 7, idx = b >> 3;
-    const int qq = nwg >> 3, rr = nwg & 7;
-    const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-    z = w / per;
-    wgid = w - z * per;
-  } else {
-    z = blockIdx.x / per;
-    const int b = blockIdx.x - z * per;
-    const int xcd = b & 7, idx = b >> 3;
-    const int qq = per >> 3, rr = per & 7;
-    wgid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
-  }
-  if (CXRK_GN <= 0 || nNt <= CXRK_GN) { mt = wgid / nNt; nt = wgid - mt * nNt; return; }
-  const int per_c = nMt * CXRK_GN;          // tiles of a full chunk
+  const int nwg = per * nz;
+  const int b = blockIdx.x;
+  const int xcd = b & 7, idx = b >> 3;
+  const int qq = nwg >> 3, rr = nwg & 7;
+  const int w = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + idx;
+  z = w / per;
+  const int wgid = w - z * per;
+  if (nNt <= TILE_GN) { mt = wgid / nNt; nt = wgid - mt * nNt; return; }
+  const int per_c = nMt * TILE_GN;          // tiles of a full chunk
   const int c = wgid / per_c, rem = wgid - c * per_c;
-  const int width = min(CXRK_GN, nNt - c * CXRK_GN);
+  const int width = min(TILE_GN, nNt - c * TILE_GN);
   mt = rem / width;                         // the last (narrower) chunk still holds nMt * width tiles
-  nt = c * CXRK_GN + (rem - mt * width);
+  nt = c * TILE_GN + (rem - mt * width);
 }
 
 // Waves per SIMD the register-staged kernels are compiled for.  Rounds 1-3 ran the 128x128 tile at 3 (168 registers: a third block
@@ -307,19 +288,14 @@ __global__ __launch_bounds__(NTHREADS, CXRK_OCC) void gemm_f32_kernel(typename L
   constexpr int BM = WM * 64, BN = WN * 64;
   constexpr int LDA = LA::LD, LDB = LB::LD;
   constexpr int ASZ = BK * LDA, BSZ = BK * LDB;
-  // ONE LDS buffer per operand (33-41 KB) and two barriers per K-tile.  Measured on 32768x3072x768 (scripts/tune_gemm.hip) with
+  // ONE LDS buffer per operand (33-41 KB) and two barriers per K-tile.  Measured on 32768x3072x768 with
   // the round-1 epilogue: 113 TFLOP/s at 3 blocks per CU, against 99 for two buffers at 2 blocks/CU (66 KB) and 107 for one buffer
   // at 4 waves/SIMD (register pressure).  The kernels are now compiled for 2 waves per SIMD (CXRK_OCC above: no spills); the LDS
-  // footprint still lets a third block in where the register file allows it.  NBUF = 2 is kept as a tuning option.
+  // footprint still lets a third block in where the register file allows it.
   // All LDS lives in ONE array (cdna_hip_programming.md: a second __shared__ object can de-pipeline the loop).
-#ifdef CXRK_NBUF
-  constexpr int NBUF = CXRK_NBUF;  // tuning override (scripts/tune_gemm.hip)
-#else
-  constexpr int NBUF = 1;
-#endif
-  __shared__ __attribute__((aligned(16))) float smem[NBUF * (ASZ + BSZ)];
+  __shared__ __attribute__((aligned(16))) float smem[ASZ + BSZ];
   float* const As0 = smem;
-  float* const Bs0 = smem + NBUF * ASZ;
+  float* const Bs0 = smem + ASZ;
 
   int mt, nt, z;
   tile_coords(nMt, nNt, nZ, mt, nt, z);
@@ -353,20 +329,16 @@ __global__ __launch_bounds__(NTHREADS, CXRK_OCC) void gemm_f32_kernel(typename L
   __syncthreads();
   if (kbeg + BK < kend) { la.load(kbeg + BK, ra); lb.load(kbeg + BK, rb); }
 
-  // Main loop.  MFMAs are asynchronous to the issuing wave (64 cycles each), so the staging of the NEXT tiles is
-  // interleaved between them instead of being appended: with two LDS buffers the registers holding tile t+1 are
-  // written to the other buffer a quarter of the way through tile t, and the global loads of tile t+2 are issued at
-  // the half-way point; only one barrier per K-tile remains.  (Single-buffer tiles stage after the MFMA block.)
-  int cur = 0;
+  // Main loop: the registers holding tile t+1 are written to the single buffer after the MFMA block of tile t, then the
+  // global loads of tile t+2 are issued.
   for (int k0 = kbeg; k0 < kend; k0 += BK) {
-    const float* Ap = As0 + cur * ASZ + wm * 64 + r + h * LDA;
-    const float* Bp = Bs0 + cur * BSZ + wn * 64 + r + h * LDB;
+    const float* Ap = As0 + wm * 64 + r + h * LDA;
+    const float* Bp = Bs0 + wn * 64 + r + h * LDB;
     const bool has1 = k0 + BK < kend, has2 = k0 + 2 * BK < kend;
     float a0 = Ap[0], a1 = Ap[32], b0 = Bp[0], b1 = Bp[32];
 #pragma unroll
     for (int kk = 0; kk < BK / 2; ++kk) {
       float a0n = 0.f, a1n = 0.f, b0n = 0.f, b1n = 0.f;
-      if (CXRK_ABL == 4 || CXRK_ABL == 6) { a0n = a0 + 1.f; a1n = a1; b0n = b0; b1n = b1; } else
       if (kk + 1 < BK / 2) {
         a0n = Ap[(2 * kk + 2) * LDA]; a1n = Ap[(2 * kk + 2) * LDA + 32];
         b0n = Bp[(2 * kk + 2) * LDB]; b1n = Bp[(2 * kk + 2) * LDB + 32];
@@ -376,18 +348,11 @@ __global__ __launch_bounds__(NTHREADS, CXRK_OCC) void gemm_f32_kernel(typename L
       acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
       acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
       a0 = a0n; a1 = a1n; b0 = b0n; b1 = b1n;
-      if (NBUF == 2 && CXRK_ABL != 4 && CXRK_ABL != 6) {
-        if (kk == 3 && has1 && CXRK_ABL != 2) { la.store(As0 + (cur ^ 1) * ASZ, ra); lb.store(Bs0 + (cur ^ 1) * BSZ, rb); }
-        if (kk == 7 && has2 && CXRK_ABL != 1) { la.load(k0 + 2 * BK, ra); lb.load(k0 + 2 * BK, rb); }
-      }
     }
-    if (NBUF == 1 && CXRK_ABL != 4 && CXRK_ABL != 6) {
-      if (CXRK_ABL != 3) __syncthreads();  // single buffer: everyone must be done reading before it is overwritten
-      if (has1 && CXRK_ABL != 2) { la.store(As0, ra); lb.store(Bs0, rb); }
-    }
-    if (CXRK_ABL != 3 && CXRK_ABL != 4 && CXRK_ABL != 6) __syncthreads();
-    if (NBUF == 1 && has2 && CXRK_ABL != 1 && CXRK_ABL != 4 && CXRK_ABL != 6) { la.load(k0 + 2 * BK, ra); lb.load(k0 + 2 * BK, rb); }
-    if (NBUF == 2) cur ^= 1;
+    __syncthreads();  // single buffer: everyone must be done reading before it is overwritten
+    if (has1) { la.store(As0, ra); lb.store(Bs0, rb); }
+    __syncthreads();
+    if (has2) { la.load(k0 + 2 * BK, ra); lb.load(k0 + 2 * BK, rb); }
   }
 
   static_assert(BK * (LDA + LDB) >= 4 * 32 * 64, "operand LDS too small to stage the epilogue");
@@ -470,12 +435,11 @@ __global__ __launch_bounds__(NTHREADS, (WM == 2 && WN == 2) ? 3 : 2) void gemm_x
         }
     }
     __syncthreads();  // everyone is done reading before the single buffer is overwritten
-    if (k0 + BK < kend && !(CXRK_ABL & 2)) { la.store2(Ahi, Alo, ra); lb.store2(Bhi, Blo, rb); }
+    if (k0 + BK < kend) { la.store2(Ahi, Alo, ra); lb.store2(Bhi, Blo, rb); }
     __syncthreads();
-    if (k0 + 2 * BK < kend) { la.load(k0 + 2 * BK, ra, !(CXRK_ABL & 1)); lb.load(k0 + 2 * BK, rb, !(CXRK_ABL & 1)); }
+    if (k0 + 2 * BK < kend) { la.load(k0 + 2 * BK, ra); lb.load(k0 + 2 * BK, rb); }
   }
   __syncthreads();
-  if ((CXRK_ABL & 4) && acc[0][0][0] != 12345.678f) return;
   gemm_epilogue<WM, WN>(acc, ep, reinterpret_cast<float*>(smem16), M, N, m0, n0, mt, z, wave, lane);
 }
 
@@ -489,7 +453,7 @@ static inline int stream_output(int M, int N, int splitk) {
   return (double)M * N * 4.0 * (splitk > 1 ? splitk : 1) >= thr;
 }
 
-int wgrad_splitk_policy(int M, int N, int K, bool planes);   // gemm.hip
+int wgrad_splitk_policy(int M, int N, int K, bool planes);   // gemm_misc.hip
 
 // 256x256-tile policy.  CXRK_WIDE (environment, read once; cxrk_set_wide_mode() at run time): 0 = never, 1 (default) = where it
 // pays, 2 = every launch on planes operands (test coverage on small / ragged shapes).  "Pays": split-bf16 launch, both tile dimensions filled, a K

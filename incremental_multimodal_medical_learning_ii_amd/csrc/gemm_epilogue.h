@@ -109,9 +109,6 @@ __device__ __forceinline__ uint4 f4_bits(float a, float b, float c, float d) {
 // 7 - lane inside the half row, which joins the two quads) instead of three ds_bpermute round trips through the LDS crossbar: the
 // forward epilogue of conv_halo.h went from 6 960 to 5 570 cycles (scripts/tune_halo.hip).  (First tried while the register-staged
 // kernels still spilled at 3 waves per SIMD; that build aborted an fp32-mode test — see CXRK_OCC in gemm_core.h.)
-#ifndef CXRK_OR8_DPP
-#define CXRK_OR8_DPP 1   // 0: the ds_bpermute form (A/B measurements)
-#endif
 __device__ __forceinline__ unsigned or8_lanes(unsigned x) {
   x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, true);    // quad_perm [1,0,3,2]
   x |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, true);    // quad_perm [2,3,0,1]
@@ -119,36 +116,22 @@ __device__ __forceinline__ unsigned or8_lanes(unsigned x) {
   return x;
 }
 
-// Experiment switch (round 3, measured and NOT kept): 1 = pipeline the side inputs of the LDS-DMA kernels' epilogues (see epi_rows).
-// With it the data-gradient launches of the step took 20.34 instead of 20.45 ms and the step 154.0 instead of 155.3 ms — inside
-// the box-to-box spread — while the 256x256 instantiations went from 249 registers to 256 + 60 spilled (scratch): the epilogue is
-// bound by its stores (256 KB per tile), not by the latency of its side inputs.
-#ifndef CXRK_EPI_PIPE
-#define CXRK_EPI_PIPE 0
-#endif
-constexpr bool epi_has_side(unsigned f) { return (f & (EF_RES_F32 | EF_RES_PL | EF_AUX_SIGN | EF_AUX_GELU | EF_AUX_MASK)) != 0u; }
-constexpr bool epi_two_fp32_sides(unsigned f) { return (f & EF_RES_F32) != 0u && (f & (EF_AUX_SIGN | EF_AUX_GELU)) != 0u; }
-
 #define EH(bit, rt) (GEN ? (rt) : ((F & (bit)) != 0u))
 
 // NSUB 64-row slabs of a wave's outputs (acc[s] = rows 64 s .. 64 s + 63 of the block at row0; NSUB = 2: the 128 x 64 outputs of a
-// wave of the 256 x 256 tile) go through 2 NSUB halves of 32 rows.
-// PIPE (compiled-in feature sets on the LDS-DMA kernels): the side inputs (residual, mask bits, GELU' source) of an 8-row pass of
-// half h + 1 are requested as soon as the same pass of half h has been stored, so only the first half's loads are waited for at
-// full memory latency; the un-pipelined form (generic feature set, register-staged kernels) loads the side inputs of a half and
-// consumes them at once — a round trip per half with nothing of this wave in between.
+// wave of the 256 x 256 tile) go through 2 NSUB halves of 32 rows; the side inputs (residual, mask bits, GELU' source) of a half
+// are loaded and consumed at once.
 // PAIR (conv_halo.h): two waves share one 64 x 64 output block, wave `psel` holding its columns 32 psel .. +31 (acc[0][i][0], all
 // 64 rows).  Both stage their column block of BOTH 32-row halves into the pair's shared staging area `st` ([2 halves][32][64]
 // fp32), meet at the workgroup barrier (every wave of the block must call this), and wave psel then finishes half psel alone:
 // the 64 x 64 block's epilogue runs on two waves.  Column sums: one partial row per (block, half) — `part` is that row.
 // S2RES: the compact stride-2 residual (EF_RES_S2) is compiled in.  Only the LDS-DMA kernels (epi_pw_dispatch / epi_pair_dispatch)
 // carry it: the register-staged fp32 / x3 kernels never see such a launch, and their code must not grow (see the note at epi64).
-template <unsigned F, int NSUB, bool PIPE, bool PAIR = false, bool S2RES = true>
+template <unsigned F, int NSUB, bool PAIR = false, bool S2RES = true>
 __device__ __forceinline__ void epi_rows(f32x16 (*acc)[2][2], const EpiParams& ep, float* st, int M, int N, int row0, int col0,
                                          int part, int z, int lane, int psel = 0) {
   constexpr bool GEN = (F & EF_GENERIC) != 0u;
-  static_assert(!(GEN && PIPE), "the generic feature set is not pipelined");
-  static_assert(!PAIR || (NSUB == 1 && !PIPE), "the pair form: one 64-row block, un-pipelined");
+  static_assert(!PAIR || NSUB == 1, "the pair form: one 64-row block");
   const bool outpl = EH(EF_OUTPL, ep.Cp != nullptr), has_bias = EH(EF_BIAS, ep.bias != nullptr);
   const bool res_f32 = EH(EF_RES_F32, ep.R != nullptr), res_pl = EH(EF_RES_PL, ep.Rp != nullptr);
   const bool relu = EH(EF_RELU, ep.act == 1), gelu = EH(EF_GELU, ep.act == 2);
@@ -204,7 +187,6 @@ __device__ __forceinline__ void epi_rows(f32x16 (*acc)[2][2], const EpiParams& e
   // fp32-mode data gradient with identity branch — are four 16-byte loads per pass: two passes ahead is what the 168-register
   // budget of the three-blocks-per-CU kernels holds without spilling)
   constexpr int PF = GEN ? 1 : (((F & EF_RES_F32) != 0u && (F & (EF_AUX_SIGN | EF_AUX_GELU)) != 0u) ? 2 : 4);
-  static_assert(!PIPE || PF == 4, "the pipelined form keeps the side inputs of a whole half");
   struct Side { unsigned dead[PF]; unsigned rowo[PF]; uint4 r0v[PF], r1v[PF], a0v[PF], a1v[PF]; unsigned mk[PF]; };
 
   // request the side inputs of pass ua (8 rows) of half hh (rows 32 hh .. 32 hh + 31 of the block) into slot u
@@ -302,11 +284,7 @@ __device__ __forceinline__ void epi_rows(f32x16 (*acc)[2][2], const EpiParams& e
       }
       if (maskout) {   // the 8 lanes of a row hold its 8 mask bytes: OR them together, lane c8 == 0 stores the 8 bytes
         unsigned w0 = c8 < 4 ? obits << (8 * c8) : 0u, w1 = c8 >= 4 ? obits << (8 * (c8 - 4)) : 0u;
-        if (CXRK_OR8_DPP) { w0 = or8_lanes(w0); w1 = or8_lanes(w1); }
-        else {
-#pragma unroll
-          for (int o = 1; o < 8; o <<= 1) { w0 |= (unsigned)__shfl_xor((int)w0, o, 64); w1 |= (unsigned)__shfl_xor((int)w1, o, 64); }
-        }
+        w0 = or8_lanes(w0); w1 = or8_lanes(w1);
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         const u32x2 w = {w0, w1};
         const unsigned mo = (rowo * (unsigned)ep.ldmaskout) | ((c8 == 0 && sd.dead[u] == 0u && col0 < N) ? 0u : VOFF_OOB);
@@ -359,23 +337,6 @@ __device__ __forceinline__ void epi_rows(f32x16 (*acc)[2][2], const EpiParams& e
       for (int up = 0; up < PF; ++up) finish_pass(sd, up, psel, ug + up);
     }
     if (colsum) flush_colsum(part);
-  } else if constexpr (PIPE) {
-    // slot u holds the side inputs of pass u of the current half; the moment pass u has been combined and stored, the slot is
-    // re-requested for pass u of the NEXT half: that load is in flight for a whole half's worth of staging, arithmetic and stores
-    // (one set of side-input registers, as in the un-pipelined form)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) load_side(sd, u, 0, u);
-#pragma unroll
-    for (int hh = 0; hh < NHALF; ++hh) {
-      stage(hh);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        finish_pass(sd, u, hh, u);
-        if (hh + 1 < NHALF) load_side(sd, u, hh + 1, u);
-      }
-      __builtin_amdgcn_wave_barrier();
-      if (colsum && (hh & 1)) flush_colsum(part + (hh >> 1));
-    }
   } else {
 #pragma unroll
     for (int hh = 0; hh < NHALF; ++hh) {
@@ -407,7 +368,7 @@ __device__ __forceinline__ void epi_rows(f32x16 (*acc)[2][2], const EpiParams& e
 template <unsigned F>
 __device__ __forceinline__ void epi64(f32x16 (&acc)[2][2], const EpiParams& ep, float* st, int M, int N, int row0, int col0,
                                       int part, int z, int lane) {
-  epi_rows<F, 1, false, false, CXRK_EXP_S2_EVERYWHERE != 0>(&acc, ep, st, M, N, row0, col0, part, z, lane);
+  epi_rows<F, 1, false, CXRK_EXP_S2_EVERYWHERE != 0>(&acc, ep, st, M, N, row0, col0, part, z, lane);
 }
 
 template <int KIND>
@@ -421,13 +382,13 @@ __device__ __forceinline__ void epi64_dispatch(int kind, f32x16 (&acc)[2][2], co
   }
 }
 
-// The LDS-DMA kernels (gemm_pw.h): NSUB slabs of 64 rows per wave, compiled-in feature sets pipelined (see epi_rows).
+// The LDS-DMA kernels (gemm_pw.h): NSUB slabs of 64 rows per wave.
 template <int KIND, int NSUB>
 __device__ __forceinline__ void epi_pw_dispatch(int kind, f32x16 (*acc)[2][2], const EpiParams& ep, float* st, int M, int N, int row0,
                                                 int col0, int part, int z, int lane) {
-  if constexpr (KIND >= EPI_NKINDS) epi_rows<EF_GENERIC, NSUB, false>(acc, ep, st, M, N, row0, col0, part, z, lane);
+  if constexpr (KIND >= EPI_NKINDS) epi_rows<EF_GENERIC, NSUB>(acc, ep, st, M, N, row0, col0, part, z, lane);
   else {
-    if (kind == KIND) epi_rows<EPI_KINDS[KIND], NSUB, (CXRK_EPI_PIPE != 0) && epi_has_side(EPI_KINDS[KIND]) && !epi_two_fp32_sides(EPI_KINDS[KIND])>(acc, ep, st, M, N, row0, col0, part, z, lane);
+    if (kind == KIND) epi_rows<EPI_KINDS[KIND], NSUB>(acc, ep, st, M, N, row0, col0, part, z, lane);
     else epi_pw_dispatch<KIND + 1, NSUB>(kind, acc, ep, st, M, N, row0, col0, part, z, lane);
   }
 }
@@ -436,9 +397,9 @@ __device__ __forceinline__ void epi_pw_dispatch(int kind, f32x16 (*acc)[2][2], c
 template <int KIND>
 __device__ __forceinline__ void epi_pair_dispatch(int kind, f32x16 (*acc)[2][2], const EpiParams& ep, float* st, int M, int N, int row0,
                                                   int col0, int part, int lane, int psel) {
-  if constexpr (KIND >= EPI_NKINDS) epi_rows<EF_GENERIC, 1, false, true>(acc, ep, st, M, N, row0, col0, part, 0, lane, psel);
+  if constexpr (KIND >= EPI_NKINDS) epi_rows<EF_GENERIC, 1, true>(acc, ep, st, M, N, row0, col0, part, 0, lane, psel);
   else {
-    if (kind == KIND) epi_rows<EPI_KINDS[KIND], 1, false, true>(acc, ep, st, M, N, row0, col0, part, 0, lane, psel);
+    if (kind == KIND) epi_rows<EPI_KINDS[KIND], 1, true>(acc, ep, st, M, N, row0, col0, part, 0, lane, psel);
     else epi_pair_dispatch<KIND + 1>(kind, acc, ep, st, M, N, row0, col0, part, lane, psel);
   }
 }

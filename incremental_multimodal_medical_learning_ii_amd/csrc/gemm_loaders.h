@@ -180,11 +180,11 @@ struct DenseKC : KCGeom<TILE, FMT, NT> {
     for (int j = 0; j < NVR; ++j)
       voff[j] = idx0 + r0 + j * RP < p.rows ? (unsigned)(((r0 + j * RP) * ld + kq * FMT::EPL) * FMT::ESZ) : VOFF_OOB;
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     const unsigned t = (k0 + BK <= K || k0 + kq * FMT::EPL < K) ? 0u : VOFF_OOB;   // K tail (the last K-tile only)
 #pragma unroll
     for (int pl = 0; pl < FMT::NPL; ++pl) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + k0, live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + k0);
 #pragma unroll
       for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, voff[j] | t);
     }
@@ -210,11 +210,11 @@ struct DenseMC : MCGeom<TILE, FMT, NT> {
 #pragma unroll
     for (int j = 0; j < NVR; ++j) voff[j] = ok ? (unsigned)(((kr0 + j * RPP) * ld + cq * FMT::EPL) * FMT::ESZ) : VOFF_OOB;
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     const bool full = k0 + BK <= K;
 #pragma unroll
     for (int pl = 0; pl < FMT::NPL; ++pl) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + (long)k0 * ld_, live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + (long)k0 * ld_);
 #pragma unroll
       for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, (full || k0 + kr0 + j * RPP < K) ? voff[j] : VOFF_OOB);
     }
@@ -271,13 +271,13 @@ struct ConvIm2colKC : KCGeom<TILE, FMT, NT> {
       }
     }
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     if constexpr (TAPWISE) {
       if (k0 != knext) { const int tap = k0 / C; tc = k0 - tap * C; tr = tap / S; ts = tap - tr * S; }
       const int t = tr * S + ts;
 #pragma unroll
       for (int pl = 0; pl < FMT::NPL; ++pl) {
-        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)(tr * W + ts) * C + tc), live);
+        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)(tr * W + ts) * C + tc));
 #pragma unroll
         for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, masked_off(off[j], inv[j], t));
       }
@@ -285,7 +285,7 @@ struct ConvIm2colKC : KCGeom<TILE, FMT, NT> {
       if (tc >= C) { tc = 0; if (++ts == S) { ts = 0; ++tr; } }
       knext = k0 + BK;
     } else {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp, live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp);
       const int k = k0 + kq * 4;
       const int tap = k / C, c = k - tap * C;
       const int r = tap / S, s = tap - r * S;
@@ -330,12 +330,12 @@ struct ConvDgradKC : KCGeom<TILE, FMT, NT> {
       } else { off[j] = 0; inv[j] = 0xffffffffu; }
     }
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     if (k0 != knext) { const int tap = k0 / Ko; tk = k0 - tap * Ko; tr = tap / S; ts = tap - tr * S; }
     const int t = tr * S + ts;
 #pragma unroll
     for (int pl = 0; pl < FMT::NPL; ++pl) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)((R - 1 - tr) * Wo + (S - 1 - ts)) * Ko + tk), live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)((R - 1 - tr) * Wo + (S - 1 - ts)) * Ko + tk));
 #pragma unroll
       for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, masked_off(off[j], inv[j], t));
     }
@@ -364,11 +364,11 @@ struct ConvFilterMC : MCGeom<TILE, FMT, NT> {
 #pragma unroll
     for (int j = 0; j < NVR; ++j) voff[j] = ok ? (unsigned)(((kr0 + j * RPP) * (int)RSC + cq * FMT::EPL) * FMT::ESZ) : VOFF_OOB;
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     if (k0 != knext) { tap = k0 / Ko; tk = k0 - tap * Ko; }
 #pragma unroll
     for (int pl = 0; pl < FMT::NPL; ++pl) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)tk * RSC + (long)tap * C), live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)tk * RSC + (long)tap * C));
 #pragma unroll
       for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, voff[j]);
     }
@@ -416,13 +416,13 @@ struct ConvDgradS2KC : KCGeom<TILE, FMT, NT> {
       } else { off[j] = 0; inv[j] = 0xffffffffu; }
     }
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     if (k0 != knext) { ti = k0 / Ko; tk = k0 - ti * Ko; }
     const int ir = ti / t.ns, is = ti - ir * t.ns;
     const int dr = ir == 0 ? t.dr[0] : t.dr[1], ds = is == 0 ? t.ds[0] : t.ds[1];
 #pragma unroll
     for (int pl = 0; pl < FMT::NPL; ++pl) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)(dr * Wo + ds) * Ko + tk), live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)(dr * Wo + ds) * Ko + tk));
 #pragma unroll
       for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, masked_off(off[j], inv[j], ti));
     }
@@ -450,13 +450,13 @@ struct ConvFilterS2MC : MCGeom<TILE, FMT, NT> {
 #pragma unroll
     for (int j = 0; j < NVR; ++j) voff[j] = ok ? (unsigned)(((kr0 + j * RPP) * (int)RSC + cq * FMT::EPL) * FMT::ESZ) : VOFF_OOB;
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     if (k0 != knext) { ti = k0 / Ko; tk = k0 - ti * Ko; }
     const int ir = ti / t.ns, is = ti - ir * t.ns;
     const int tap = (ir == 0 ? t.r[0] : t.r[1]) * S + (is == 0 ? t.s[0] : t.s[1]);
 #pragma unroll
     for (int pl = 0; pl < FMT::NPL; ++pl) {
-      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)tk * RSC + (long)tap * C), live);
+      const __amdgpu_buffer_rsrc_t rs = tile_rsrc(bp + pl * plane + ((long)tk * RSC + (long)tap * C));
 #pragma unroll
       for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, voff[j]);
     }
@@ -515,7 +515,7 @@ struct ConvIm2colMC : MCGeom<TILE, FMT, NT> {
       pwo[j] = k % Wo; const int t = k / Wo; pho[j] = t % Ho; pn[j] = t / Ho;
     }
   }
-  __device__ __forceinline__ void load(int k0, V (&v)[NV], bool live = true) {
+  __device__ __forceinline__ void load(int k0, V (&v)[NV]) {
     if (k0 != knext) seek(k0);
     const bool tail = k0 + BK > K;
     if (linear) {
@@ -532,7 +532,7 @@ struct ConvIm2colMC : MCGeom<TILE, FMT, NT> {
       }
 #pragma unroll
       for (int pl = 0; pl < FMT::NPL; ++pl) {
-        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(x + pl * plane + ((long)k0 * C - bias), live);
+        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(x + pl * plane + ((long)k0 * C - bias));
 #pragma unroll
         for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, o[j]);
       }
@@ -547,7 +547,7 @@ struct ConvIm2colMC : MCGeom<TILE, FMT, NT> {
       }
 #pragma unroll
       for (int pl = 0; pl < FMT::NPL; ++pl) {
-        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(x + pl * plane + (long)un * H * W * C, live);
+        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(x + pl * plane + (long)un * H * W * C);
 #pragma unroll
         for (int j = 0; j < NVR; ++j) v[pl * NVR + j] = bloadv<FMT>(rs, o[j]);
       }

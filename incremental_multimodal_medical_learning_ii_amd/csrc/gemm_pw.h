@@ -615,7 +615,7 @@ __global__ __launch_bounds__(CFG::NT, CFG::WAVES_PER_SIMD) void gemm_pw_kernel(t
   __syncthreads();   // every wave is done with the operand buffers: they become the epilogue's transpose staging
   float* stg = reinterpret_cast<float*>(smem) + wave * (32 * 64);
   // planes operands are always 16-byte aligned (launch_gemm_pw refuses anything else): the fast epilogue only.  The wave's WTM / 2
-  // slabs of 64 rows go through ONE pipelined pass (side inputs of the next 32-row half requested while this one is stored).
+  // slabs of 64 rows go through ONE epi_rows call.
   epi_pw_dispatch<0, WTM / 2>(ep.kind, acc, ep, stg, M, N, m0 + arow, n0 + bcol, mt * (CFG::TM / 64) + wm * (WTM / 2), z, lane);
   PW_STAMP(3);
   if (ep.stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); PW_STAMP(4); }

@@ -618,7 +618,7 @@ def conv_bwd_data(dy, w_scaled, residual, relu_src, dx, N, H, W, C, Ko, R, S, st
 
 
 def conv_bwd_params(x, dy, w, scale, rstd, rmean, sumdy, dw, dgamma, dbeta, accumulate, N, H, W, C, Cpad, Ko, R, S, stride, pad):
-    """dW = scale * wgrad(x, dy); dbeta = sumdy; dgamma = rstd * (<w, wgrad> - mean * sumdy)  (csrc/conv.hip)."""
+    """dW = scale * wgrad(x, dy); dbeta = sumdy; dgamma = rstd * (<w, wgrad> - mean * sumdy)  (csrc/conv_wgrad.hip)."""
     lib = _lib.load()
     wsb = lib.cxrk_conv_wgrad_ws_bytes(N, H, W, Cpad, Ko, R, S, stride, pad)
     ws = workspace(wsb, x.device)
