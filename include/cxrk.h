@@ -8,7 +8,10 @@
  * Conventions (all entry points):
  *   - plain device pointers + sizes; fp32 data; int64 ids/masks; no hidden allocation, no hidden synchronisation;
  *   - work is enqueued on `stream` (the caller's current HIP stream) and the call returns immediately;
- *   - scratch memory is passed in (`ws`, `ws_bytes`); the matching `*_ws_bytes` function sizes it;
+ *   - scratch memory is passed in (`ws`, `ws_bytes`); the matching `*_ws_bytes` function sizes it: an entry point touches
+ *     nothing outside [ws, ws + that many bytes) and reads nothing there that it has not written in the same call.  `ws` must
+ *     be 256-byte aligned (hipMalloc and every caching allocator give that): it is carved into regions at 256-byte offsets
+ *     and read as 16-byte vectors / 8-byte sort keys; an entry point that uses a workspace returns -1 for a misaligned one;
  *   - return 0 on success, <0 on error: -1 bad argument/alignment, -2 workspace too small, -3 launch failure,
  *     -4 unsupported shape.  The Python wrappers raise RuntimeError/ValueError for these, mirroring the
  *     reference's exception behaviour;

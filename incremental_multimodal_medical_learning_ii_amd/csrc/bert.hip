@@ -926,7 +926,7 @@ extern "C" int cxrk_residual_ln_bwd(const float* dy, const float* xhat, const fl
                                     int H, const float* dx_add, void* dxv, long dxplane, float* dgamma, float* dbeta, int accumulate,
                                     float* dxsum, int dxsum_accumulate, float* ws, size_t ws_bytes, hipStream_t stream) {
   CXRK_CHECK_ARG(dy && xhat && rstd && gamma && dxv && dgamma && dbeta && rows > 0 && H > 0 && H <= 64 * LN_MAXV && dxplane >= 0);
-  if (ws == nullptr || ws_bytes < cxrk_residual_ln_bwd_ws_bytes(rows, H)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, cxrk_residual_ln_bwd_ws_bytes(rows, H));
   const bool vec = ln_bwd_vec_ok(H, dy, xhat, gamma, dxv, dx_add, dxplane);
   if ((dxplane || dxsum) && !vec) return CXRK_ERR_ARG;
   return launch_ln_bwd<LNB_PLAIN>(dy, xhat, rstd, gamma, rows, H, dx_add, dxv, dxplane, dgamma, dbeta, accumulate, dxsum, dxsum_accumulate, ws,
@@ -990,7 +990,7 @@ static int launch_attn_bwd(const float* qkv, const float* probs, const float* dc
   const int ALD = dH + 4;
   const float scale = 1.0f / sqrtf((float)dH);
   if (L > AL) {
-    if (ws == nullptr || ws_bytes < cxrk_attn_bwd_ws_bytes(B, L, nH, dH)) return CXRK_ERR_WS;
+    CXRK_CHECK_WS(ws, ws_bytes, cxrk_attn_bwd_ws_bytes(B, L, nH, dH));
     const size_t shq = (size_t)((TQ + 2 * TK) * ALD + TQ * (TK + 1)) * sizeof(float);
     const size_t shk = (size_t)(2 * TQ * ALD + 2 * TQ * (TK + 1)) * sizeof(float);
     hipLaunchKernelGGL(attn_bwd_long_q_kernel<DROP>, dim3((unsigned)(B * nH * ceil_div(L, TQ))), dim3(256), shq, stream, qkv, probs, dctx, L,
@@ -1104,7 +1104,7 @@ extern "C" int cxrk_residual_ln_bwd_drop(const float* dy, const float* xhat, con
                                          hipStream_t stream) {
   CXRK_CHECK_ARG(dy && xhat && rstd && gamma && dxv && dgamma && dbeta && rows > 0 && H > 0 && H <= 64 * LN_MAXV && dxplane >= 0 &&
                  (mode == LNB_DROP_RES || mode == LNB_DROP_DY) && ((mode == LNB_DROP_RES) == (dxmv != nullptr)));
-  if (ws == nullptr || ws_bytes < cxrk_residual_ln_bwd_ws_bytes(rows, H)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, cxrk_residual_ln_bwd_ws_bytes(rows, H));
   if (!(ln_bwd_vec_ok(H, dy, xhat, gamma, dxv, dx_add, dxplane) && (!dxmv || aligned16(dxmv)))) return CXRK_ERR_UNSUPPORTED;
   LnBwdDrop dr{};
   if (make_drop(seed, counter, layer, site, row_offset, p, rows_per_seq, dr.dk) != CXRK_OK) return CXRK_ERR_ARG;

@@ -273,7 +273,7 @@ extern "C" int cxrk_coldot(const void* a, long aplane, const void* b, long bplan
   CXRK_CHECK_ARG(fmt_ok(a, aplane) && fmt_ok(b, bplane) && out && rows > 0 && C > 0 && (C % 8) == 0);
   int np = coldot_parts(rows, C);
   const int cql = col_lanes_log2(C);
-  if (ws == nullptr || ws_bytes < (size_t)np * C * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, (size_t)np * C * sizeof(float));
   const int rows_per = (int)((rows + np - 1) / np);
   np = (int)((rows + rows_per - 1) / rows_per);
   hipLaunchKernelGGL(coldot_partial_kernel, dim3(ceil_div(C, 8 << cql), np), dim3(256), 0, stream, a, aplane, b, bplane, bshift, rows, C, rows_per, cql,
@@ -306,7 +306,7 @@ extern "C" int cxrk_colstats(const void* x, long plane, long rows, int C, float*
   CXRK_CHECK_ARG(fmt_ok(x, plane) && mean && var && rows > 0 && C > 0 && (C % 8) == 0);
   int np = coldot_parts(rows, C);
   const int cql = col_lanes_log2(C);
-  if (ws == nullptr || ws_bytes < 2 * (size_t)np * C * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, 2 * (size_t)np * C * sizeof(float));
   const int rows_per = (int)((rows + np - 1) / np);
   np = (int)((rows + rows_per - 1) / rows_per);
   float* pm = ws; float* p2 = ws + (size_t)np * C;

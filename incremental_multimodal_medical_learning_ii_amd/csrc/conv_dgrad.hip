@@ -191,7 +191,7 @@ extern "C" int cxrk_conv_bn_act_bwd_data(const float* dy, const float* w_scaled,
   if (sums) {
     CXRK_CHECK_ARG(!(R == 1 && stride == 2));
     np = dgrad_colsum_parts(N, H, W, C, stride, Ko, R, S, pad, false);
-    if (ws == nullptr || ws_bytes < (size_t)(np + 64) * C * sizeof(float)) return CXRK_ERR_WS;
+    CXRK_CHECK_WS(ws, ws_bytes, (size_t)(np + 64) * C * sizeof(float));
     ep.colsum_part = ws;
   }
   const int rc = conv_bwd_data_impl<F32>(dy, 0, w_scaled, 0, ep, residual || relu_src, N, H, W, C, Ko, R, S, stride, pad, stream);
@@ -237,7 +237,7 @@ static int conv_bwd_data_pl_impl(const void* dy, long dyplane, const void* w_sca
   if (sums) {
     CXRK_CHECK_ARG(!(R == 1 && stride == 2));
     np = dgrad_colsum_parts(N, H, W, C, stride, Ko, R, S, pad, true);
-    if (ws == nullptr || ws_bytes < (size_t)(np + 64) * C * sizeof(float)) return CXRK_ERR_WS;
+    CXRK_CHECK_WS(ws, ws_bytes, (size_t)(np + 64) * C * sizeof(float));
     ep.colsum_part = ws;
   }
   const int rc = conv_bwd_data_impl<PL>(static_cast<const unsigned short*>(dy), dyplane, static_cast<const unsigned short*>(w_scaled), wplane,

@@ -111,7 +111,7 @@ static int conv_bwd_params_impl(const typename FMT::T* x, long xplane, const typ
   if ((long)H * W * Cpad * 4 * 3 >= (1L << 31)) return CXRK_ERR_UNSUPPORTED;  // a K-tile of 32 pixels spans <= 3 images
   int sk = wgrad_splitk(Ko, Nc, Kl, FMT::PLANES);
   const size_t slab_floats = (size_t)sk * Ko * Nc;
-  if (ws == nullptr || ws_bytes < (slab_floats + (size_t)Ko * wgrad_dot_parts(Nc)) * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, (slab_floats + (size_t)Ko * wgrad_dot_parts(Nc)) * sizeof(float));
   EpiParams ep{};
   ep.C = ws; ep.ldc = Nc; ep.alpha = 1.f; ep.slab_stride = (long)Ko * Nc;
   int rc;

@@ -10,6 +10,11 @@
 #define CXRK_ERR_UNSUPPORTED (-4)
 
 #define CXRK_CHECK_ARG(cond) do { if (!(cond)) return CXRK_ERR_ARG; } while (0)
+// A workspace must hold `need` bytes (else CXRK_ERR_WS) and be 256-byte aligned (else CXRK_ERR_ARG; include/cxrk.h, "scratch memory"):
+// the entry points carve it into regions at 256-byte offsets and read it as float4 / 8-byte keys.
+#define CXRK_CHECK_WS(ws, ws_bytes, need) do { \
+    if ((ws) == nullptr || (ws_bytes) < (need)) return CXRK_ERR_WS; \
+    if ((reinterpret_cast<uintptr_t>(ws) & 255) != 0) return CXRK_ERR_ARG; } while (0)
 #define CXRK_LAUNCH_CHECK() do { if (hipGetLastError() != hipSuccess) return CXRK_ERR_LAUNCH; } while (0)
 
 namespace cxrk {

@@ -98,7 +98,7 @@ extern "C" size_t cxrk_embed_bwd_ws_bytes(long T, int H) {
 extern "C" int cxrk_embed_bwd(const long* ids, const float* dx, long T, int H, float* dword, float* ws, size_t ws_bytes,
                               hipStream_t stream) {
   CXRK_CHECK_ARG(ids && dx && dword && T > 0 && H > 0 && T < (1L << 31));
-  if (ws == nullptr || ws_bytes < cxrk_embed_bwd_ws_bytes(T, H)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, cxrk_embed_bwd_ws_bytes(T, H));
   const long nchunks = (T + CH - 1) / CH;
   unsigned char* p = reinterpret_cast<unsigned char*>(ws);
   unsigned long long* keys = reinterpret_cast<unsigned long long*>(p); p += align256((size_t)T * 8);

@@ -20,7 +20,7 @@ extern "C" int cxrk_gemm_f32(int transA, int transB, int M, int N, int K, const 
   const bool plain = !bias && !R && !aux && !C2 && act == 0;
   if (splitk > 1) {
     CXRK_CHECK_ARG(plain && (N % 4 == 0));
-    if (ws == nullptr || ws_bytes < cxrk_gemm_splitk_ws_bytes(M, N, splitk)) return CXRK_ERR_WS;
+    CXRK_CHECK_WS(ws, ws_bytes, cxrk_gemm_splitk_ws_bytes(M, N, splitk));
     ep.C = ws; ep.ldc = N; ep.alpha = 1.f; ep.slab_stride = (long)M * N;
   } else {
     if (accumulate) { CXRK_CHECK_ARG(R == nullptr); ep.R = C; ep.ldr = ldc; }

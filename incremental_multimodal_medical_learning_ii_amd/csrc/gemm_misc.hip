@@ -212,7 +212,7 @@ extern "C" int cxrk_colsum_pl(const void* X, long ldx, long plane, long rows, in
   int nparts = (int)((rows + 511) / 512);
   if (nparts > 512) nparts = 512;
   if (nparts < 1) nparts = 1;
-  if (ws == nullptr || ws_bytes < (size_t)nparts * cols * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, (size_t)nparts * cols * sizeof(float));
   const int rows_per = (int)((rows + nparts - 1) / nparts);
   nparts = (int)((rows + rows_per - 1) / rows_per);
   hipLaunchKernelGGL(colsum_partial_pl_kernel, dim3(ceil_div(cols, 256), nparts), dim3(256), 0, stream,
@@ -230,7 +230,7 @@ extern "C" int cxrk_colvar(const void* X, long ldx, long plane, long rows, int c
   int nparts = (int)((rows + 511) / 512);
   if (nparts > 512) nparts = 512;
   if (nparts < 1) nparts = 1;
-  if (ws == nullptr || ws_bytes < (size_t)nparts * cols * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, (size_t)nparts * cols * sizeof(float));
   const int rows_per = (int)((rows + nparts - 1) / nparts);
   nparts = (int)((rows + rows_per - 1) / rows_per);
   hipLaunchKernelGGL(colvar_partial_kernel, dim3(ceil_div(cols, 256), nparts), dim3(256), 0, stream,
@@ -248,7 +248,7 @@ extern "C" int cxrk_colsum(const float* X, long ldx, long rows, int cols, float*
   int nparts = (int)((rows + 511) / 512);
   if (nparts > 512) nparts = 512;
   if (nparts < 1) nparts = 1;
-  if (ws == nullptr || ws_bytes < (size_t)nparts * cols * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, (size_t)nparts * cols * sizeof(float));
   const int rows_per = (int)((rows + nparts - 1) / nparts);
   nparts = (int)((rows + rows_per - 1) / rows_per);
   if (cols % 4 == 0 && ldx % 4 == 0 && aligned16(X) && aligned16(ws))

@@ -75,11 +75,11 @@ extern "C" int cxrk_gemm_pl(int transA, int transB, int M, int N, int K, const v
   const bool plain = !bias && !R && !Rp && !aux && !maskin && !maskout && !C2 && act == 0;
   if (colsum) {
     CXRK_CHECK_ARG(splitk == 1 && (N % 8) == 0);
-    if (ws == nullptr || ws_bytes < cxrk_gemm_pl_colsum_ws_bytes(M, N)) return CXRK_ERR_WS;
+    CXRK_CHECK_WS(ws, ws_bytes, cxrk_gemm_pl_colsum_ws_bytes(M, N));
   }
   if (splitk > 1) {
     CXRK_CHECK_ARG(plain && C && !Cp && (N % 4 == 0));
-    if (ws == nullptr || ws_bytes < cxrk_gemm_splitk_ws_bytes(M, N, splitk)) return CXRK_ERR_WS;
+    CXRK_CHECK_WS(ws, ws_bytes, cxrk_gemm_splitk_ws_bytes(M, N, splitk));
     ep.C = ws; ep.ldc = N; ep.alpha = 1.f; ep.slab_stride = (long)M * N;
   } else {
     if (accumulate) { CXRK_CHECK_ARG(R == nullptr && Rp == nullptr && C); ep.R = C; ep.ldr = ldc; }

@@ -352,7 +352,7 @@ static int cosine_bwd(const float* x, const float* y, const float* cosv, const f
   int pc_max = (int)((64 * 1024) / ((size_t)4 * D * sizeof(float)));
   if (pc_max < 1) return CXRK_ERR_UNSUPPORTED;
   int nb = cos_bwd_blocks(B);
-  if (ws == nullptr || ws_bytes < (size_t)nb * P * D * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, (size_t)nb * P * D * sizeof(float));
   const int rows_per = (int)((B + nb - 1) / nb);
   nb = (int)((B + rows_per - 1) / rows_per);
   for (int p0 = 0; p0 < P; p0 += pc_max) {
@@ -388,7 +388,7 @@ extern "C" int cxrk_bce_posneg_fwd_bwd(const float* cosv, const float* labels, l
                                        float* logits, float* dcos, float* loss, float* ws, size_t ws_bytes,
                                        hipStream_t stream) {
   CXRK_CHECK_ARG(cosv && labels && loss && B > 0 && C > 0 && ldlab >= C);
-  if (ws == nullptr || ws_bytes < 256 * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, 256 * sizeof(float));
   long nb = (B * C + 255) / 256; if (nb > 256) nb = 256;
   hipLaunchKernelGGL(bce_posneg_kernel, dim3((unsigned)nb), dim3(256), 0, stream, cosv, labels, B, C, ldlab, diff, logits, dcos, ws);
   CXRK_LAUNCH_CHECK();

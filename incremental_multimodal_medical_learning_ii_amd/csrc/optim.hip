@@ -115,7 +115,7 @@ extern "C" size_t cxrk_weight_reset_ws_bytes(void) { return 2 * 256 * sizeof(flo
 extern "C" int cxrk_weight_reset(float* pnew, const float* pold, long n, float threshold, unsigned long long* counters,
                                  float* ws, size_t ws_bytes, hipStream_t stream) {
   CXRK_CHECK_ARG(pnew && pold && counters && n > 0);
-  if (ws == nullptr || ws_bytes < 2 * 256 * sizeof(float)) return CXRK_ERR_WS;
+  CXRK_CHECK_WS(ws, ws_bytes, 2 * 256 * sizeof(float));
   long nb = (n + 255) / 256; if (nb > 256) nb = 256;
   hipLaunchKernelGGL(absdiff_minmax_kernel, dim3((unsigned)nb), dim3(256), 0, stream, pnew, pold, n, ws);
   CXRK_LAUNCH_CHECK();

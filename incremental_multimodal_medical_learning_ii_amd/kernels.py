@@ -34,6 +34,18 @@ def _chk(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t
 
 
+def _chk_out(t, shape, name: str, dtype=torch.float32):
+    """a caller-provided output (`out=`): fp32 tensor (contiguous columns; rows may be strided) or contiguous Planes of `shape`"""
+    if isinstance(t, Planes):
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"{name}: expected contiguous Planes of shape {tuple(shape)}, got {tuple(t.shape)}")
+        return t
+    _chk(t, name, dtype)
+    if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous tensor of shape {tuple(shape)}, got {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
 def _rowmajor2d(t: torch.Tensor, name: str) -> Tuple[torch.Tensor, int]:
     _chk(t, name)
     if t.dim() != 2:
@@ -461,14 +473,18 @@ def _vec(t: torch.Tensor, C: int, name: str) -> torch.Tensor:
     return t
 
 
-def colstats(x, unbiased: bool = False):
-    """(mean[C], var[C]) over the rows of x ([..., C] fp32 or Planes, C % 8 == 0) in one pass; var biased (1 / n) or unbiased (1 / (n - 1))."""
+def colstats(x, unbiased: bool = False, out=None):
+    """(mean[C], var[C]) over the rows of x ([..., C] fp32 or Planes, C % 8 == 0) in one pass; var biased (1 / n) or unbiased (1 / (n - 1)).
+    `out`: optional (mean, var) pair to write into."""
     lib = _lib.load()
     C = x.shape[-1]
     rows = x.numel() // C
     xp, xpl = _fmt(x, "colstats.x")
-    mean = torch.empty(C, dtype=torch.float32, device=x.device)
-    var = torch.empty(C, dtype=torch.float32, device=x.device)
+    if out is None:
+        mean = torch.empty(C, dtype=torch.float32, device=x.device)
+        var = torch.empty(C, dtype=torch.float32, device=x.device)
+    else:
+        mean, var = _vec(out[0], C, "colstats.mean"), _vec(out[1], C, "colstats.var")
     ws = workspace(2 * lib.cxrk_coldot_ws_bytes(rows, C), x.device)
     check(lib.cxrk_colstats(xp, xpl, rows, C, _p(mean), _p(var), 1.0 / max(1, rows - 1) if unbiased else 1.0 / rows, _p(ws), ws.numel() * 4,
                             _stream()), f"cxrk_colstats(rows={rows},C={C})")
@@ -511,7 +527,7 @@ def bn_apply(z, scale, shift, residual=None, relu: bool = True, want_mask: bool 
     return y, mask
 
 
-def coldot(a, b, bshift=None) -> torch.Tensor:
+def coldot(a, b, bshift=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out[c] = sum_rows a[r, c] * (b[r, c] - bshift[c]); a, b: [..., C] fp32 or Planes (formats may differ); bshift: fp32 [C] or None."""
     lib = _lib.load()
     C = a.shape[-1]
@@ -520,7 +536,7 @@ def coldot(a, b, bshift=None) -> torch.Tensor:
         raise ValueError(f"coldot: {tuple(a.shape)} vs {tuple(b.shape)}")
     ap, apl = _fmt(a, "coldot.a")
     bp, bpl = _fmt(b, "coldot.b")
-    out = torch.empty(C, dtype=torch.float32, device=a.device)
+    out = torch.empty(C, dtype=torch.float32, device=a.device) if out is None else _vec(out, C, "coldot.out")
     ws = workspace(lib.cxrk_coldot_ws_bytes(rows, C), a.device)
     check(lib.cxrk_coldot(ap, apl, bp, bpl, _p(_vec(bshift, C, "coldot.bshift")) if bshift is not None else None, rows, C, _p(out), _p(ws), ws.numel() * 4, _stream()), "cxrk_coldot")
     return out
@@ -934,14 +950,28 @@ def residual_ln_bwd(dy, xhat, rstd, gamma, dgamma, dbeta, dx_add=None, accumulat
 
 
 def residual_ln_bwd_drop(dy, xhat, rstd, gamma, dgamma, dbeta, drop: Drop, rows_per_seq: int, accumulate: bool = False,
-                         out_planes: bool = False, dxsum=None, dxsum_accumulate: bool = False, mask_dy: bool = False):
+                         out_planes: bool = False, dxsum=None, dxsum_accumulate: bool = False, mask_dy: bool = False, out=None):
     """Backward of y = LayerNorm(keep * s * x + res): returns (dsum, dxm) -- dsum = the gradient of the sum (the residual path), dxm =
     keep * s * dsum (the dense output's gradient), both fp32 or both Planes; `dxsum` receives the column sums of dxm.
-    mask_dy: backward of y = keep * s * LayerNorm(x) instead (the embeddings): returns (dx, None)."""
+    mask_dy: backward of y = keep * s * LayerNorm(x) instead (the embeddings): returns (dx, None).
+    `out`: optional (dx, dxm) pair to write into (both fp32 or both Planes of one plane stride; dxm None with mask_dy)."""
     lib = _lib.load()
     rows, H = dy.shape
-    dx, dxp, dxpl = _new_out(rows, H, dy.device, out_planes)
-    dxm, dxmp = (None, None) if mask_dy else _new_out(rows, H, dy.device, out_planes)[:2]
+    if out is not None:
+        dx, dxm = out
+        _chk_out(dx, (rows, H), "ln.out[0]")
+        if (dxm is None) != bool(mask_dy):
+            raise ValueError("residual_ln_bwd_drop: out = (dx, dxm), dxm None exactly when mask_dy")
+        dxp, dxpl = (dx.ptr(), dx.plane) if isinstance(dx, Planes) else (dx.data_ptr(), 0)
+        dxmp = None
+        if dxm is not None:
+            _chk_out(dxm, (rows, H), "ln.out[1]")
+            if isinstance(dxm, Planes) != isinstance(dx, Planes) or (isinstance(dxm, Planes) and dxm.plane != dxpl):
+                raise ValueError("residual_ln_bwd_drop: dx and dxm must share the storage format and the plane stride")
+            dxmp = dxm.ptr() if isinstance(dxm, Planes) else dxm.data_ptr()
+    else:
+        dx, dxp, dxpl = _new_out(rows, H, dy.device, out_planes)
+        dxm, dxmp = (None, None) if mask_dy else _new_out(rows, H, dy.device, out_planes)[:2]
     wsb = lib.cxrk_residual_ln_bwd_ws_bytes(rows, H)
     ws = workspace(wsb, dy.device)
     check(lib.cxrk_residual_ln_bwd_drop(_p(_chk(dy, "ln.dy")), _p(xhat), _p(rstd), _p(gamma), rows, H, int(rows_per_seq),
@@ -967,9 +997,13 @@ def attn_fwd(qkv, mask, B, L, nH, dH, save_probs: bool = True, out_planes: bool 
     return ctx, probs
 
 
-def attn_bwd(qkv, probs, dctx, B, L, nH, dH, out_planes: bool = False, drop: Optional[Drop] = None):
+def attn_bwd(qkv, probs, dctx, B, L, nH, dH, out_planes: bool = False, drop: Optional[Drop] = None, out=None):
     lib = _lib.load()
-    dqkv, dp, dpl = _new_out(qkv.shape[0], qkv.shape[1], qkv.device, out_planes)
+    if out is None:
+        dqkv, dp, dpl = _new_out(qkv.shape[0], qkv.shape[1], qkv.device, out_planes)
+    else:
+        _chk_out(out, tuple(qkv.shape), "attn.out")
+        dqkv, dp, dpl = (out, out.ptr(), out.plane) if isinstance(out, Planes) else (out, out.data_ptr(), 0)
     wsb = lib.cxrk_attn_bwd_ws_bytes(B, L, nH, dH)        # the dS matrix of the tiled form (L > 64); 0 otherwise
     ws = workspace(wsb, qkv.device) if wsb else None
     if drop is not None:
@@ -1072,16 +1106,25 @@ def pairwise_cosine_fwd(x, y):
     return cosv, xn, yn
 
 
-def pairwise_cosine_bwd(x, y, cosv, dcos, xn, yn, need_dx: bool = True):
+def pairwise_cosine_bwd(x, y, cosv, dcos, xn, yn, need_dx: bool = True, out=None, accumulate_dy: bool = False):
+    """`out`: optional (dx, dy) pair to write into (dx None with need_dx=False); accumulate_dy: dy += instead of dy =."""
     lib = _lib.load()
     B, D = x.shape
     Pn = y.shape[0]
-    dx = torch.empty_like(x) if need_dx else None
-    dy = torch.empty_like(y)
+    if out is None:
+        dx = torch.empty_like(x) if need_dx else None
+        dy = torch.empty_like(y)
+    else:
+        dx, dy = out
+        if (dx is None) != (not need_dx):
+            raise ValueError("pairwise_cosine: out = (dx, dy), dx None exactly when need_dx is False")
+        if dx is not None:
+            _chk_out(dx, (B, D), "cosine.out[0]")
+        _chk_out(dy, (Pn, D), "cosine.out[1]")
     wsb = lib.cxrk_pairwise_cosine_bwd_ws_bytes(B, Pn, D)
     ws = workspace(wsb, x.device)
     check(lib.cxrk_pairwise_cosine_bwd(_p(x), _p(y), _p(cosv), _p(_chk(dcos.contiguous(), "cosine.dcos")), _p(xn), _p(yn),
-                                       B, Pn, D, _p(dx), _p(dy), 0, _p(ws), ws.numel() * 4, _stream()),
+                                       B, Pn, D, _p(dx), _p(dy), int(accumulate_dy), _p(ws), ws.numel() * 4, _stream()),
           "cxrk_pairwise_cosine_bwd")
     return dx, dy
 
@@ -1104,16 +1147,24 @@ def pairwise_cosine_max_fwd(x, y, groups: int):
     return cosv, xn, yn, mx, mean, arg
 
 
-def pairwise_cosine_max_bwd(x, y, cosv, dmax, arg, xn, yn, need_dx: bool = True):
+def pairwise_cosine_max_bwd(x, y, cosv, dmax, arg, xn, yn, need_dx: bool = True, out=None, accumulate_dy: bool = False):
     lib = _lib.load()
     B, D = x.shape
     Pn = y.shape[0]
     G = arg.shape[1]
-    dx = torch.empty_like(x) if need_dx else None
-    dy = torch.empty_like(y)
+    if out is None:
+        dx = torch.empty_like(x) if need_dx else None
+        dy = torch.empty_like(y)
+    else:
+        dx, dy = out
+        if (dx is None) != (not need_dx):
+            raise ValueError("pairwise_cosine: out = (dx, dy), dx None exactly when need_dx is False")
+        if dx is not None:
+            _chk_out(dx, (B, D), "cosine.out[0]")
+        _chk_out(dy, (Pn, D), "cosine.out[1]")
     ws = workspace(lib.cxrk_pairwise_cosine_bwd_ws_bytes(B, Pn, D), x.device)
     check(lib.cxrk_pairwise_cosine_max_bwd(_p(x), _p(y), _p(cosv), _p(_chk(dmax.contiguous(), "cosine.dmax")), _p(arg), _p(xn), _p(yn),
-                                           B, G, Pn // G, D, _p(dx), _p(dy), 0, _p(ws), ws.numel() * 4, _stream()),
+                                           B, G, Pn // G, D, _p(dx), _p(dy), int(accumulate_dy), _p(ws), ws.numel() * 4, _stream()),
           "cxrk_pairwise_cosine_max_bwd")
     return dx, dy
 
@@ -1131,8 +1182,9 @@ def patch_similarity(patches, text):
     return out
 
 
-def bce_posneg_fwd_bwd(cosv, labels, diff: bool = True, need_grad: bool = True):
-    """cos [B,2C] (2c = pos, 2c+1 = neg), labels [B,C] view (stride(1)==1) -> logits [B,C], dcos [B,2C], loss []"""
+def bce_posneg_fwd_bwd(cosv, labels, diff: bool = True, need_grad: bool = True, out=None):
+    """cos [B,2C] (2c = pos, 2c+1 = neg), labels [B,C] view (stride(1)==1) -> logits [B,C], dcos [B,2C], loss []
+    `out`: optional (logits, dcos, loss) triple to write into (dcos None with need_grad=False)."""
     lib = _lib.load()
     B, C2 = cosv.shape
     C = C2 // 2
@@ -1141,9 +1193,18 @@ def bce_posneg_fwd_bwd(cosv, labels, diff: bool = True, need_grad: bool = True):
         labels = labels.unsqueeze(1)
     if labels.shape[1] > 1 and labels.stride(1) != 1:
         labels = labels.contiguous()
-    logits = torch.empty(B, C, dtype=torch.float32, device=cosv.device)
-    dcos = torch.empty_like(cosv) if need_grad else None
-    loss = torch.empty((), dtype=torch.float32, device=cosv.device)
+    if out is None:
+        logits = torch.empty(B, C, dtype=torch.float32, device=cosv.device)
+        dcos = torch.empty_like(cosv) if need_grad else None
+        loss = torch.empty((), dtype=torch.float32, device=cosv.device)
+    else:
+        logits, dcos, loss = out
+        if (dcos is None) != (not need_grad):
+            raise ValueError("bce: out = (logits, dcos, loss), dcos None exactly when need_grad is False")
+        _chk_out(logits, (B, C), "bce.out[0]")
+        if dcos is not None:
+            _chk_out(dcos, (B, C2), "bce.out[1]")
+        _chk_out(loss, (), "bce.out[2]")
     ws = workspace(lib.cxrk_bce_posneg_ws_bytes(), cosv.device)
     check(lib.cxrk_bce_posneg_fwd_bwd(_p(_chk(cosv, "bce.cos")), _p(labels), B, C, labels.stride(0), int(diff), _p(logits),
                                       _p(dcos), _p(loss), _p(ws), ws.numel() * 4, _stream()), "cxrk_bce_posneg_fwd_bwd")
