@@ -268,6 +268,13 @@ int cxrk_gelu_bwd(const float* dy, const float* pre, long n, float* dx, hipStrea
  * infonce:     north-star head (not in the reference): on a logits block S[rows][cols] = X_hat_local @ Y_hat_all^T / tau,
  *              row_lse gives lse + diagonal (+ accumulates sum(lse-diag)*scale into loss_out);
  *              grad_inplace turns S into exp(S-lse_row[i]) + exp(S-lse_col[j]) - 2*[j==diag_off+i].
+ * multipos:    the same head with label-aware targets: every row and column carries a 64-bit key (any int64 value), and the
+ *              positives of row i are the columns j with keys_col[j] == keys_row[i] (n_i of them).  row_stats gives, per row, lse,
+ *              the mean of S[i][j] over the positives (0 when there is none) and n_i as a float (exact: cols < 2^24), in one pass
+ *              over S (+ accumulates sum(lse-posmean)*scale into loss_out, in a fixed order: no atomics);
+ *              grad_inplace turns S into exp(S-lse_row[i]) + exp(S-lse_col[j]) - 2*[keys_row[i]==keys_col[j]] / n_row[i].
+ *              S rows are ld >= cols floats apart; 16-byte accesses where ld % 4 == 0 and the bases are 16-byte aligned, scalar
+ *              otherwise.  No scratch memory: lse / posmean / npos are outputs of the caller.
  * pairwise_cosine: torchmetrics pairwise_cosine_similarity as called by Trainer.myCosineSimilarity (Trainer.py:1682-1704).
  * pairwise_cosine_max: the MAX_EMB branch of the same function (Trainer.py:1691-1693): y holds G groups of Pg prompt
  *              vectors (group g = rows g*Pg .. g*Pg+Pg-1); besides cos [B][G*Pg] it returns, per image and group, the maximum
@@ -287,6 +294,12 @@ int cxrk_infonce_row_lse(const float* S, long ld, int rows, int cols, int diag_o
                          float* loss_out, float loss_scale, int loss_accumulate, hipStream_t stream);
 int cxrk_infonce_grad_inplace(float* S, long ld, int rows, int cols, int diag_off, const float* lse_row,
                               const float* lse_col, hipStream_t stream);
+int cxrk_multipos_row_stats(const float* S, long ld, int rows, int cols, const long long* keys_row,
+                            const long long* keys_col, float* lse, float* posmean, float* npos, float* loss_out,
+                            float loss_scale, int loss_accumulate, hipStream_t stream);
+int cxrk_multipos_grad_inplace(float* S, long ld, int rows, int cols, const long long* keys_row,
+                               const long long* keys_col, const float* n_row, const float* lse_row, const float* lse_col,
+                               hipStream_t stream);
 int cxrk_pairwise_cosine_fwd(const float* x, const float* y, long B, int P, int D, float* cosv, float* xnorm,
                              float* ynorm, hipStream_t stream);
 size_t cxrk_pairwise_cosine_bwd_ws_bytes(long B, int P, int D);

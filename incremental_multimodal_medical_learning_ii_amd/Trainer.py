@@ -19,7 +19,9 @@ Two extensions behind the same entry points (both off unless asked for):
     CXR-BERT forward, InfoNCE over the global batch, hand-written backward, fused Adam) per batch, with the reference's
     iteration / logging / continual-learning bookkeeping around it; `val` / `test` embed the images with the trained image
     model and score them against the class prompts embedded by the trained text model (the zero-shot chain of
-    `Trainer.py:797-837`).  The text model is the one inside `bert_encoder`.
+    `Trainer.py:797-837`).  The text model is the one inside `bert_encoder`.  `"positives": "labels" | "text"` in the dict makes
+    pairs of the global batch with the same label vector / the same prompt tokens positives of each other (multi-positive InfoNCE,
+    DESIGN.md §5.2; "labels" needs the fourth tensor of the batch); the default is one positive per row.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -153,7 +155,8 @@ class Trainer:
             if OPTIM not in ("adam", "sgd"):
                 raise Exception
             self._joint = JointContrastiveTrainer(self.image_model, self.bert_encoder.model, lr=lr,
-                                                  temperature=float(je.get("temperature", 0.07)), group=process_group, optim=OPTIM)
+                                                  temperature=float(je.get("temperature", 0.07)), group=process_group, optim=OPTIM,
+                                                  positives=je.get("positives"))
             print("*** JOINT ENCODER TRAINING (InfoNCE over the global batch): no adapters ***")
         params = []
         if self._joint is not None:
@@ -589,18 +592,27 @@ class Trainer:
 
     def _joint_step(self, batch):
         """The north-star step on one batch `(images, input_ids, attention_mask[, labels])`: this rank's row shard through both
-        encoders, InfoNCE over the global batch, backward, gradient all-reduce, fused optimiser step."""
+        encoders, InfoNCE over the global batch, backward, gradient all-reduce, fused optimiser step.  With
+        `joint_encoders={..., "positives": "labels" | "text"}` the pairs' keys are hashed from the shard's host tensors (the labels
+        need not go to the device) and the loss is the multi-positive one."""
         if len(batch) < 3:
             raise ValueError("joint-encoder training expects loaders that yield (images, input_ids, attention_mask[, labels]); got a "
                              f"batch of {len(batch)} tensors")
         images, ids, mask = batch[0], batch[1], batch[2]
+        positives = self._joint.positives
+        if positives == "labels" and len(batch) < 4:
+            raise ValueError("joint-encoder training with positives='labels' needs the labels: the loader must yield (images, input_ids, "
+                             f"attention_mask, labels [B, C]); got a batch of {len(batch)} tensors")
         n = images.shape[0]
         lo, hi = self._shard(n) if self.world > 1 else (0, n)
         if self.world > 1 and n % self.world:
             raise ValueError(f"joint-encoder training shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
         dev = self.device
+        keys = None
+        if positives is not None:   # once per step, where the loader left the tensors
+            keys = self._joint.pair_keys(ids[lo:hi], mask[lo:hi], batch[3][lo:hi] if positives == "labels" else None)
         loss = self._joint.step(images[lo:hi].to(dev, non_blocking=True), ids[lo:hi].to(dev, non_blocking=True),
-                                mask[lo:hi].to(dev, non_blocking=True))
+                                mask[lo:hi].to(dev, non_blocking=True), keys=keys)
         self._bert_cache.clear()
         return loss
 

@@ -76,6 +76,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_l2norm_bwd": (I, [P, P, L, P, L, I, P, P]),
     "cxrk_infonce_row_lse": (I, [P, L, I, I, I, P, P, P, F, I, P]),
     "cxrk_infonce_grad_inplace": (I, [P, L, I, I, I, P, P, P]),
+    "cxrk_multipos_row_stats": (I, [P, L, I, I, P, P, P, P, P, P, F, I, P]),
+    "cxrk_multipos_grad_inplace": (I, [P, L, I, I, P, P, P, P, P, P]),
     "cxrk_pairwise_cosine_fwd": (I, [P, P, L, I, I, P, P, P, P]),
     "cxrk_pairwise_cosine_bwd_ws_bytes": (Z, [L, I, I]),
     "cxrk_pairwise_cosine_bwd": (I, [P, P, P, P, P, P, L, I, I, P, P, I, P, Z, P]),

@@ -10,6 +10,10 @@ batch is sharded by rows.  Communication per step: all-gather of [B,256] normali
 log-sum-exps, a scalar all-reduce for the reported loss, and the bucketed all-reduce of the ~133 M-parameter flat
 gradient buffer.  This step is NOT in the reference: temperature is an explicit
 argument (default 0.07, the usual CLIP-style value; the reference specifies none).
+
+`positives="labels" | "text"`: label-aware multi-positive targets.  Every pair gets a 64-bit key (`keys_from_labels`,
+`keys_from_tokens`); pairs of the global batch with equal keys are positives of each other.  One more all-gather per step, of the
+[B] int64 keys.  `positives=None` (the default) is the plain loss and issues exactly the calls it always did.
 """
 from __future__ import annotations
 
@@ -21,10 +25,95 @@ from . import functional as Fh
 from . import optim as cxr_optim
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# keys of the multi-positive loss
+# ----------------------------------------------------------------------------------------------------------------
+_M64 = (1 << 64) - 1
+KEY_GOLDEN = 0x9E3779B97F4A7C15     # position multiplier
+KEY_MIX1 = 0xBF58476D1CE4E5B9       # the two multipliers of the splitmix64 finaliser
+KEY_MIX2 = 0x94D049BB133111EB
+
+
+def _i64(c: int) -> int:
+    """the int64 (two's complement) reading of a 64-bit constant"""
+    return c - (1 << 64) if c >= (1 << 63) else c
+
+
+def _lsr(z: torch.Tensor, k: int) -> torch.Tensor:
+    """logical right shift of the 64-bit pattern held in an int64 tensor (torch's >> is arithmetic)"""
+    return (z >> k) & ((1 << (64 - k)) - 1)
+
+
+def _mix64(z: torch.Tensor) -> torch.Tensor:
+    z = (z ^ _lsr(z, 30)) * _i64(KEY_MIX1)
+    z = (z ^ _lsr(z, 27)) * _i64(KEY_MIX2)
+    return z ^ _lsr(z, 31)
+
+
+def row_keys(int_rows: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int [B, L] (+ optional mask [B, L], non-zero = in) -> int64 [B]: a deterministic 64-bit hash of each row's masked-in
+    integer sequence.  Integer tensor ops only, on the device of the input; the same bits on every rank, on CPU and on GPU.
+
+    Exactly, in uint64 arithmetic (everything mod 2^64; the int64 result is the two's-complement reading of the same 64 bits):
+
+        mix(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+        p_t    = number of masked-in positions among 0..t of the row (1 for the first masked-in element; all in without a mask)
+        key    = mix( sum over the masked-in positions t of  mix( mix(x_t) + p_t * 0x9E3779B97F4A7C15 ) )
+
+    with x_t the element as a 64-bit two's-complement pattern and >> the logical shift (mix is the splitmix64 finaliser, a
+    bijection).  A masked-out position contributes nothing and does not advance p, so padding of any length and content leaves the
+    key unchanged; an empty row has key 0.  Two rows with the same masked-in sequence always share a key; two different sequences
+    share one with probability about 2^-64, so a global batch of Bg rows holds a false positive pair with probability about
+    Bg^2 / 2^64 (4e-12 at Bg = 8192)."""
+    if int_rows.dim() != 2:
+        raise ValueError(f"row_keys: expected a [B, L] integer tensor, got shape {tuple(int_rows.shape)}")
+    if int_rows.dtype.is_floating_point or int_rows.dtype.is_complex:
+        raise ValueError(f"row_keys: expected an integer tensor, got {int_rows.dtype}")
+    x = int_rows.to(torch.int64)
+    if mask is None:
+        pos = torch.arange(1, x.shape[1] + 1, dtype=torch.int64, device=x.device).expand_as(x)
+        inn = None
+    else:
+        if tuple(mask.shape) != tuple(x.shape):
+            raise ValueError(f"row_keys: mask {tuple(mask.shape)} does not match the rows {tuple(x.shape)}")
+        inn = (mask != 0).to(device=x.device, dtype=torch.int64)
+        pos = torch.cumsum(inn, dim=1)
+    term = _mix64(_mix64(x) + pos * _i64(KEY_GOLDEN))
+    if inn is not None:
+        term = term * inn
+    return _mix64(term.sum(dim=1))
+
+
+def keys_from_labels(labels: torch.Tensor) -> torch.Tensor:
+    """[B, C] label matrix -> int64 [B] keys: two rows share a key iff their label vectors are equal (up to the collision odds of
+    `row_keys`).  The values must be integral (0.0 / 1.0 floats, bools and integers are fine); anything else raises ValueError."""
+    if not isinstance(labels, torch.Tensor) or labels.dim() != 2:
+        raise ValueError(f"keys_from_labels: expected a [B, C] tensor, got {getattr(labels, 'shape', type(labels).__name__)}")
+    if labels.dtype.is_complex:
+        raise ValueError("keys_from_labels: complex labels")
+    if labels.dtype.is_floating_point:
+        if not bool((torch.isfinite(labels) & (labels == labels.round())).all()):
+            raise ValueError("keys_from_labels: label values must be integral (0.0 / 1.0 floats are fine); soft labels have no "
+                             "equality classes")
+    return row_keys(labels.to(torch.int64))
+
+
+def keys_from_tokens(input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+    """token ids [B, L] + attention mask [B, L] -> int64 [B] keys: two rows share a key iff their unpadded token sequences are
+    equal (up to the collision odds of `row_keys`); the padding's length and content do not matter."""
+    return row_keys(input_ids, attention_mask)
+
+
+POSITIVES = (None, "labels", "text")
+
+
 class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
-                 optim: str = "adam"):
+                 optim: str = "adam", positives: Optional[str] = None):
+        if positives not in POSITIVES:
+            raise ValueError(f"positives must be None, 'labels' or 'text', got {positives!r}")
+        self.positives = positives
         self.image_model, self.text_model = image_model, text_model
         self.temperature, self.group = temperature, group
         import os
@@ -91,17 +180,37 @@ class JointContrastiveTrainer:
         spans = {tag: self.optimizer.grad_span(ps) for tag, ps in groups.items()}
         return {tag: sp for tag, sp in spans.items() if sp is not None}
 
-    def forward_loss(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+    def pair_keys(self, input_ids, attention_mask, labels=None, keys=None) -> Optional[torch.Tensor]:
+        """The int64 [B] keys of this step's pairs, or None for the plain loss.  Explicit `keys` win; otherwise `positives` decides:
+        None -> None (labels are ignored, no arithmetic is issued), "text" -> `keys_from_tokens(input_ids, attention_mask)`,
+        "labels" -> `keys_from_labels(labels)` (ValueError without labels).  The hash runs on the device its inputs are on -- the
+        host, when the loader's tensors are passed as they come -- and `forward_loss` moves the [B] result to the embeddings."""
+        if keys is not None:
+            return keys
+        if self.positives is None:
+            return None
+        if self.positives == "text":
+            return keys_from_tokens(input_ids, attention_mask)
+        if labels is None:
+            raise ValueError("JointContrastiveTrainer(positives='labels'): this step got no labels (pass labels=[B, C] or keys=[B])")
+        return keys_from_labels(labels)
+
+    def forward_loss(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+                     labels: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The two encoders are independent up to the loss, so the text encoder runs on a second HIP stream: the tail of one
         encoder's launch (its last, partly filled round of workgroups) overlaps the head of the other's.  Autograd replays
         each encoder's backward on the stream its forward ran on and joins them again before `backward()` returns.
         Text dropout masks are keyed by the global sequence index: this rank's shard starts at rank * local rows (the shards are
-        equal and contiguous, gathered in rank order)."""
+        equal and contiguous, gathered in rank order).
+        `labels` / `keys`: see `pair_keys`; computed once, before the encoders run."""
+        keys = self.pair_keys(input_ids, attention_mask, labels, keys)
+        if keys is not None:
+            keys = keys.to(images.device, non_blocking=True)
         self.text_model.dropout_row_offset = self.rank * int(input_ids.shape[0])
         if not (self.two_streams and images.is_cuda):
             img = self.image_model(images)
             txt = self.text_model.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
-            return Fh.infonce_loss(img, txt, self.temperature, self.group)
+            return self._loss(img, txt, keys)
         if self._text_stream is None:
             self._text_stream = torch.cuda.Stream(device=images.device)
         cur = torch.cuda.current_stream(images.device)
@@ -111,9 +220,15 @@ class JointContrastiveTrainer:
         img = self.image_model(images)
         cur.wait_stream(self._text_stream)
         txt.record_stream(cur)
-        return Fh.infonce_loss(img, txt, self.temperature, self.group)
+        return self._loss(img, txt, keys)
 
-    def step(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor) -> torch.Tensor:
+    def _loss(self, img, txt, keys):
+        if keys is None:
+            return Fh.infonce_loss(img, txt, self.temperature, self.group)
+        return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys)
+
+    def step(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+             labels: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One optimisation step on this rank's shard; returns the global-batch loss (device scalar, no host sync).
 
         Data-parallel overlap (N > 1): the gradient all-reduce of a range of the flat buffer (`reduce_spans`) is started by the
@@ -141,14 +256,14 @@ class JointContrastiveTrainer:
 
             self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = on_ready
             try:
-                loss = self.forward_loss(images, input_ids, attention_mask)   # the hook is captured by the two autograd nodes here
+                loss = self.forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
             finally:
                 self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
             loss.backward()
             self.last_overlapped = tuple(fired)
             self.optimizer.all_reduce_grads(self.group, skip=[self._spans[t] for t in fired], pending=works)
         else:
-            loss = self.forward_loss(images, input_ids, attention_mask)
+            loss = self.forward_loss(images, input_ids, attention_mask, labels, keys)
             loss.backward()
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)

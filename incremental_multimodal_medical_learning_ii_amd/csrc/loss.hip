@@ -87,6 +87,87 @@ __global__ void lse_loss_kernel(const float* __restrict__ lse, const float* __re
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// multi-positive InfoNCE: the positives of row i are the columns whose 64-bit key equals the row's.
+// ---------------------------------------------------------------------------------------------------------------
+// Per-thread running (max, sum of exp(x - max)) over a strided part of one row, with the matching columns' sum and count.
+struct RowAcc {
+  float m = -INFINITY, s = 0.f, pos = 0.f; int n = 0;
+  __device__ __forceinline__ void rescale(float mx) {   // raise the running maximum to mx >= m
+    if (mx > m) { s *= expf(m - mx); m = mx; }          // (m = -inf: s is 0 and stays 0)
+  }
+  __device__ __forceinline__ void add(float x, bool match) {
+    s += expf(x - m);
+    if (match) { pos += x; ++n; }
+  }
+};
+
+// lse[i] = log sum_j exp(S[i][j]); posmean[i] = mean of S[i][j] over keys_col[j] == keys_row[i]; npos[i] = their number.
+// One 256-thread block per row, ONE pass over the row; VEC: 16-byte loads of S (ld % 4 == 0, base 16-byte aligned).
+template <bool VEC>
+__global__ __launch_bounds__(256) void multipos_row_stats_kernel(const float* __restrict__ S, long ld, int cols,
+                                                                 const long long* __restrict__ keys_row,
+                                                                 const long long* __restrict__ keys_col, float* __restrict__ lse,
+                                                                 float* __restrict__ posmean, float* __restrict__ npos) {
+  __shared__ float sh[16];
+  __shared__ int shn[4];
+  const long row = blockIdx.x;
+  const float* s = S + row * ld;
+  const long long kr = keys_row[row];
+  RowAcc a;
+  int tail = 0;
+  if (VEC) {
+    tail = cols & ~3;
+    for (int j = threadIdx.x * 4; j < tail; j += 1024) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(s + j);
+      a.rescale(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a.add(v[q], keys_col[j + q] == kr);
+    }
+  }
+  for (int j = tail + threadIdx.x; j < cols; j += 256) { const float x = s[j]; a.rescale(x); a.add(x, keys_col[j] == kr); }
+  // merge in a fixed order: block maximum, then the sums rescaled to it
+  const float M = block_max(a.m, sh);
+  const float sum = block_sum(a.m == -INFINITY ? 0.f : a.s * expf(a.m - M), sh);
+  const float pos = block_sum(a.pos, sh);
+  int n = a.n;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0) shn[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    n = (shn[0] + shn[1]) + (shn[2] + shn[3]);
+    lse[row] = M + logf(sum);
+    posmean[row] = n > 0 ? pos / (float)n : 0.f;
+    npos[row] = (float)n;
+  }
+}
+
+// G[i][j] = exp(S[i][j]-lse_row[i]) + exp(S[i][j]-lse_col[j]) - 2*[keys_row[i] == keys_col[j]] / n_row[i], in place.
+// grid (rows, ceil(cols / 1024)); a thread owns 4 consecutive columns: one 16-byte load / store where VEC allows, else scalar.
+template <bool VEC>
+__global__ __launch_bounds__(256) void multipos_grad_kernel(float* __restrict__ S, long ld, int cols,
+                                                            const long long* __restrict__ keys_row,
+                                                            const long long* __restrict__ keys_col, const float* __restrict__ n_row,
+                                                            const float* __restrict__ lse_row, const float* __restrict__ lse_col) {
+  const long i = blockIdx.x;
+  const int j0 = (blockIdx.y * 256 + threadIdx.x) * 4;
+  if (j0 >= cols) return;
+  float* s = S + i * ld;
+  const long long kr = keys_row[i];
+  const float lr = lse_row[i], w = 2.f / n_row[i];
+  if (VEC && j0 + 4 <= cols) {
+    f32x4 v = *reinterpret_cast<const f32x4*>(s + j0);
+    const f32x4 lc = *reinterpret_cast<const f32x4*>(lse_col + j0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = expf(v[q] - lr) + expf(v[q] - lc[q]) - (keys_col[j0 + q] == kr ? w : 0.f);
+    *reinterpret_cast<f32x4*>(s + j0) = v;
+  } else {
+    const int j1 = min(j0 + 4, cols);
+    for (int j = j0; j < j1; ++j) { const float x = s[j]; s[j] = expf(x - lr) + expf(x - lse_col[j]) - (keys_col[j] == kr ? w : 0.f); }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // pairwise cosine: cos[i][p] = <x_i, y_p> / (|x_i| |y_p|)  (no epsilon: torchmetrics semantics)
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void pairwise_cosine_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
@@ -311,6 +392,35 @@ extern "C" int cxrk_infonce_grad_inplace(float* S, long ld, int rows, int cols, 
   const long n = (long)rows * cols;
   hipLaunchKernelGGL(infonce_grad_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, ld, (long)rows, cols,
                      diag_off, lse_row, lse_col);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_multipos_row_stats(const float* S, long ld, int rows, int cols, const long long* keys_row,
+                                       const long long* keys_col, float* lse, float* posmean, float* npos, float* loss_out,
+                                       float loss_scale, int loss_accumulate, hipStream_t stream) {
+  CXRK_CHECK_ARG(S && keys_row && keys_col && lse && posmean && npos && rows > 0 && cols > 0 && ld >= cols);
+  if (ld % 4 == 0 && aligned16(S))
+    hipLaunchKernelGGL(multipos_row_stats_kernel<true>, dim3(rows), dim3(256), 0, stream, S, ld, cols, keys_row, keys_col, lse, posmean, npos);
+  else
+    hipLaunchKernelGGL(multipos_row_stats_kernel<false>, dim3(rows), dim3(256), 0, stream, S, ld, cols, keys_row, keys_col, lse, posmean, npos);
+  CXRK_LAUNCH_CHECK();
+  if (loss_out) {   // sum_i (lse[i] - posmean[i]) * scale, one block, fixed order
+    hipLaunchKernelGGL(lse_loss_kernel, dim3(1), dim3(256), 0, stream, lse, posmean, rows, loss_scale, loss_out, loss_accumulate);
+    CXRK_LAUNCH_CHECK();
+  }
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_multipos_grad_inplace(float* S, long ld, int rows, int cols, const long long* keys_row,
+                                          const long long* keys_col, const float* n_row, const float* lse_row,
+                                          const float* lse_col, hipStream_t stream) {
+  CXRK_CHECK_ARG(S && keys_row && keys_col && n_row && lse_row && lse_col && rows > 0 && cols > 0 && ld >= cols);
+  const dim3 grid(rows, (unsigned)((cols + 1023) / 1024));
+  if (ld % 4 == 0 && aligned16(S) && aligned16(lse_col))
+    hipLaunchKernelGGL(multipos_grad_kernel<true>, grid, dim3(256), 0, stream, S, ld, cols, keys_row, keys_col, n_row, lse_row, lse_col);
+  else
+    hipLaunchKernelGGL(multipos_grad_kernel<false>, grid, dim3(256), 0, stream, S, ld, cols, keys_row, keys_col, n_row, lse_row, lse_col);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }

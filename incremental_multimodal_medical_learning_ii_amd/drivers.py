@@ -119,7 +119,8 @@ def _setup(args, kind):
     if joint:
         im, engine = _joint_models(args, device)
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine,
-                             joint_encoders={"image_model": im, "temperature": args.temperature})
+                             joint_encoders={"image_model": im, "temperature": args.temperature,
+                                             "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None))})
     else:
         from .health_multimodal.text import get_cxr_bert_inference
         engine = get_cxr_bert_inference(args.pretrained_text, device="cuda")
@@ -231,6 +232,9 @@ def make_parser():
     ap.add_argument("--small-text", action="store_true", help="--joint: a 2-layer text model instead of the 12-layer CXR-BERT (quick runs)")
     ap.add_argument("--text-dropout", action="store_true",
                     help="--joint: train the text model in train mode with HF dropout (CXRBertModel.enable_dropout_); default: eval mode")
+    ap.add_argument("--positives", default="pair", choices=["pair", "labels", "text"],
+                    help="--joint: the positives of a pair in the InfoNCE loss: only itself (pair, default), every pair of the global "
+                         "batch with the same label vector (labels) or the same prompt text (text)")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -240,6 +244,9 @@ def main(argv=None):
     if args.text_dropout and not args.joint:
         raise SystemExit("--text-dropout trains the text encoder in-loop and needs --joint (the adapter schedules use frozen "
                          "pre-computed text embeddings)")
+    if args.positives != "pair" and not args.joint:
+        raise SystemExit("--positives selects the targets of the north-star InfoNCE step and needs --joint (the adapter schedules "
+                         "use the labels through the pos-neg BCE loss)")
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)
     if int(os.environ.get("RANK", "0")) == 0:

@@ -214,10 +214,19 @@ class _InfoNCE(torch.autograd.Function):
     [B, 2D] embeddings and one of the [B, 2] log-sum-exps is all the communication: every rank then holds what it
     needs to form the exact gradient of the global-mean loss w.r.t. its own rows — no reduce-scatter of embedding
     gradients and no second matmul exchange.
+
+    With `keys` (int64 [B], one per local pair; image i and text i share it) the targets are multi-positive: the positives of
+    row i are the columns j of the global batch with k_j = k_i (n_i of them, i itself included), and
+        loss = 1/(2 Bg) sum_i [ lse_row_i - 1/n_i sum_{j in P(i)} S_ij ]  +  the same over the columns,
+        dL/dS_ij = ( softmax_row_ij + softmax_col_ij - 2 [k_i = k_j] / n_i ) / (2 Bg).
+    Data-parallel: one more all-gather, of the [B] keys, issued next to the embedding gather.  The row keys of S1 and S2 are the
+    local slice, the column keys the gathered vector, and n_i comes from the stats kernel (it counts against the global columns).
+    Because a key belongs to a PAIR, entry (i, j) matches exactly when (j, i) does, so the column count of a matching entry equals
+    its row count (n_j = n_i): the column term needs no exchange of counts.  With all keys distinct this is the plain loss.
     """
 
     @staticmethod
-    def forward(ctx, img, txt, temperature, group):
+    def forward(ctx, img, txt, temperature, group, keys=None):
         import torch.distributed as dist
         dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         img, txt = img.detach().contiguous(), txt.detach().contiguous()
@@ -230,6 +239,15 @@ class _InfoNCE(torch.autograd.Function):
             # is issued, not inside loss.backward() with the other ranks already waiting in the gradient all-reduce
             raise ValueError(f"infonce_loss: global batch {B * world_} (= {B} rows x {world_} ranks) and embedding size {D} must be "
                              f"multiples of 4 (drop or pad the ragged last batch)")
+        if keys is not None:
+            # the same rule: a bad `keys` fails on this rank before any collective is issued
+            if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
+                raise ValueError(f"infonce_loss: keys must be an int64 tensor, got {getattr(keys, 'dtype', type(keys).__name__)}")
+            if tuple(keys.shape) != (B,):
+                raise ValueError(f"infonce_loss: keys must have shape ({B},), one per local row, got {tuple(keys.shape)}")
+            if keys.device != img.device:
+                raise ValueError(f"infonce_loss: keys are on {keys.device} but the embeddings on {img.device}")
+            keys = keys.detach().contiguous()
         if dist_on:
             # image and text halves of ONE [B, 2D] send buffer, written in place by the normalisation kernels; the gathered
             # [Bg, 2D] buffer is read by the GEMMs through its column halves (row stride 2D): no cat / contiguous copies
@@ -238,12 +256,14 @@ class _InfoNCE(torch.autograd.Function):
             ih, inorm = K.l2norm_fwd(img, out=send[:, :D])
             th, tnorm = K.l2norm_fwd(txt, out=send[:, D:])
             both = _all_gather_rows(send, group)                           # [Bg, 2D]
+            keys_all = _all_gather_rows(keys, group) if keys is not None else None      # [Bg] int64
             ih_all, th_all = both[:, :D], both[:, D:]
         else:
             rank, world = 0, 1
             ih, inorm = K.l2norm_fwd(img)
             th, tnorm = K.l2norm_fwd(txt)
             ih_all, th_all = ih, th
+            keys_all = keys
         Bg = B * world
         off = rank * B
         inv_tau = 1.0 / float(temperature)
@@ -252,8 +272,13 @@ class _InfoNCE(torch.autograd.Function):
         K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=inv_tau)
         K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=inv_tau)
         loss = torch.zeros((), dtype=torch.float32, device=img.device)
-        lse1, _ = K.infonce_row_lse(S1, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-        lse2, _ = K.infonce_row_lse(S2, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+        if keys is None:
+            lse1, _ = K.infonce_row_lse(S1, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+            lse2, _ = K.infonce_row_lse(S2, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+            npos = None
+        else:
+            lse1, _, npos = K.multipos_row_stats(S1, keys, keys_all, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+            lse2, _, _ = K.multipos_row_stats(S2, keys, keys_all, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
         if dist_on:
             dist.all_reduce(loss, group=group)
             lse1_all, lse2_all = _all_gather_rows(lse1, group), _all_gather_rows(lse2, group)   # [Bg] each (4 KiB per rank)
@@ -261,6 +286,7 @@ class _InfoNCE(torch.autograd.Function):
             lse1_all, lse2_all = lse1, lse2
         ctx.save_for_backward(S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm)
         ctx.meta = (off, inv_tau, Bg)
+        ctx.keys = None if keys is None else (keys, keys_all, npos)   # integer / count tensors: not autograd inputs or outputs
         return loss
 
     @staticmethod
@@ -269,8 +295,13 @@ class _InfoNCE(torch.autograd.Function):
         off, inv_tau, Bg = ctx.meta
         B, D = ih.shape
         # dL/dS_ij = (softmax_row + softmax_col - 2*delta) / (2 Bg); fold 1/tau and the upstream scalar into alpha
-        K.infonce_grad_inplace(S1, off, lse1, lse2_all)
-        K.infonce_grad_inplace(S2, off, lse2, lse1_all)
+        if ctx.keys is None:
+            K.infonce_grad_inplace(S1, off, lse1, lse2_all)
+            K.infonce_grad_inplace(S2, off, lse2, lse1_all)
+        else:
+            keys, keys_all, npos = ctx.keys
+            K.multipos_grad_inplace(S1, keys, keys_all, npos, lse1, lse2_all)
+            K.multipos_grad_inplace(S2, keys, keys_all, npos, lse2, lse1_all)
         c = inv_tau * 0.5 / Bg
         dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
         dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
@@ -279,12 +310,17 @@ class _InfoNCE(torch.autograd.Function):
         di = K.l2norm_bwd(dih, ih, inorm)
         dt = K.l2norm_bwd(dth, th, tnorm)
         g = gloss.reshape(()).contiguous()
-        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None
+        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None, None
 
 
-def infonce_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: float = 0.07, group=None) -> torch.Tensor:
-    """Symmetric InfoNCE over the global batch (all ranks of `group`, or the default group when initialised)."""
-    return _InfoNCE.apply(img_emb, txt_emb, temperature, group)
+def infonce_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: float = 0.07, group=None,
+                 keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Symmetric InfoNCE over the global batch (all ranks of `group`, or the default group when initialised).
+
+    `keys` (optional): int64 [B] on the embeddings' device, one key per local (image, text) pair; pairs of the global batch with
+    equal keys are positives of each other (multi-positive targets, see `_InfoNCE`; `contrastive.keys_from_labels` /
+    `keys_from_tokens` build them).  `keys=None` is the plain loss: one positive per row, the diagonal."""
+    return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys)
 
 
 @torch.no_grad()

@@ -1090,6 +1090,36 @@ def infonce_grad_inplace(S, diag_off, lse_row, lse_col):
     return S
 
 
+def _keys(k, n, what):
+    _chk(k, what, torch.int64)
+    if k.dim() != 1 or k.shape[0] != n or not k.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous int64 [{n}] tensor, got shape {tuple(k.shape)}")
+    return k
+
+
+def multipos_row_stats(S, keys_row, keys_col, loss_out=None, loss_scale: float = 0.0, loss_accumulate: bool = False):
+    """(lse, posmean, npos) per row of S: the positives of row i are the columns j with keys_col[j] == keys_row[i]."""
+    lib = _lib.load()
+    rows, cols = S.shape
+    lse = torch.empty(rows, dtype=torch.float32, device=S.device)
+    posmean = torch.empty(rows, dtype=torch.float32, device=S.device)
+    npos = torch.empty(rows, dtype=torch.float32, device=S.device)
+    check(lib.cxrk_multipos_row_stats(_p(_chk(S, "multipos.S")), S.stride(0), rows, cols, _p(_keys(keys_row, rows, "multipos.keys_row")),
+                                      _p(_keys(keys_col, cols, "multipos.keys_col")), _p(lse), _p(posmean), _p(npos), _p(loss_out),
+                                      float(loss_scale), int(loss_accumulate), _stream()),
+          "cxrk_multipos_row_stats")
+    return lse, posmean, npos
+
+
+def multipos_grad_inplace(S, keys_row, keys_col, n_row, lse_row, lse_col):
+    lib = _lib.load()
+    rows, cols = S.shape
+    check(lib.cxrk_multipos_grad_inplace(_p(S), S.stride(0), rows, cols, _p(_keys(keys_row, rows, "multipos.keys_row")),
+                                         _p(_keys(keys_col, cols, "multipos.keys_col")), _p(n_row), _p(lse_row), _p(lse_col), _stream()),
+          "cxrk_multipos_grad_inplace")
+    return S
+
+
 def pairwise_cosine_fwd(x, y):
     lib = _lib.load()
     x = _chk(x, "cosine.x").contiguous()
