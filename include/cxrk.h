@@ -275,6 +275,16 @@ int cxrk_gelu_bwd(const float* dy, const float* pre, long n, float* dx, hipStrea
  *              grad_inplace turns S into exp(S-lse_row[i]) + exp(S-lse_col[j]) - 2*[keys_row[i]==keys_col[j]] / n_row[i].
  *              S rows are ld >= cols floats apart; 16-byte accesses where ld % 4 == 0 and the bases are 16-byte aligned, scalar
  *              otherwise.  No scratch memory: lse / posmean / npos are outputs of the caller.
+ * *_scaled:    the two heads with a LEARNABLE temperature: the block holds the unscaled cosines C (logits GEMM with alpha = 1) and
+ *              log_scale points at theta = log(1/tau) on the device; the logits are x = exp(theta) * c.  row_lse_scaled /
+ *              row_stats_scaled write what their fixed-temperature forms write, computed on x in one pass over each row.
+ *              grad_scaled_inplace turns C into exp(theta) * g (g = the gradient term of the fixed-temperature form on x), so the
+ *              backward GEMMs need nothing of theta on the host, and writes the partial sums of g * x that make d theta:
+ *              partials[i * nchunk + k] = sum of g*x over columns [1024 k, 1024 (k+1)) of row i, nchunk = ceil(cols / 1024); the
+ *              caller provides rows * nchunk floats and every one of them is written (an output, not scratch memory).
+ * logit_scale_grad: dtheta[0] = (accumulate ? dtheta[0] : 0) + upstream[0] * scale * (sum partials1[0..n1) + sum partials2[0..n2));
+ *              one block, fixed order; upstream is a device scalar; partials2 may be NULL with n2 = 0.
+ * clamp_inplace: x[i] = min(max(x[i], lo), hi) for lo <= hi; a NaN stays a NaN.
  * pairwise_cosine: torchmetrics pairwise_cosine_similarity as called by Trainer.myCosineSimilarity (Trainer.py:1682-1704).
  * pairwise_cosine_max: the MAX_EMB branch of the same function (Trainer.py:1691-1693): y holds G groups of Pg prompt
  *              vectors (group g = rows g*Pg .. g*Pg+Pg-1); besides cos [B][G*Pg] it returns, per image and group, the maximum
@@ -300,6 +310,19 @@ int cxrk_multipos_row_stats(const float* S, long ld, int rows, int cols, const l
 int cxrk_multipos_grad_inplace(float* S, long ld, int rows, int cols, const long long* keys_row,
                                const long long* keys_col, const float* n_row, const float* lse_row, const float* lse_col,
                                hipStream_t stream);
+int cxrk_infonce_row_lse_scaled(const float* C, long ld, int rows, int cols, int diag_off, const float* log_scale, float* lse,
+                                float* diag, float* loss_out, float loss_scale, int loss_accumulate, hipStream_t stream);
+int cxrk_infonce_grad_scaled_inplace(float* C, long ld, int rows, int cols, int diag_off, const float* lse_row,
+                                     const float* lse_col, const float* log_scale, float* partials, hipStream_t stream);
+int cxrk_multipos_row_stats_scaled(const float* C, long ld, int rows, int cols, const long long* keys_row,
+                                   const long long* keys_col, const float* log_scale, float* lse, float* posmean, float* npos,
+                                   float* loss_out, float loss_scale, int loss_accumulate, hipStream_t stream);
+int cxrk_multipos_grad_scaled_inplace(float* C, long ld, int rows, int cols, const long long* keys_row,
+                                      const long long* keys_col, const float* n_row, const float* lse_row, const float* lse_col,
+                                      const float* log_scale, float* partials, hipStream_t stream);
+int cxrk_logit_scale_grad(const float* partials1, long n1, const float* partials2, long n2, const float* upstream, float scale,
+                          float* dtheta, int accumulate, hipStream_t stream);
+int cxrk_clamp_inplace(float* x, long n, float lo, float hi, hipStream_t stream);
 int cxrk_pairwise_cosine_fwd(const float* x, const float* y, long B, int P, int D, float* cosv, float* xnorm,
                              float* ynorm, hipStream_t stream);
 size_t cxrk_pairwise_cosine_bwd_ws_bytes(long B, int P, int D);

@@ -21,7 +21,9 @@ Two extensions behind the same entry points (both off unless asked for):
     model and score them against the class prompts embedded by the trained text model (the zero-shot chain of
     `Trainer.py:797-837`).  The text model is the one inside `bert_encoder`.  `"positives": "labels" | "text"` in the dict makes
     pairs of the global batch with the same label vector / the same prompt tokens positives of each other (multi-positive InfoNCE,
-    DESIGN.md §5.2; "labels" needs the fourth tensor of the batch); the default is one positive per row.
+    DESIGN.md §5.2; "labels" needs the fourth tensor of the batch); the default is one positive per row.  `"learn_temperature": True`
+    (optionally `"log_scale_bounds": (lo, hi)`) makes the temperature a parameter: "temperature" is then its initial
+    value, `save` / `load` carry it as `logit_scale.pt`, and `train` logs `train/temperature` once per epoch.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -156,7 +158,8 @@ class Trainer:
                 raise Exception
             self._joint = JointContrastiveTrainer(self.image_model, self.bert_encoder.model, lr=lr,
                                                   temperature=float(je.get("temperature", 0.07)), group=process_group, optim=OPTIM,
-                                                  positives=je.get("positives"))
+                                                  positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
+                                                  **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}))
             print("*** JOINT ENCODER TRAINING (InfoNCE over the global batch): no adapters ***")
         params = []
         if self._joint is not None:
@@ -641,6 +644,7 @@ class Trainer:
                 self.writer.add_scalar('train/LR', self.optimizer.param_groups[0]['lr'], iteration)
         if cl:
             self.myIncremental_save_log(iteration)
+        self._log_temperature(epoch)
 
     def train_class_incremental(self, train_loader, criterion, epoch, CONTINUAL_LEARNING=None, threshold=None,
                                 current_task=None, last_batch=0, actual_task=None):
@@ -661,6 +665,7 @@ class Trainer:
                 self.writer.add_scalar('train/Loss', loss, batch_idx)
         if cl:
             self.myIncremental_save_log(batch_idx)
+        self._log_temperature(epoch)
         return batch_idx
 
     def train_class_more_labels_incremental(self, train_loader, criterion, epoch, CONTINUAL_LEARNING=None, threshold=None,
@@ -682,7 +687,13 @@ class Trainer:
                 self.writer.add_scalar('train/Loss', loss, batch_idx)
         if cl:
             self.myIncremental_save_log(batch_idx)
+        self._log_temperature(epoch)
         return batch_idx
+
+    def _log_temperature(self, epoch):
+        """the learned temperature, once per epoch (the one read-back of the logit scale; never inside the step loop)"""
+        if self._joint is not None and self._joint.logit_scale is not None and self.writer is not None:
+            self.writer.add_scalar('train/temperature', self._joint.current_temperature(), epoch)
 
     @torch.no_grad()
     def _eval_loop(self, loader, criterion, epoch, log_tag):
@@ -768,6 +779,11 @@ class Trainer:
             flat, base = self.optimizer.flat_p, self.optimizer.flat_p.data_ptr()
             for p in self.optimizer.params:
                 o, n = (p.data_ptr() - base) // 4, p.numel()
+                if p is self._joint.logit_scale:
+                    # one element: min = max of |new - old|, so `d < min + threshold * (max - min)` never holds and the learned
+                    # temperature is never restored; said here instead of left to that arithmetic, and counted as updated
+                    self._reset_total += n
+                    continue
                 K.weight_reset(flat[o:o + n], self._flat_copy[o:o + n], threshold, self._reset_counters)
                 self._reset_total += n
 
@@ -814,6 +830,8 @@ class Trainer:
         if self._joint is not None and self.rank == 0:
             torch.save(self.image_model.state_dict(), os.path.join(self.writer.log_dir, 'image_model.pt'))
             torch.save(self.bert_encoder.model.state_dict(), os.path.join(self.writer.log_dir, 'text_model.pt'))
+            if self._joint.logit_scale is not None:
+                torch.save({"logit_scale": self._joint.logit_scale.detach().cpu()}, os.path.join(self.writer.log_dir, 'logit_scale.pt'))
         if hasattr(self.writer, "flush"):
             self.writer.flush()
 
@@ -841,4 +859,7 @@ class Trainer:
                     own = mod.state_dict()
                     for k, v in sd.items():
                         own[k].copy_(v)
+            if self._joint.logit_scale is not None:
+                sd = torch.load(os.path.join(self.writer.log_dir, 'logit_scale.pt'), map_location="cpu", weights_only=True)
+                self._joint.logit_scale.data.copy_(sd["logit_scale"].reshape(1))
             self._bert_cache.clear()

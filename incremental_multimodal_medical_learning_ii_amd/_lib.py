@@ -78,6 +78,12 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_infonce_grad_inplace": (I, [P, L, I, I, I, P, P, P]),
     "cxrk_multipos_row_stats": (I, [P, L, I, I, P, P, P, P, P, P, F, I, P]),
     "cxrk_multipos_grad_inplace": (I, [P, L, I, I, P, P, P, P, P, P]),
+    "cxrk_infonce_row_lse_scaled": (I, [P, L, I, I, I, P, P, P, P, F, I, P]),
+    "cxrk_infonce_grad_scaled_inplace": (I, [P, L, I, I, I, P, P, P, P, P]),
+    "cxrk_multipos_row_stats_scaled": (I, [P, L, I, I, P, P, P, P, P, P, P, F, I, P]),
+    "cxrk_multipos_grad_scaled_inplace": (I, [P, L, I, I, P, P, P, P, P, P, P, P]),
+    "cxrk_logit_scale_grad": (I, [P, L, P, L, P, F, P, I, P]),
+    "cxrk_clamp_inplace": (I, [P, L, F, F, P]),
     "cxrk_pairwise_cosine_fwd": (I, [P, P, L, I, I, P, P, P, P]),
     "cxrk_pairwise_cosine_bwd_ws_bytes": (Z, [L, I, I]),
     "cxrk_pairwise_cosine_bwd": (I, [P, P, P, P, P, P, L, I, I, P, P, I, P, Z, P]),

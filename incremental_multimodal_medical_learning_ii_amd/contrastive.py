@@ -14,14 +14,22 @@ argument (default 0.07, the usual CLIP-style value; the reference specifies none
 `positives="labels" | "text"`: label-aware multi-positive targets.  Every pair gets a 64-bit key (`keys_from_labels`,
 `keys_from_tokens`); pairs of the global batch with equal keys are positives of each other.  One more all-gather per step, of the
 [B] int64 keys.  `positives=None` (the default) is the plain loss and issues exactly the calls it always did.
+
+`learn_temperature=True`: the temperature is a parameter.  The trainer owns `logit_scale` = theta = log(1/tau), as
+CLIP parametrises it, initialised from `temperature`; it sits in the flat buffers behind the text encoder, takes the same optimiser
+step, and is clamped to `log_scale_bounds` after it.  The loss kernels read theta on the device; its gradient travels in the flat
+gradient all-reduce (at the end of the "text" span): no new collective, no host sync.  `learn_temperature=False` (the default) creates no parameter and issues
+exactly the calls it always did.
 """
 from __future__ import annotations
 
-from typing import Optional
+import math
+from typing import Optional, Tuple
 
 import torch
 
 from . import functional as Fh
+from . import kernels as K
 from . import optim as cxr_optim
 
 
@@ -105,14 +113,24 @@ def keys_from_tokens(input_ids: torch.Tensor, attention_mask: torch.Tensor) -> t
 
 
 POSITIVES = (None, "labels", "text")
+LOG_SCALE_BOUNDS = (0.0, math.log(100.0))     # CLIP / open_clip: tau in [0.01, 1]
 
 
 class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
-                 optim: str = "adam", positives: Optional[str] = None):
+                 optim: str = "adam", positives: Optional[str] = None, learn_temperature: bool = False,
+                 log_scale_bounds: Tuple[float, float] = LOG_SCALE_BOUNDS):
         if positives not in POSITIVES:
             raise ValueError(f"positives must be None, 'labels' or 'text', got {positives!r}")
+        self.logit_scale = None
+        if learn_temperature:
+            lo, hi = (float(v) for v in log_scale_bounds)
+            if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+                raise ValueError(f"log_scale_bounds must be finite with lo <= hi, got {log_scale_bounds!r}")
+            if not temperature > 0:
+                raise ValueError(f"learn_temperature: the initial temperature must be positive, got {temperature!r}")
+            self.log_scale_bounds = (lo, hi)
         self.positives = positives
         self.image_model, self.text_model = image_model, text_model
         self.temperature, self.group = temperature, group
@@ -128,6 +146,13 @@ class JointContrastiveTrainer:
             if n.startswith("cls.predictions.") and not train_mlm_head:
                 continue  # MLM head: no gradient on this path
             tparams.append(p)
+        if learn_temperature:
+            # behind the text parameters: the "text" reduce span stays gap-free and runs on over theta's slot (`reduce_spans`), so
+            # the spans still tile the buffer and the final flat all-reduce has nothing left.  Every rank derives theta from the same
+            # `temperature`; `Trainer`'s initial broadcast of the flat parameter buffer covers it as well.
+            dev = next(image_model.parameters()).device
+            self.logit_scale = torch.nn.Parameter(torch.tensor([math.log(1.0 / float(temperature))], dtype=torch.float32, device=dev))
+            tparams = tparams + [self.logit_scale]
         if optim == "adam":          # the reference's `optim.Adam(params, lr)` / `optim.SGD(params, lr)` (Trainer.py:172-178)
             self.optimizer = cxr_optim.Adam(params + tparams, lr=lr)
         elif optim == "sgd":
@@ -143,6 +168,12 @@ class JointContrastiveTrainer:
         self._dropout_synced = None
         self.sync_dropout_state()
         self._spans = self.reduce_spans(inamed, tparams) if self.world > 1 else {}
+
+    def current_temperature(self) -> float:
+        """tau = exp(-theta) as a host float: the one place that reads theta back (a host sync), and only when called."""
+        if self.logit_scale is None:
+            return float(self.temperature)
+        return math.exp(-float(self.logit_scale.detach().cpu()))
 
     def sync_dropout_state(self) -> None:
         """Text dropout under data parallelism: every rank takes rank 0's (seed, counter), so that with the row offset of
@@ -164,7 +195,9 @@ class JointContrastiveTrainer:
 
     def reduce_spans(self, inamed=None, tparams=None) -> dict:
         """{tag: (lo, hi)} element ranges of the flat gradient buffer that become complete together during `backward()`, in the
-        order they complete: "text" (the whole text encoder: its backward is a third of the step's and ends first), then the
+        order they complete: "text" (the whole text encoder: its backward is a third of the step's and ends first; with
+        `learn_temperature` also theta's slot behind it, which the loss's backward has written before the text encoder's backward
+        starts, on the stream that backward then waits for), then the
         image encoder from the back: "head" (projector + layer4), "layer3", "layer2", "stem" (layer1 + stem).  Each range is
         all-reduced as soon as its gradients are complete (hooks on the encoders' backward, see `step`), under the rest of the
         backward; a tag whose parameters do not form one gap-free range is left to the final reduce."""
@@ -174,6 +207,8 @@ class JointContrastiveTrainer:
         if tparams is None:
             ids = {id(p) for p in self.optimizer.params}
             tparams = [p for p in self.text_model.parameters() if id(p) in ids]
+            if self.logit_scale is not None:
+                tparams.append(self.logit_scale)
         groups = {"text": list(tparams)}
         for n, p in inamed:
             groups.setdefault(stage_of_param(n), []).append(p)
@@ -223,6 +258,8 @@ class JointContrastiveTrainer:
         return self._loss(img, txt, keys)
 
     def _loss(self, img, txt, keys):
+        if self.logit_scale is not None:
+            return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys, log_scale=self.logit_scale)
         if keys is None:
             return Fh.infonce_loss(img, txt, self.temperature, self.group)
         return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys)
@@ -268,4 +305,6 @@ class JointContrastiveTrainer:
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)
         self.optimizer.step()
+        if self.logit_scale is not None:
+            K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)
         return loss.detach()

@@ -1,7 +1,8 @@
 // Similarity + loss heads.
 //  * L2 row normalisation fwd/bwd (F.normalize semantics, eps on the norm)
 //  * InfoNCE pieces on a materialised logits block S[B][Bg] (the logits GEMMs run on the shared MFMA mainloop):
-//    row log-sum-exp + diagonal pick, and the in-place softmax-gradient transform
+//    row log-sum-exp + diagonal pick, and the in-place softmax-gradient transform; their multi-positive (keyed) forms; and the
+//    forms with a learnable temperature (device logit scale, fused d theta partial sums)
 //  * torchmetrics-style pairwise cosine fwd/bwd (reference Trainer.myCosineSimilarity, Trainer.py:1682-1704)
 //  * pos-neg logits + BCE-with-logits(mean) fwd+bwd in one pass (Trainer.py:575-583, ZERO_JOINT_BOUNDS.py:36)
 //  * eval scoring (Trainer.py:797-837)
@@ -165,6 +166,134 @@ __global__ __launch_bounds__(256) void multipos_grad_kernel(float* __restrict__ 
     const int j1 = min(j0 + 4, cols);
     for (int j = j0; j < j1; ++j) { const float x = s[j]; s[j] = expf(x - lr) + expf(x - lse_col[j]) - (keys_col[j] == kr ? w : 0.f); }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// learnable temperature: the block holds the unscaled cosines C, the logits are x = s * c with s = exp(theta), theta on the device.
+// ---------------------------------------------------------------------------------------------------------------
+// RowAcc in cosine space: s > 0, so the row maximum of x is s * (the maximum of c).  M = fl(s * mc) is the offset every exponent of the
+// row is taken against with ONE rounding, fma(s, c, -M); M's own rounding cancels in lse = M + log(sum).
+struct ScaledRowAcc {
+  float mc = -INFINITY, M = -INFINITY, s = 0.f, pos = 0.f; int n = 0;
+  __device__ __forceinline__ void rescale(float c, float sc) {
+    if (c > mc) { const float Mn = sc * c; s *= expf(M - Mn); mc = c; M = Mn; }   // (M = -inf: s is 0 and stays 0)
+  }
+  __device__ __forceinline__ void add(float c, float sc, bool match) {
+    s += expf(fmaf(sc, c, -M));
+    if (match) { pos += sc * c; ++n; }
+  }
+};
+
+// multipos_row_stats_kernel on x = exp(*log_scale) * C.  KEYED: positives by key; else the one positive of row i is column
+// diag_off + i (posmean = the diagonal logit, npos unused).  One pass over the row in both forms.
+template <bool VEC, bool KEYED>
+__global__ __launch_bounds__(256) void scaled_row_stats_kernel(const float* __restrict__ C, long ld, int cols, int diag_off,
+                                                               const long long* __restrict__ keys_row,
+                                                               const long long* __restrict__ keys_col,
+                                                               const float* __restrict__ log_scale, float* __restrict__ lse,
+                                                               float* __restrict__ posmean, float* __restrict__ npos) {
+  __shared__ float sh[16];
+  __shared__ int shn[4];
+  const long row = blockIdx.x;
+  const float* c = C + row * ld;
+  const float sc = expf(log_scale[0]);
+  const long long kr = KEYED ? keys_row[row] : 0;
+  const int dcol = diag_off + (int)row;
+  ScaledRowAcc a;
+  int tail = 0;
+  if (VEC) {
+    tail = cols & ~3;
+    for (int j = threadIdx.x * 4; j < tail; j += 1024) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(c + j);
+      a.rescale(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), sc);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) a.add(v[q], sc, KEYED ? keys_col[j + q] == kr : j + q == dcol);
+    }
+  }
+  for (int j = tail + threadIdx.x; j < cols; j += 256) {
+    const float x = c[j];
+    a.rescale(x, sc);
+    a.add(x, sc, KEYED ? keys_col[j] == kr : j == dcol);
+  }
+  // merge in a fixed order: block maximum, then the sums rescaled to it
+  const float M = block_max(a.M, sh);
+  const float sum = block_sum(a.M == -INFINITY ? 0.f : a.s * expf(a.M - M), sh);
+  const float pos = block_sum(a.pos, sh);
+  int n = a.n;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+  if ((threadIdx.x & 63) == 0) shn[threadIdx.x >> 6] = n;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    n = (shn[0] + shn[1]) + (shn[2] + shn[3]);
+    lse[row] = M + logf(sum);
+    posmean[row] = n > 0 ? pos / (float)n : 0.f;
+    if (KEYED) npos[row] = (float)n;
+  }
+}
+
+// In place on C, with x = s * c:  g = exp(x-lse_row[i]) + exp(x-lse_col[j]) - 2*[positive(i,j)] / n_i;  C[i][j] <- s * g, and
+// part[i * gridDim.y + chunk] = sum over the chunk's columns of g * x (block_sum: fixed order).  grid (rows, ceil(cols / 1024)), a
+// thread owns 4 consecutive columns as in multipos_grad_kernel.  No thread leaves before the block sum.
+template <bool VEC, bool KEYED>
+__global__ __launch_bounds__(256) void scaled_grad_kernel(float* __restrict__ C, long ld, int cols, int diag_off,
+                                                          const long long* __restrict__ keys_row,
+                                                          const long long* __restrict__ keys_col, const float* __restrict__ n_row,
+                                                          const float* __restrict__ lse_row, const float* __restrict__ lse_col,
+                                                          const float* __restrict__ log_scale, float* __restrict__ part) {
+  __shared__ float sh[16];
+  const long i = blockIdx.x;
+  const int j0 = (blockIdx.y * 256 + threadIdx.x) * 4;
+  float* c = C + i * ld;
+  const float sc = expf(log_scale[0]);
+  const long long kr = KEYED ? keys_row[i] : 0;
+  const int dcol = diag_off + (int)i;
+  const float lr = lse_row[i], w = KEYED ? 2.f / n_row[i] : 2.f;
+  float acc = 0.f;
+  if (VEC && j0 + 4 <= cols) {
+    f32x4 v = *reinterpret_cast<const f32x4*>(c + j0);
+    const f32x4 lc = *reinterpret_cast<const f32x4*>(lse_col + j0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const bool match = KEYED ? keys_col[j0 + q] == kr : j0 + q == dcol;
+      const float g = expf(fmaf(sc, v[q], -lr)) + expf(fmaf(sc, v[q], -lc[q])) - (match ? w : 0.f);
+      acc += g * (sc * v[q]);
+      v[q] = sc * g;
+    }
+    *reinterpret_cast<f32x4*>(c + j0) = v;
+  } else if (j0 < cols) {
+    const int j1 = min(j0 + 4, cols);
+    for (int j = j0; j < j1; ++j) {
+      const float x = c[j];
+      const bool match = KEYED ? keys_col[j] == kr : j == dcol;
+      const float g = expf(fmaf(sc, x, -lr)) + expf(fmaf(sc, x, -lse_col[j])) - (match ? w : 0.f);
+      acc += g * (sc * x);
+      c[j] = sc * g;
+    }
+  }
+  acc = block_sum(acc, sh);
+  if (threadIdx.x == 0) part[i * gridDim.y + blockIdx.y] = acc;
+}
+
+// dtheta[0] (+)= upstream[0] * scale * (sum part1 + sum part2); single block, fixed order.
+__global__ __launch_bounds__(256) void logit_scale_grad_kernel(const float* __restrict__ part1, long n1,
+                                                               const float* __restrict__ part2, long n2,
+                                                               const float* __restrict__ upstream, float scale,
+                                                               float* __restrict__ dtheta, int accumulate) {
+  __shared__ float sh[16];
+  float s1 = 0.f, s2 = 0.f;
+  for (long i = threadIdx.x; i < n1; i += 256) s1 += part1[i];
+  for (long i = threadIdx.x; i < n2; i += 256) s2 += part2[i];
+  const float s = block_sum(s1, sh) + block_sum(s2, sh);
+  if (threadIdx.x == 0) { const float v = upstream[0] * scale * s; dtheta[0] = accumulate ? dtheta[0] + v : v; }
+}
+
+// x <- min(max(x, lo), hi) by comparisons, which are false for a NaN: a NaN stays a NaN (fminf / fmaxf would return the bound).
+__global__ void clamp_kernel(float* __restrict__ x, long n, float lo, float hi) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float v = x[i];
+  x[i] = v < lo ? lo : (v > hi ? hi : v);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -421,6 +550,89 @@ extern "C" int cxrk_multipos_grad_inplace(float* S, long ld, int rows, int cols,
     hipLaunchKernelGGL(multipos_grad_kernel<true>, grid, dim3(256), 0, stream, S, ld, cols, keys_row, keys_col, n_row, lse_row, lse_col);
   else
     hipLaunchKernelGGL(multipos_grad_kernel<false>, grid, dim3(256), 0, stream, S, ld, cols, keys_row, keys_col, n_row, lse_row, lse_col);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+// learnable temperature: one templated pair of kernels serves the plain (KEYED = false) and the keyed entry points
+template <bool KEYED>
+static int scaled_row_stats(const float* C, long ld, int rows, int cols, int diag_off, const long long* keys_row,
+                            const long long* keys_col, const float* log_scale, float* lse, float* posmean, float* npos,
+                            float* loss_out, float loss_scale, int loss_accumulate, hipStream_t stream) {
+  if (ld % 4 == 0 && aligned16(C))
+    hipLaunchKernelGGL((scaled_row_stats_kernel<true, KEYED>), dim3(rows), dim3(256), 0, stream, C, ld, cols, diag_off, keys_row,
+                       keys_col, log_scale, lse, posmean, npos);
+  else
+    hipLaunchKernelGGL((scaled_row_stats_kernel<false, KEYED>), dim3(rows), dim3(256), 0, stream, C, ld, cols, diag_off, keys_row,
+                       keys_col, log_scale, lse, posmean, npos);
+  CXRK_LAUNCH_CHECK();
+  if (loss_out) {   // sum_i (lse[i] - posmean[i]) * scale, one block, fixed order
+    hipLaunchKernelGGL(lse_loss_kernel, dim3(1), dim3(256), 0, stream, lse, posmean, rows, loss_scale, loss_out, loss_accumulate);
+    CXRK_LAUNCH_CHECK();
+  }
+  return CXRK_OK;
+}
+
+template <bool KEYED>
+static int scaled_grad(float* C, long ld, int rows, int cols, int diag_off, const long long* keys_row, const long long* keys_col,
+                       const float* n_row, const float* lse_row, const float* lse_col, const float* log_scale, float* partials,
+                       hipStream_t stream) {
+  const dim3 grid(rows, (unsigned)((cols + 1023) / 1024));
+  if (ld % 4 == 0 && aligned16(C) && aligned16(lse_col))
+    hipLaunchKernelGGL((scaled_grad_kernel<true, KEYED>), grid, dim3(256), 0, stream, C, ld, cols, diag_off, keys_row, keys_col, n_row,
+                       lse_row, lse_col, log_scale, partials);
+  else
+    hipLaunchKernelGGL((scaled_grad_kernel<false, KEYED>), grid, dim3(256), 0, stream, C, ld, cols, diag_off, keys_row, keys_col, n_row,
+                       lse_row, lse_col, log_scale, partials);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_infonce_row_lse_scaled(const float* C, long ld, int rows, int cols, int diag_off, const float* log_scale,
+                                           float* lse, float* diag, float* loss_out, float loss_scale, int loss_accumulate,
+                                           hipStream_t stream) {
+  CXRK_CHECK_ARG(C && log_scale && lse && diag && rows > 0 && cols > 0 && ld >= cols && diag_off >= 0 && diag_off + rows <= cols);
+  return scaled_row_stats<false>(C, ld, rows, cols, diag_off, nullptr, nullptr, log_scale, lse, diag, nullptr, loss_out, loss_scale,
+                                 loss_accumulate, stream);
+}
+
+extern "C" int cxrk_infonce_grad_scaled_inplace(float* C, long ld, int rows, int cols, int diag_off, const float* lse_row,
+                                                const float* lse_col, const float* log_scale, float* partials, hipStream_t stream) {
+  CXRK_CHECK_ARG(C && lse_row && lse_col && log_scale && partials && rows > 0 && cols > 0 && ld >= cols && diag_off >= 0 &&
+                 diag_off + rows <= cols);
+  return scaled_grad<false>(C, ld, rows, cols, diag_off, nullptr, nullptr, nullptr, lse_row, lse_col, log_scale, partials, stream);
+}
+
+extern "C" int cxrk_multipos_row_stats_scaled(const float* C, long ld, int rows, int cols, const long long* keys_row,
+                                              const long long* keys_col, const float* log_scale, float* lse, float* posmean,
+                                              float* npos, float* loss_out, float loss_scale, int loss_accumulate,
+                                              hipStream_t stream) {
+  CXRK_CHECK_ARG(C && keys_row && keys_col && log_scale && lse && posmean && npos && rows > 0 && cols > 0 && ld >= cols);
+  return scaled_row_stats<true>(C, ld, rows, cols, 0, keys_row, keys_col, log_scale, lse, posmean, npos, loss_out, loss_scale,
+                                loss_accumulate, stream);
+}
+
+extern "C" int cxrk_multipos_grad_scaled_inplace(float* C, long ld, int rows, int cols, const long long* keys_row,
+                                                 const long long* keys_col, const float* n_row, const float* lse_row,
+                                                 const float* lse_col, const float* log_scale, float* partials,
+                                                 hipStream_t stream) {
+  CXRK_CHECK_ARG(C && keys_row && keys_col && n_row && lse_row && lse_col && log_scale && partials && rows > 0 && cols > 0 &&
+                 ld >= cols);
+  return scaled_grad<true>(C, ld, rows, cols, 0, keys_row, keys_col, n_row, lse_row, lse_col, log_scale, partials, stream);
+}
+
+extern "C" int cxrk_logit_scale_grad(const float* partials1, long n1, const float* partials2, long n2, const float* upstream,
+                                     float scale, float* dtheta, int accumulate, hipStream_t stream) {
+  CXRK_CHECK_ARG(partials1 && n1 > 0 && n2 >= 0 && (partials2 || n2 == 0) && upstream && dtheta);
+  hipLaunchKernelGGL(logit_scale_grad_kernel, dim3(1), dim3(256), 0, stream, partials1, n1, partials2, n2, upstream, scale, dtheta,
+                     accumulate);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_clamp_inplace(float* x, long n, float lo, float hi, hipStream_t stream) {
+  CXRK_CHECK_ARG(x && n > 0 && lo <= hi);   // (a NaN bound fails lo <= hi)
+  hipLaunchKernelGGL(clamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, x, n, lo, hi);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }

@@ -120,7 +120,8 @@ def _setup(args, kind):
         im, engine = _joint_models(args, device)
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine,
                              joint_encoders={"image_model": im, "temperature": args.temperature,
-                                             "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None))})
+                                             "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None)),
+                                             "learn_temperature": bool(getattr(args, "learn_temperature", False))})
     else:
         from .health_multimodal.text import get_cxr_bert_inference
         engine = get_cxr_bert_inference(args.pretrained_text, device="cuda")
@@ -235,6 +236,9 @@ def make_parser():
     ap.add_argument("--positives", default="pair", choices=["pair", "labels", "text"],
                     help="--joint: the positives of a pair in the InfoNCE loss: only itself (pair, default), every pair of the global "
                          "batch with the same label vector (labels) or the same prompt text (text)")
+    ap.add_argument("--learn-temperature", action="store_true",
+                    help="--joint: learn the InfoNCE temperature (logit scale log(1/tau), initialised from --temperature, clamped to "
+                         "[0, ln 100] after every step); default: the temperature is fixed")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -247,6 +251,9 @@ def main(argv=None):
     if args.positives != "pair" and not args.joint:
         raise SystemExit("--positives selects the targets of the north-star InfoNCE step and needs --joint (the adapter schedules "
                          "use the labels through the pos-neg BCE loss)")
+    if args.learn_temperature and not args.joint:
+        raise SystemExit("--learn-temperature makes the temperature of the north-star InfoNCE step a parameter and needs --joint (the "
+                         "adapter schedules have no temperature)")
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)
     if int(os.environ.get("RANK", "0")) == 0:

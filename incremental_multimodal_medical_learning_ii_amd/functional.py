@@ -14,6 +14,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import kernels as K
+from .gradsink import GradSink
 
 
 class _L2Norm(torch.autograd.Function):
@@ -223,10 +224,20 @@ class _InfoNCE(torch.autograd.Function):
     local slice, the column keys the gathered vector, and n_i comes from the stats kernel (it counts against the global columns).
     Because a key belongs to a PAIR, entry (i, j) matches exactly when (j, i) does, so the column count of a matching entry equals
     its row count (n_j = n_i): the column term needs no exchange of counts.  With all keys distinct this is the plain loss.
+
+    With `log_scale` (theta = log(1/tau), a one-element fp32 device tensor, differentiable) the temperature is LEARNED
+    (DESIGN.md §5.3): `temperature` is ignored, the logits GEMMs run with alpha = 1 and the *_scaled kernels form
+    S = exp(theta) * C on the device, so nothing on the host depends on theta and nothing is read back.
+        dL/dtheta = sum_ij dL/dS_ij * S_ij = 1/(2 Bg) sum_ij G_ij S_ij,
+    for the plain and the keyed loss alike.  The gradient kernels leave exp(theta) * G in the block (the backward GEMMs keep the
+    host alpha 0.5/Bg) and the partial sums of G o S; one single-block kernel folds them, times the upstream scalar, into
+    theta's gradient.  Data-parallel: a rank's S1 block carries the complete G of its image rows, its S2 block the transpose's,
+    so each rank adds (sum_S1 + sum_S2) G o S / (4 Bg) and the sum all-reduce of the flat gradient buffer completes it: no new
+    collective.
     """
 
     @staticmethod
-    def forward(ctx, img, txt, temperature, group, keys=None):
+    def forward(ctx, img, txt, temperature, group, keys=None, log_scale=None):
         import torch.distributed as dist
         dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         img, txt = img.detach().contiguous(), txt.detach().contiguous()
@@ -248,6 +259,16 @@ class _InfoNCE(torch.autograd.Function):
             if keys.device != img.device:
                 raise ValueError(f"infonce_loss: keys are on {keys.device} but the embeddings on {img.device}")
             keys = keys.detach().contiguous()
+        theta = None
+        if log_scale is not None:
+            # and again: a bad `log_scale` fails on this rank before any collective is issued
+            if not isinstance(log_scale, torch.Tensor) or log_scale.dtype != torch.float32:
+                raise ValueError(f"infonce_loss: log_scale must be an fp32 tensor, got {getattr(log_scale, 'dtype', type(log_scale).__name__)}")
+            if log_scale.numel() != 1 or log_scale.dim() > 1:
+                raise ValueError(f"infonce_loss: log_scale must be 0-d or have shape (1,), got {tuple(log_scale.shape)}")
+            if log_scale.device != img.device:
+                raise ValueError(f"infonce_loss: log_scale is on {log_scale.device} but the embeddings on {img.device}")
+            theta = log_scale.detach()
         if dist_on:
             # image and text halves of ONE [B, 2D] send buffer, written in place by the normalisation kernels; the gathered
             # [Bg, 2D] buffer is read by the GEMMs through its column halves (row stride 2D): no cat / contiguous copies
@@ -266,13 +287,20 @@ class _InfoNCE(torch.autograd.Function):
             keys_all = keys
         Bg = B * world
         off = rank * B
-        inv_tau = 1.0 / float(temperature)
+        inv_tau = 1.0 if theta is not None else 1.0 / float(temperature)    # learnable: the kernels scale by exp(theta)
         S1 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local images x all texts
         S2 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local texts  x all images
         K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=inv_tau)
         K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=inv_tau)
         loss = torch.zeros((), dtype=torch.float32, device=img.device)
-        if keys is None:
+        if theta is not None and keys is None:
+            lse1, _ = K.infonce_row_lse_scaled(S1, off, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+            lse2, _ = K.infonce_row_lse_scaled(S2, off, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+            npos = None
+        elif theta is not None:
+            lse1, _, npos = K.multipos_row_stats_scaled(S1, keys, keys_all, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+            lse2, _, _ = K.multipos_row_stats_scaled(S2, keys, keys_all, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+        elif keys is None:
             lse1, _ = K.infonce_row_lse(S1, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
             lse2, _ = K.infonce_row_lse(S2, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
             npos = None
@@ -284,18 +312,29 @@ class _InfoNCE(torch.autograd.Function):
             lse1_all, lse2_all = _all_gather_rows(lse1, group), _all_gather_rows(lse2, group)   # [Bg] each (4 KiB per rank)
         else:
             lse1_all, lse2_all = lse1, lse2
-        ctx.save_for_backward(S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm)
+        # theta is saved as the parameter itself, not a copy: the backward reads it again and writes into its `.grad`, and autograd's
+        # version check refuses a theta that was updated in place between forward and backward
+        ctx.save_for_backward(S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm, log_scale)
         ctx.meta = (off, inv_tau, Bg)
         ctx.keys = None if keys is None else (keys, keys_all, npos)   # integer / count tensors: not autograd inputs or outputs
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm = ctx.saved_tensors
+        S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm, log_scale = ctx.saved_tensors
         off, inv_tau, Bg = ctx.meta
         B, D = ih.shape
         # dL/dS_ij = (softmax_row + softmax_col - 2*delta) / (2 Bg); fold 1/tau and the upstream scalar into alpha
-        if ctx.keys is None:
+        parts = None
+        if log_scale is not None and ctx.keys is None:
+            theta = log_scale.detach()
+            parts = (K.infonce_grad_scaled_inplace(S1, off, lse1, lse2_all, theta)[1], K.infonce_grad_scaled_inplace(S2, off, lse2, lse1_all, theta)[1])
+        elif log_scale is not None:
+            theta = log_scale.detach()
+            keys, keys_all, npos = ctx.keys
+            parts = (K.multipos_grad_scaled_inplace(S1, keys, keys_all, npos, lse1, lse2_all, theta)[1],
+                     K.multipos_grad_scaled_inplace(S2, keys, keys_all, npos, lse2, lse1_all, theta)[1])
+        elif ctx.keys is None:
             K.infonce_grad_inplace(S1, off, lse1, lse2_all)
             K.infonce_grad_inplace(S2, off, lse2, lse1_all)
         else:
@@ -310,17 +349,37 @@ class _InfoNCE(torch.autograd.Function):
         di = K.l2norm_bwd(dih, ih, inorm)
         dt = K.l2norm_bwd(dth, th, tnorm)
         g = gloss.reshape(()).contiguous()
-        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None, None
+        dtheta = None
+        if parts is not None and ctx.needs_input_grad[5]:
+            # straight into theta's `.grad` (the flat gradient buffer's slot) when it is a leaf that has one: autograd then adds
+            # nothing.  A non-leaf theta gets a fresh tensor, returned to autograd
+            if log_scale.is_leaf:
+                sink = GradSink([log_scale])
+                dst, accumulate = sink.dst(0)
+                K.logit_scale_grad(parts[0], parts[1], g, 0.25 / Bg, dst, accumulate)
+                dtheta = sink.result()[0]
+            else:
+                dtheta = torch.empty_like(log_scale)
+                K.logit_scale_grad(parts[0], parts[1], g, 0.25 / Bg, dtheta, False)
+        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None, None, dtheta
 
 
 def infonce_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: float = 0.07, group=None,
-                 keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 keys: Optional[torch.Tensor] = None, log_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Symmetric InfoNCE over the global batch (all ranks of `group`, or the default group when initialised).
 
     `keys` (optional): int64 [B] on the embeddings' device, one key per local (image, text) pair; pairs of the global batch with
     equal keys are positives of each other (multi-positive targets, see `_InfoNCE`; `contrastive.keys_from_labels` /
-    `keys_from_tokens` build them).  `keys=None` is the plain loss: one positive per row, the diagonal."""
-    return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys)
+    `keys_from_tokens` build them).  `keys=None` is the plain loss: one positive per row, the diagonal.
+
+    `log_scale` (optional): theta = log(1/tau) as a 0-d or [1] fp32 tensor on the embeddings' device, differentiable (a parameter):
+    the learnable temperature.  When given, `temperature` is ignored and the loss is computed with tau = exp(-theta) read on the
+    device; `log_scale=None` is the fixed-temperature path, unchanged.  A leaf `log_scale` with a `.grad` of its own layout (a
+    parameter of the flat optimiser) has its gradient added there directly; any other gets it through autograd.  It must not be
+    updated in place between forward and backward (autograd's version check raises)."""
+    if log_scale is None:
+        return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys)
+    return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys, log_scale)
 
 
 @torch.no_grad()

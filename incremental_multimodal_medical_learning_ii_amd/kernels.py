@@ -1120,6 +1120,89 @@ def multipos_grad_inplace(S, keys_row, keys_col, n_row, lse_row, lse_col):
     return S
 
 
+def _log_scale(t):
+    _chk(t, "log_scale")
+    if t.numel() != 1 or t.dim() > 1:
+        raise ValueError(f"log_scale must be a 0-d or [1] fp32 tensor, got shape {tuple(t.shape)}")
+    return t
+
+
+def scaled_partials_numel(rows: int, cols: int) -> int:
+    """floats of the `partials` output of the two *_grad_scaled_inplace entry points (include/cxrk.h)"""
+    return rows * ((cols + 1023) // 1024)
+
+
+def infonce_row_lse_scaled(C, diag_off, log_scale, loss_out=None, loss_scale: float = 0.0, loss_accumulate: bool = False):
+    """`infonce_row_lse` on exp(log_scale) * C; log_scale is a device scalar (no host sync)."""
+    lib = _lib.load()
+    rows, cols = C.shape
+    lse = torch.empty(rows, dtype=torch.float32, device=C.device)
+    diag = torch.empty(rows, dtype=torch.float32, device=C.device)
+    check(lib.cxrk_infonce_row_lse_scaled(_p(_chk(C, "infonce.C")), C.stride(0), rows, cols, diag_off, _p(_log_scale(log_scale)), _p(lse),
+                                          _p(diag), _p(loss_out), float(loss_scale), int(loss_accumulate), _stream()),
+          "cxrk_infonce_row_lse_scaled")
+    return lse, diag
+
+
+def infonce_grad_scaled_inplace(C, diag_off, lse_row, lse_col, log_scale):
+    """C <- exp(log_scale) * G in place; returns (C, partials [rows * ceil(cols / 1024)] of sum G * S for `logit_scale_grad`)."""
+    lib = _lib.load()
+    rows, cols = C.shape
+    part = torch.empty(scaled_partials_numel(rows, cols), dtype=torch.float32, device=C.device)
+    check(lib.cxrk_infonce_grad_scaled_inplace(_p(_chk(C, "infonce.C")), C.stride(0), rows, cols, diag_off, _p(lse_row), _p(lse_col),
+                                               _p(_log_scale(log_scale)), _p(part), _stream()),
+          "cxrk_infonce_grad_scaled_inplace")
+    return C, part
+
+
+def multipos_row_stats_scaled(C, keys_row, keys_col, log_scale, loss_out=None, loss_scale: float = 0.0, loss_accumulate: bool = False):
+    """`multipos_row_stats` on exp(log_scale) * C."""
+    lib = _lib.load()
+    rows, cols = C.shape
+    lse = torch.empty(rows, dtype=torch.float32, device=C.device)
+    posmean = torch.empty(rows, dtype=torch.float32, device=C.device)
+    npos = torch.empty(rows, dtype=torch.float32, device=C.device)
+    check(lib.cxrk_multipos_row_stats_scaled(_p(_chk(C, "multipos.C")), C.stride(0), rows, cols, _p(_keys(keys_row, rows, "multipos.keys_row")),
+                                             _p(_keys(keys_col, cols, "multipos.keys_col")), _p(_log_scale(log_scale)), _p(lse), _p(posmean),
+                                             _p(npos), _p(loss_out), float(loss_scale), int(loss_accumulate), _stream()),
+          "cxrk_multipos_row_stats_scaled")
+    return lse, posmean, npos
+
+
+def multipos_grad_scaled_inplace(C, keys_row, keys_col, n_row, lse_row, lse_col, log_scale):
+    """the keyed form of `infonce_grad_scaled_inplace`"""
+    lib = _lib.load()
+    rows, cols = C.shape
+    part = torch.empty(scaled_partials_numel(rows, cols), dtype=torch.float32, device=C.device)
+    check(lib.cxrk_multipos_grad_scaled_inplace(_p(_chk(C, "multipos.C")), C.stride(0), rows, cols, _p(_keys(keys_row, rows, "multipos.keys_row")),
+                                                _p(_keys(keys_col, cols, "multipos.keys_col")), _p(n_row), _p(lse_row), _p(lse_col),
+                                                _p(_log_scale(log_scale)), _p(part), _stream()),
+          "cxrk_multipos_grad_scaled_inplace")
+    return C, part
+
+
+def logit_scale_grad(part1, part2, upstream, scale: float, out, accumulate: bool):
+    """out[0] (+)= upstream * scale * (sum part1 + sum part2); `upstream` a device scalar, `out` a one-element fp32 tensor."""
+    lib = _lib.load()
+    _chk(out, "logit_scale_grad.out")
+    if out.numel() != 1:
+        raise ValueError(f"logit_scale_grad.out must hold one element, got shape {tuple(out.shape)}")
+    check(lib.cxrk_logit_scale_grad(_p(_chk(part1, "logit_scale_grad.part1")), part1.numel(), _p(part2), 0 if part2 is None else part2.numel(),
+                                    _p(_chk(upstream, "logit_scale_grad.upstream")), float(scale), _p(out), int(accumulate), _stream()),
+          "cxrk_logit_scale_grad")
+    return out
+
+
+def clamp_inplace(x, lo: float, hi: float):
+    """x <- min(max(x, lo), hi) in place on a dense tensor; a NaN stays a NaN."""
+    lib = _lib.load()
+    _chk(x, "clamp.x")
+    if not x.is_contiguous():
+        raise ValueError("clamp.x must be contiguous")
+    check(lib.cxrk_clamp_inplace(_p(x), x.numel(), float(lo), float(hi), _stream()), "cxrk_clamp_inplace")
+    return x
+
+
 def pairwise_cosine_fwd(x, y):
     lib = _lib.load()
     x = _chk(x, "cosine.x").contiguous()
