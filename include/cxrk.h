@@ -110,7 +110,8 @@ int cxrk_conv_bn_act_fwd_pl(const void* x, long xplane, const void* w_scaled, lo
                             int W, int C, int Ko, int R, int S, int stride, int pad, int relu, hipStream_t stream);
 /* sums (optional, [C]) = column sums of dx: the BatchNorm beta gradient of the unit that produced relu_src / maskin (dx is
  * that unit's masked output gradient), reduced in the data-gradient epilogue; needs ws of
- * cxrk_conv_bwd_data_colsum_ws_bytes().  Not for 1x1 stride-2 filters. */
+ * cxrk_conv_bwd_data_colsum_ws_bytes().  Not for 1x1 stride-2 filters.  With sums, dx / residual / relu_src must be 16-byte
+ * aligned (CXRK_ERR_ARG otherwise: the column sums exist in the 16-byte epilogue only). */
 size_t cxrk_conv_bwd_data_colsum_ws_bytes(int N, int H, int W, int C, int stride);
 int cxrk_conv_bn_act_bwd_data(const float* dy, const float* w_scaled, const float* residual, const float* relu_src,
                               float* dx, int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad,

@@ -192,7 +192,9 @@ int main(int argc, char** argv) {
     setenv("EPI_VERBOSE", "1", 1);
     return run_case(atoi(argv[1]), atoi(argv[2]), atoi(argv[3]), atoi(argv[2]), false, true, 0, false, true, true);
   }
-  const int shapes[][3] = {{4, 8, 128}, {4, 128, 8}, {16, 2048, 512}, {70, 40, 64}, {8, 128, 128}, {130, 136, 72}, {64, 64, 32}, {300, 72, 40}, {16, 512, 2048}};
+  // the last two: N % 4 != 0, the scalar (per-column) branch of gemm_epilogue64_f32
+  const int shapes[][3] = {{4, 8, 128}, {4, 128, 8}, {16, 2048, 512}, {70, 40, 64}, {8, 128, 128}, {130, 136, 72}, {64, 64, 32}, {300, 72, 40}, {16, 512, 2048},
+                           {70, 63, 64}, {33, 5, 8}};
   for (auto& s : shapes)
     for (int cfg = 0; cfg < 6; ++cfg) {
       const bool bias = cfg == 1 || cfg == 2 || cfg == 4, res = cfg == 2 || cfg == 3 || cfg == 5, inplace = cfg == 5;
@@ -200,9 +202,14 @@ int main(int argc, char** argv) {
       fails += run_case(s[0], s[1], s[2], s[1], bias, res, act, inplace);
       if (cfg == 3) fails += run_case(s[0], s[1], s[2], (long)s[1] * 3 + 8, bias, res, act, false);   // strided output rows
       if (cfg == 0) {
+        fails += run_case(s[0], s[1], s[2], s[1], true, false, 2, false, false, false, true);   // FFN up, fp32 mode (kind 17)
+        if (s[1] % 4 != 0) {   // the fused column sums need 16-byte rows: the launch must be refused (prep_epilogue), not run
+          EpiParams ep{}; ep.C = reinterpret_cast<float*>(16); ep.ldc = s[1]; ep.colsum_part = reinterpret_cast<float*>(16);
+          if (prep_epilogue(ep, s[0], s[1], 1)) { printf("FAIL M=%d N=%d: column sums accepted without 16-byte rows\n", s[0], s[1]); ++fails; }
+          continue;
+        }
         fails += run_case(s[0], s[1], s[2], s[1], false, false, 0, false, true, true);    // conv data gradient, fp32 mode (kind 14)
         fails += run_case(s[0], s[1], s[2], s[1], false, true, 0, false, true, true);     // + identity gradient (kind 15)
-        fails += run_case(s[0], s[1], s[2], s[1], true, false, 2, false, false, false, true);   // FFN up, fp32 mode (kind 17)
         fails += run_case(s[0], s[1], s[2], s[1], false, false, 0, false, false, true);   // generic: plain + column sums
       }
     }

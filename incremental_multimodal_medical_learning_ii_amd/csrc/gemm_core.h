@@ -197,6 +197,8 @@ __device__ __forceinline__ void gemm_epilogue64_f32(f32x16 (&acc)[2][2], const E
           if (ep.nt) { const f32x4 o = {v[0], v[1], v[2], v[3]}; __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(C + row * ep.ldc + col)); }
           else *reinterpret_cast<float4*>(C + row * ep.ldc + col) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
+          // no fused column sums here (bs stays zero, and the partial row below is one float4 store): prep_epilogue refuses
+          // colsum_part without vec, so no launch reaches this branch with it set
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             if (col + q >= N) break;
@@ -493,6 +495,9 @@ static inline bool prep_epilogue(EpiParams& e, int M, int N, int splitk) {
   auto ok8 = [](const void* p_, long ld) { return p_ == nullptr || (aligned16(p_) && (ld % 8) == 0); };
   e.vec = (N % 4 == 0) && ok16(e.C, e.ldc) && ((e.slab_stride % 4) == 0) && ok16(e.R, e.ldr) && ok16(e.aux, e.ldaux) &&
           ok16(e.C2, e.ldc2) && (e.bias == nullptr || aligned16(e.bias));
+  // the fused column sums exist in the 16-byte epilogues only (the scalar branch of gemm_epilogue64_f32 would leave them zero):
+  // reachable through cxrk_conv_bn_act_bwd_data with `sums` and a dx / residual / relu_src that is not 16-byte aligned
+  if (e.colsum_part && !e.vec) return false;
   e.pl = (e.Cp || e.Rp || e.maskin || e.maskout || e.auxmode == 3) ? 1 : 0;
   e.fast = e.vec && (N % 8) == 0 && ok8(e.Cp, e.ldc) && ok8(e.Rp, e.ldr) && (e.cplane % 8) == 0 && (e.rplane % 8) == 0 &&
            (!e.maskout || ((N % 64) == 0 && (e.ldmaskout % 8) == 0 && (((uintptr_t)e.maskout) & 7) == 0));

@@ -15,6 +15,7 @@ pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("precision")]
 from incremental_multimodal_medical_learning_ii_amd import kernels as K  # noqa: E402
 from incremental_multimodal_medical_learning_ii_amd import functional as Fh  # noqa: E402
 from oracle import ref_loss, ref_step  # noqa: E402
+from kernel_refs import attention_reference  # noqa: E402
 
 DEV = "cuda"
 from incremental_multimodal_medical_learning_ii_amd import _lib as _cxr_lib  # noqa: E402
@@ -600,26 +601,15 @@ def test_embed_ln_and_scatter():
                                       (65, True), (100, False), (200, True), (512, True), (96, "empty")])   # > 64: the tiled kernels
 def test_attention_fwd_bwd(L, ragged):
     B, nH, dH = 3, 4, (64 if L != 100 else 32)
-    qkv = rnd(B * L, 3 * nH * dH, scale=0.7).requires_grad_(True)
-    mask = torch.ones(B, L, dtype=torch.int64)
-    if ragged:
-        for i in range(B):
-            mask[i, max(1, L - 3 * i - 2):] = 0
-    if ragged == "empty":
-        mask[1] = 0     # a padding-only row of a sharded batch: HF (additive finfo.min) gives a uniform, finite attention row
-    q, k, v = qkv.view(B, L, 3, nH, dH).permute(2, 0, 3, 1, 4)
-    s = q @ k.transpose(-1, -2) / math.sqrt(dH) + (1.0 - mask[:, None, None, :].float()) * torch.finfo(torch.float32).min
-    ctx = (torch.softmax(s, -1) @ v).transpose(1, 2).reshape(B * L, nH * dH)
-    gc = rnd(B * L, nH * dH, seed=2)
-    ctx.backward(gc)
-    qd = qkv.detach().to(DEV)
+    qkv, mask, gc, ctx, dqkv = attention_reference(B, L, nH, dH, ragged)      # PyTorch-CPU fp32 (tests/kernel_refs.py)
+    qd = qkv.to(DEV)
     cd, probs = K.attn_fwd(qd, mask.to(DEV), B, L, nH, dH)
     close(cd, ctx, what="attn fwd")
     dq = K.attn_bwd(qd, probs, gc.to(DEV), B, L, nH, dH)
-    close(dq, qkv.grad, tol=5e-5, what="attn bwd")
+    close(dq, dqkv, tol=5e-5, what="attn bwd")
     cp, _ = K.attn_fwd(qd, mask.to(DEV), B, L, nH, dH, out_planes=True)
     close(cp.float(), ctx, what="attn fwd -> planes")
-    close(K.attn_bwd(qd, probs, gc.to(DEV), B, L, nH, dH, out_planes=True).float(), qkv.grad, tol=5e-5, what="attn bwd -> planes")
+    close(K.attn_bwd(qd, probs, gc.to(DEV), B, L, nH, dH, out_planes=True).float(), dqkv, tol=5e-5, what="attn bwd -> planes")
 
 
 # ------------------------------------------------------------------------------------------------ heads

@@ -16,6 +16,7 @@ import torch
 import torch.nn.functional as F
 
 import memguard as MG
+from kernel_refs import ln_bwd_ref as _ln_bwd_ref, ln_case as _ln_case      # shared with tests/test_fallback_paths_gpu.py
 
 pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("precision")]
 
@@ -330,18 +331,6 @@ def test_conv_bwd_params(cfg, wide):
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm backward
-def _ln_case(rows, H):
-    xhat = rnd(rows, H, seed=1)
-    xhat = (xhat - xhat.mean(1, keepdim=True)) / xhat.std(1, unbiased=False, keepdim=True)
-    return rnd(rows, H), xhat, 0.5 + rnd(rows, seed=2).abs(), 1 + 0.1 * rnd(H, seed=3), rnd(rows, H, seed=4)
-
-
-def _ln_bwd_ref(dy, xhat, rstd, gamma):
-    gdy = dy * gamma
-    dx = rstd[:, None] * (gdy - gdy.mean(1, keepdim=True) - xhat * (gdy * xhat).mean(1, keepdim=True))
-    return dx, (dy * xhat).sum(0), dy.sum(0)
-
-
 @pytest.mark.parametrize("H", [64, 128, 768])
 @pytest.mark.parametrize("rows", [1, 15, 16, 17, 77, 16400])
 def test_residual_ln_bwd(rows, H):
