@@ -27,15 +27,28 @@ class GradSink:
         self.need = list(need) if need is not None else [True] * len(params)
         self.ret: List[Optional[torch.Tensor]] = [None] * len(params)
 
-    def dst(self, j: int, force_fresh: bool = False, zero: bool = False):
-        """(tensor the kernels write, accumulate flag).  zero: a fresh tensor must start at zero (scatter-add targets)."""
+    def _own_grad(self, j: int) -> Optional[torch.Tensor]:
         p = self.params[j]
         g = getattr(p, "grad", None)
-        if not force_fresh and own_layout(g, p) and dense(g):
+        return g if own_layout(g, p) and dense(g) else None
+
+    def dst(self, j: int, force_fresh: bool = False, zero: bool = False):
+        """(tensor the kernels write, accumulate flag).  zero: a fresh tensor must start at zero (scatter-add targets)."""
+        g = None if force_fresh else self._own_grad(j)
+        if g is not None:
             return g, True
+        p = self.params[j]
         t = torch.zeros_like(p) if zero else torch.empty_like(p)
         self.ret[j] = t
         return t, False
+
+    def dst_group(self, *indices: int, force_fresh: bool = False):
+        """([tensors the kernels write], accumulate flag) for the gradient outputs of ONE launch, which has one accumulate switch:
+        every listed parameter's own `.grad`, or -- as soon as one of them does not qualify -- a fresh tensor for every one."""
+        own = [None if force_fresh else self._own_grad(j) for j in indices]
+        if all(g is not None for g in own):
+            return own, True
+        return [self.dst(j, True)[0] for j in indices], False
 
     def result(self) -> tuple:
         return tuple(g if n else None for g, n in zip(self.ret, self.need))

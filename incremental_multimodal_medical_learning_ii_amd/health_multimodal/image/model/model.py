@@ -158,7 +158,7 @@ class ImageModel(nn.Module):
         self.prepare_()
         params, bufs = self._tensors()
         hook = self.grad_ready_hook if torch.is_grad_enabled() else None
-        meta = (self._specs, self._blocks, len(params), want_patch, hook, momentum)
+        meta = IE.EncodeMeta(self._specs, self._blocks, len(params), want_patch, hook, momentum)
         with torch.set_grad_enabled(torch.is_grad_enabled() and not self.freeze_encoder):
             emb, patch = IE.ImageEncodeFn.apply(x, meta, *params, *bufs)
         if momentum is not None:       # the kernels updated running_mean / running_var in place; the counter is host bookkeeping

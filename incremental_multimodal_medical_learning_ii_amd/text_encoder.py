@@ -241,9 +241,7 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
         g, acc = sink.dst(base + 5)
         K.colsum(dproj, g, accumulate=acc)
         dh2 = _dgrad(dpo, wdo_w, pl)
-        (dgh, a1), (dbh, a2) = sink.dst(base + 2), sink.dst(base + 3)
-        if a1 != a2:
-            (dgh, a1), (dbh, a2) = sink.dst(base + 2, True), sink.dst(base + 3, True)
+        (dgh, dbh), a1 = sink.dst_group(base + 2, base + 3)
         dh1 = K.residual_ln_bwd(dh2, xhat_h, rstd_h, p[base + 2], dgh, dbh, accumulate=a1)
         dh1p = K.gelu_bwd(dh1, h1_pre)
         dh1o = op(dh1p)
@@ -266,9 +264,7 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
         def ln_bwd(dy, xhat, rstd, gamma, jg, jbias):
             """LayerNorm backward; the bias gradient of the dense layer in front of it (parameter jbias) is the column sum of the
             result and comes out of the same kernel."""
-            (dg, a1), (db, a2) = sink.dst(jg), sink.dst(jg + 1)
-            if a1 != a2:
-                (dg, a1), (db, a2) = sink.dst(jg, True), sink.dst(jg + 1, True)
+            (dg, db), a1 = sink.dst_group(jg, jg + 1)
             bg, bacc = sink.dst(jbias)
             return K.residual_ln_bwd(dy, xhat, rstd, gamma, dg, db, accumulate=a1, out_planes=pl, dxsum=bg, dxsum_accumulate=bacc)
 
@@ -278,9 +274,7 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
             if d is None:
                 g = ln_bwd(dy, xhat, rstd, gamma, jg, jbias)
                 return g, g
-            (dg, a1), (db, a2) = sink.dst(jg), sink.dst(jg + 1)
-            if a1 != a2:
-                (dg, a1), (db, a2) = sink.dst(jg, True), sink.dst(jg + 1, True)
+            (dg, db), a1 = sink.dst_group(jg, jg + 1)
             bg, bacc = sink.dst(jbias)
             return K.residual_ln_bwd_drop(dy, xhat, rstd, gamma, dg, db, d, rps, accumulate=a1, out_planes=pl, dxsum=bg,
                                           dxsum_accumulate=bacc)
@@ -338,9 +332,7 @@ def _backward(p: Sequence[torch.Tensor], ids: torch.Tensor, n_layers: int, n_hea
             dx = _dgrad(dqkv, wqkv_w, pl, residual=dsum1)
         saved[i] = None  # free this layer's activations early
 
-    (deg, a1), (deb, a2) = sink.dst(3), sink.dst(4)
-    if a1 != a2:
-        (deg, a1), (deb, a2) = sink.dst(3, True), sink.dst(4, True)
+    (deg, deb), a1 = sink.dst_group(3, 4)
     d_emb = _site(drop, 0, K.DROP_EMBED)
     if d_emb is None:
         demb = K.residual_ln_bwd(dx, xhat0, rstd0, eg, deg, deb, accumulate=a1)

@@ -184,3 +184,55 @@ def test_gradient_span_of_a_parameter_subset():
     assert opt.grad_span([]) is None
     lo, hi = opt.grad_span(txt)
     assert hi == opt.flat_g.numel() and all(lo <= (p.grad.data_ptr() - opt.flat_g.data_ptr()) // 4 < hi for p in txt)
+
+
+def _old_two_step_idiom(sink, idx, force_fresh=False):
+    """The idiom `GradSink.dst_group` replaced, written out: ask for every destination, and when the accumulate flags disagree ask
+    again for fresh tensors everywhere."""
+    got = [sink.dst(j, force_fresh) for j in idx]
+    if len({acc for _, acc in got}) > 1:
+        got = [sink.dst(j, True) for j in idx]
+    return [t for t, _ in got], got[0][1]
+
+
+@pytest.mark.parametrize("case", ["all_own", "missing", "wrong_dtype", "non_dense", "force_fresh"])
+def test_gradsink_dst_group_is_all_in_place_or_all_fresh(case):
+    from incremental_multimodal_medical_learning_ii_amd.gradsink import GradSink
+
+    def make():
+        ps = [torch.zeros(4, 6, 1, 1).contiguous(memory_format=torch.channels_last).requires_grad_(True),
+              torch.zeros(6, requires_grad=True), torch.zeros(3, 5, requires_grad=True)]
+        for p in ps:
+            p.grad = torch.zeros_like(p)
+        if case == "missing":
+            ps[1].grad = None
+        elif case == "wrong_dtype":
+            ps[1].grad_dtype = None       # let the parameter carry a gradient of another dtype
+            ps[1].grad = torch.zeros(6, dtype=torch.float64)
+        elif case == "non_dense":     # a strided view: right shape and dtype, but its elements do not occupy one gap-free block
+            ps[2].grad = torch.zeros(3, 10)[:, ::2]
+            assert ps[2].grad.shape == ps[2].shape and not ps[2].grad.is_contiguous()
+        return ps
+
+    force = case == "force_fresh"
+    ps = make()
+    sink = GradSink(ps)
+    tensors, acc = sink.dst_group(0, 1, 2, force_fresh=force)
+    assert len(tensors) == 3
+    if case == "all_own":
+        assert acc is True and sink.ret == [None, None, None]
+        assert all(t.data_ptr() == p.grad.data_ptr() and t is p.grad for t, p in zip(tensors, ps))
+    else:
+        assert acc is False
+        for t, p, r in zip(tensors, ps, sink.ret):
+            assert r is t                                                   # every slot is returned to autograd ...
+            assert p.grad is None or t.data_ptr() != p.grad.data_ptr()      # ... as a fresh tensor, also where a .grad qualified
+            assert t.shape == p.shape and t.stride() == p.stride() and t.dtype == torch.float32
+    # the idiom written out gives the same (is param.grad?, accumulate, ret filled?) outcome on the same inputs
+    ps2 = make()
+    sink2 = GradSink(ps2)
+    exp_t, exp_acc = _old_two_step_idiom(sink2, (0, 1, 2), force)
+    assert acc == exp_acc
+    assert [t is p.grad for t, p in zip(tensors, ps)] == [t is p.grad for t, p in zip(exp_t, ps2)]
+    assert [r is not None for r in sink.ret] == [r is not None for r in sink2.ret]
+    assert all(r is None or r is t for r, t in zip(sink2.ret, exp_t))

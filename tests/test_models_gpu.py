@@ -169,6 +169,59 @@ def test_image_model_forward_backward(golden_dir):
     assert not model(x.to(DEV)).requires_grad
 
 
+PATCH_PX = 64      # 2 images of 64 x 64: the head sees 2 x 2 patches, the smallest size at which the spatial mean and its `add=` form
+#                    are not trivial
+
+
+def test_image_patch_cotangent_through_the_backward():
+    """`ImageModel._run(want_patch=True)` with gradients enabled: cotangents on the embedding only (the yardstick: code the test
+    above covers), on the projected patch output only, and on both, through the hand-written backward.  Reference: the CPU oracle's
+    trunk + projector under the captured decisions (patch tensor; the embedding is its mean).  The first two cases run with `.grad`
+    unset (fresh tensors go back to autograd), the third with every `.grad` preset to zeros of the parameter's own layout (the
+    kernels accumulate in place): both `GradSink` outcomes on the real backward."""
+    from incremental_multimodal_medical_learning_ii_amd import image_encoder as IE
+    from oracle import ref_image
+    model = get_biovil_resnet(None)
+    syn.fill_module_(model)
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()}
+    model.to(DEV).eval()
+    x = syn.synthetic_images(2, PATCH_PX, seed=29)
+    gen = torch.Generator().manual_seed(30)
+    P = PATCH_PX // 32
+    probe_e, probe_p = torch.randn(2, 128, generator=gen), torch.randn(2, P, P, 128, generator=gen)
+    named = {k: v for k, v in model.named_parameters() if ".fc." not in k}
+    ref = None
+    for case in ("emb", "patch", "both"):
+        for v in named.values():
+            v.grad = torch.zeros_like(v) if case == "both" else None
+        with IE.capture_relu_decisions() as cap:
+            emb, patch = model._run(x.to(DEV), want_patch=True)
+        assert emb.shape == (2, 128) and patch.shape == (2, P, P, 128)
+        if ref is None:     # the oracle's graph, built once under the decisions of the first pass (every later pass must repeat them)
+            p = {k: v.detach().clone().requires_grad_(k in named) for k, v in sd_cpu.items()}
+            pol = ref_image.ReluPolicy(cap[0])
+            patch_ref = ref_image.projector(p, ref_image.resnet50_trunk(p, x, relu=pol), relu=pol).permute(0, 2, 3, 1)
+            ref = (cap[0], p, pol, patch_ref, patch_ref.mean(dim=(1, 2)))
+        masks, p, pol, patch_ref, emb_ref = ref
+        assert len(cap[0]) == len(masks) and all(torch.equal(a, b) for a, b in zip(cap[0], masks))
+        assert torch.equal(cap[0].pool_taps, masks.pool_taps)
+        assert pol.flips <= _flip_budget()[0] and pol.max_flip_rel < _flip_budget()[1], (pol.flips, pol.max_flip_rel)
+        assert pol.pool_flips <= _flip_budget()[0] // 100 + 2 and pol.pool_max_gap < _flip_budget()[1], (pol.pool_flips, pol.pool_max_gap)
+        assert rel(emb, emb_ref) < TOL and rel(patch, patch_ref) < TOL, (rel(emb, emb_ref), rel(patch, patch_ref))
+
+        def loss(e, q):
+            return ((e * probe_e.to(e.device)).sum() if case != "patch" else 0) + ((q * probe_p.to(q.device)).sum() if case != "emb" else 0)
+        loss(emb, patch).backward()
+        keys = list(named)
+        gref = dict(zip(keys, torch.autograd.grad(loss(emb_ref, patch_ref), [p[k] for k in keys], retain_graph=True)))
+        worst = max(((rel(named[k].grad, gref[k]), k) for k in keys), key=lambda t: t[0])
+        print(f"patch cotangent [{_cxr_lib.get_precision()}, {PATCH_PX} px, {case}]: worst gradient error {worst[0]:.3e} ({worst[1]}), "
+              f"flips {pol.flips} / {pol.count}, pool flips {pol.pool_flips}")
+        assert worst[0] < TOL, (case, worst)
+    for v in named.values():
+        v.grad = None
+
+
 def test_batchnorm_calibration_matches_a_train_mode_pass(monkeypatch):
     """`ImageModel.calibrate_batchnorm_` (synthetic-weight set-up of bench.py): after the call every BatchNorm's running statistics
     are the statistics of its own input over the batch — batch mean and unbiased batch variance, the values a train-mode
