@@ -16,7 +16,15 @@
  *     -4 unsupported shape.  The Python wrappers raise RuntimeError/ValueError for these, mirroring the
  *     reference's exception behaviour;
  *   - row-major tensors; activations of the image encoder are NHWC, filters are [Ko][R][S][C] (= a torch OIHW
- *     tensor in channels_last memory format).
+ *     tensor in channels_last memory format);
+ *   - non-finite values propagate as in the torch operation the entry point cites (float64 CPU reference, autograd for the
+ *     backwards): an output element that is NaN there is non-finite here, and one that is finite there is finite here (a NaN does
+ *     not leak into other rows / channels / segments / images).  ReLU, max-pool, the L2-norm clamp, the cosine maximum and the
+ *     weight_reset threshold keep a NaN (comparisons, never fmaxf / fminf on the value itself); the ReLU decision bit of a NaN
+ *     output is 0; masks select (a NaN gradient at a ReLU-off position gives 0).  For +Inf only "non-finite there => non-finite
+ *     here" holds: planes storage turns Inf into NaN (lo = Inf - Inf).  Where the reference multiplies by an exact zero (masked
+ *     keys, dropped elements) the result may be 0 or NaN.  Backward entry points are specified for a non-finite incoming gradient
+ *     with finite saved state.
  */
 #ifndef CXRK_H
 #define CXRK_H

@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const void* __restrict__ 
     unsigned bits = 0;
     if (relu) {
 #pragma unroll
-      for (int q = 0; q < 8; ++q) { bits |= (v[q] > 0.f ? 1u : 0u) << q; v[q] = fmaxf(v[q], 0.f); }
+      for (int q = 0; q < 8; ++q) { bits |= (v[q] > 0.f ? 1u : 0u) << q; v[q] = relu_keep_nan(v[q]); }
     }
     st8(y, yplane, t * 8, v);
     if (mask) mask[t] = (unsigned char)bits;

@@ -50,7 +50,8 @@ __global__ void nhwc_to_nchw_kernel(const float* __restrict__ x, float* __restri
 }
 
 // 3x3 / stride 2 / pad 1 max-pool, NHWC, 4 channels per thread.  idx = winning tap (first maximum in scan order,
-// as torch's max_pool2d backward routes the gradient).
+// as torch's max_pool2d backward routes the gradient).  A NaN tap wins wherever it sits in the window (torch: `val > max || isnan(val)`),
+// in the planes kernel below too.
 __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, unsigned char* __restrict__ idx,
                                    int N, int H, int W, int C, int Ho, int Wo) {
   const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -70,10 +71,10 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ x, float* __restric
       if ((unsigned)wi >= (unsigned)W) continue;
       const float4 v = *reinterpret_cast<const float4*>(x + ((n * H + hi) * W + wi) * C + c4 * 4);
       const unsigned char tap = (unsigned char)(r * 3 + s);
-      if (first || v.x > best.x) { best.x = v.x; bi.x = tap; }
-      if (first || v.y > best.y) { best.y = v.y; bi.y = tap; }
-      if (first || v.z > best.z) { best.z = v.z; bi.z = tap; }
-      if (first || v.w > best.w) { best.w = v.w; bi.w = tap; }
+      if (first || v.x > best.x || v.x != v.x) { best.x = v.x; bi.x = tap; }
+      if (first || v.y > best.y || v.y != v.y) { best.y = v.y; bi.y = tap; }
+      if (first || v.z > best.z || v.z != v.z) { best.z = v.z; bi.z = tap; }
+      if (first || v.w > best.w || v.w != v.w) { best.w = v.w; bi.w = tap; }
       first = false;
     }
   }
@@ -154,7 +155,7 @@ __global__ void maxpool_fwd_pl_kernel(const unsigned short* __restrict__ x, long
       float v[8]; planes_load8(x, xplane, ((n * H + hi) * W + wi) * C + c8 * 8, v);
       const unsigned char tap = (unsigned char)(r * 3 + s);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) if (first || v[q] > best[q]) { best[q] = v[q]; bi[q] = tap; }
+      for (int q = 0; q < 8; ++q) if (first || v[q] > best[q] || v[q] != v[q]) { best[q] = v[q]; bi[q] = tap; }
       first = false;
     }
   }

@@ -96,6 +96,14 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
   return fmaf(x * 0.39894228040143267794f, g.e, g.phi);
 }
 
+// ReLU as torch.relu computes it: a NaN stays a NaN (fmaxf(NaN, 0) is 0, which would hide a diverged activation from every
+// later layer and from the loss); -0 and every negative value give +0 as fmaxf did.  The decision bit beside it stays `v > 0`.
+__device__ __forceinline__ float relu_keep_nan(float v) { return v <= 0.f ? 0.f : v; }
+
+// NaN-propagating minimum / maximum (torch.min / torch.max): fminf / fmaxf return the other operand.
+__device__ __forceinline__ float min_keep_nan(float a, float b) { return (a != a || a < b) ? a : b; }
+__device__ __forceinline__ float max_keep_nan(float a, float b) { return (a != a || a > b) ? a : b; }
+
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 // ---- split-bf16 ("planes") storage -----------------------------------------------------------------------------------

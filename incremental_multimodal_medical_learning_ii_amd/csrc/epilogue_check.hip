@@ -1,6 +1,8 @@
 // Stand-alone check of the epilogue lane maps (gemm_epilogue.h) on small / ragged shapes, with guard regions around every
 // buffer: a store that leaves its tensor lands in a guard and is REPORTED instead of faulting.  Exact-fp32 mainloop, CPU fp64
 // reference.   Built by the Makefile next to the library (`epilogue_check`); `epilogue_check M N K` runs one shape verbosely.
+// `poison`: bias[N / 2] is NaN, so column N / 2 must come out NaN through the ReLU (torch.relu keeps a NaN; fmaxf(NaN, 0) is 0), with
+// decision bit 0, and no other column may change.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -24,13 +26,16 @@ struct Buf {
   }
   float* ptr() const { return d + GUARD; }
   const float* host() const { return h.data() + GUARD; }
+  void poke(size_t i, float v) { h[GUARD + i] = v; (void)hipMemcpy(d + GUARD + i, &v, 4, hipMemcpyHostToDevice); }
   std::vector<float> back() const { std::vector<float> o(n + 2 * GUARD); (void)hipMemcpy(o.data(), d, o.size() * 4, hipMemcpyDeviceToHost); return o; }
 };
 
-static int run_case(int M, int N, int K, long ldc, bool bias, bool res, int act, bool inplace, bool auxsign = false, bool colsum = false, bool c2 = false) {
+static int run_case(int M, int N, int K, long ldc, bool bias, bool res, int act, bool inplace, bool auxsign = false, bool colsum = false, bool c2 = false,
+                    bool poison = false) {
   Buf A, B, C, R, Bi;
   A.alloc((size_t)M * K, true, 1); B.alloc((size_t)N * K, true, 2); C.alloc((size_t)M * ldc, false, 3);
   R.alloc((size_t)M * ldc, true, 4); Bi.alloc((size_t)N, true, 5);
+  if (poison) Bi.poke((size_t)N / 2, NAN);
   if (inplace) (void)hipMemcpy(C.ptr(), R.host(), (size_t)M * ldc * 4, hipMemcpyHostToDevice);
   EpiParams ep{}; ep.C = C.ptr(); ep.ldc = ldc; ep.alpha = 0.5f; ep.act = act;
   if (bias) ep.bias = Bi.ptr();
@@ -61,10 +66,11 @@ static int run_case(int M, int N, int K, long ldc, bool bias, bool res, int act,
       for (int k = 0; k < K; ++k) s += (double)A.host()[(size_t)i * K + k] * B.host()[(size_t)j * K + k];
       s = 0.5 * s + (bias ? Bi.host()[j] : 0.0) + (res ? R.host()[(size_t)i * ldc + j] : 0.0);
       if (c2) { const double d2 = fabs(s - out2[GUARD + (size_t)i * ldc + j]); md = fmax(md, d2); if (!(d2 < 1e-3)) ++bad; }
-      if (act == 1) s = s > 0 ? s : 0;
+      if (act == 1) s = s <= 0 ? 0 : s;   // a NaN stays
       if (act == 2) s = 0.5 * s * (1.0 + erf(s * 0.7071067811865476));
       if (auxsign) s = AX.host()[(size_t)i * ldc + j] > 0.f ? s : 0.0;
       cs[j] += s;
+      if (s != s) { if (got == got) ++bad; continue; }   // expected NaN: the output must be NaN
       const double d = fabs(s - got); md = fmax(md, d);
       if (!(d < 1e-3)) { if (bad < 12 && getenv("EPI_VERBOSE")) printf("    wrong C[%d][%ld] = %g, expected %g\n", i, j, got, s); ++bad; }
     }
@@ -82,8 +88,8 @@ static int run_case(int M, int N, int K, long ldc, bool bias, bool res, int act,
     }
   auto chk = [&](const Buf& b, const char* nm) { const std::vector<float> o = b.back(); size_t hits = 0; for (size_t i = 0; i < o.size(); ++i) hits += memcmp(&o[i], &b.h[i], 4) != 0; if (hits) printf("  INPUT %s modified in %zu places\n", nm, hits); return hits; };
   size_t in_hits = chk(A, "A") + chk(B, "B") + chk(Bi, "bias") + (inplace ? 0 : chk(R, "R"));
-  printf("%s M=%d N=%d K=%d ldc=%ld bias=%d res=%d(inplace %d) act=%d: max err %.2e, wrong %d, stray writes %zu\n",
-         (bad || guard_hits || in_hits) ? "FAIL" : "ok  ", M, N, K, ldc, bias, res, inplace, act, md, bad, guard_hits + in_hits);
+  printf("%s M=%d N=%d K=%d ldc=%ld bias=%d res=%d(inplace %d) act=%d%s: max err %.2e, wrong %d, stray writes %zu\n",
+         (bad || guard_hits || in_hits) ? "FAIL" : "ok  ", M, N, K, ldc, bias, res, inplace, act, poison ? " NaN bias" : "", md, bad, guard_hits + in_hits);
   (void)hipFree(A.d); (void)hipFree(B.d); (void)hipFree(C.d); (void)hipFree(R.d); (void)hipFree(Bi.d); (void)hipFree(AX.d); (void)hipFree(CS.d); (void)hipFree(C2.d);
   return (bad || guard_hits || in_hits) ? 1 : 0;
 }
@@ -119,10 +125,12 @@ struct PBuf {   // a [2][n] bf16 planes tensor with guards around the whole allo
 };
 
 // out = act(0.5 * A B^T + bias + res) [* mask bits]; planes or fp32 output; optional ReLU decision bits out, column sums
-static int run_planes_case(int M, int N, int K, bool outpl, bool bias, bool respl, int act, bool maskin, bool maskout, bool colsum) {
+static int run_planes_case(int M, int N, int K, bool outpl, bool bias, bool respl, int act, bool maskin, bool maskout, bool colsum,
+                           bool poison = false) {
   PBuf A, B, Cp, R; Buf C, Bi, CS;
   A.alloc((size_t)M * K, true, 11); B.alloc((size_t)N * K, true, 12); Cp.alloc((size_t)M * N, false, 13); R.alloc((size_t)M * N, true, 14);
   C.alloc((size_t)M * N, false, 15); Bi.alloc((size_t)N, true, 16);
+  if (poison) Bi.poke((size_t)N / 2, NAN);
   const bool wide = M >= 256 && N >= 256;
   const int tm = wide ? 256 : (N <= 64 ? 256 : (M <= 64 ? 64 : 128));
   const int parts = ((M + tm - 1) / tm) * (tm / 64);
@@ -165,10 +173,15 @@ static int run_planes_case(int M, int N, int K, bool outpl, bool bias, bool resp
       for (int k = 0; k < K; ++k) v += (double)A.val[(size_t)i * K + k] * B.val[(size_t)j * K + k];
       v = 0.5 * v + (bias ? Bi.host()[j] : 0.0) + (respl ? R.val[(size_t)i * N + j] : 0.0);
       const bool pos = v > 0;
-      if (act == 1) v = pos ? v : 0;
+      if (act == 1) v = v <= 0 ? 0 : v;   // a NaN stays
       if (maskin && !((hmin[GUARD + (size_t)i * (N / 8) + j / 8] >> (j % 8)) & 1)) v = 0;
       cs[j] += v;
       const double got = outpl ? (double)bf16_f(op[GUARD + (size_t)i * N + j]) + bf16_f(op[GUARD + Cp.plane() + (size_t)i * N + j]) : (double)of[GUARD + (size_t)i * N + j];
+      if (v != v) {   // expected NaN: the output must be NaN and its decision bit 0 (NaN > 0 is false)
+        if (got == got) ++bad;
+        if (maskout && ((omout[GUARD + (size_t)i * (N / 8) + j / 8] >> (j % 8)) & 1)) ++bad;
+        continue;
+      }
       const double d = fabs(got - v); md = fmax(md, d);
       if (!(d < 2e-3)) ++bad;
       if (maskout && fabs(v) > 1e-3 && (((omout[GUARD + (size_t)i * (N / 8) + j / 8] >> (j % 8)) & 1) != (pos ? 1 : 0))) ++bad;
@@ -179,8 +192,8 @@ static int run_planes_case(int M, int N, int K, bool outpl, bool bias, bool resp
       for (int p_ = 0; p_ < parts; ++p_) { const float v = ocs[GUARD + (size_t)p_ * N + j]; if (v != -12345.f) t += v; }
       if (!(fabs(t - cs[j]) < 2e-2)) ++bad;
     }
-  printf("%s planes M=%d N=%d K=%d out=%s bias=%d res_pl=%d act=%d maskin=%d maskout=%d colsum=%d: max err %.2e, wrong %d, stray writes %zu\n",
-         (bad || stray) ? "FAIL" : "ok  ", M, N, K, outpl ? "planes" : "fp32", bias, respl, act, maskin, maskout, colsum, md, bad, stray);
+  printf("%s planes M=%d N=%d K=%d out=%s bias=%d res_pl=%d act=%d maskin=%d maskout=%d colsum=%d%s: max err %.2e, wrong %d, stray writes %zu\n",
+         (bad || stray) ? "FAIL" : "ok  ", M, N, K, outpl ? "planes" : "fp32", bias, respl, act, maskin, maskout, colsum, poison ? " NaN bias" : "", md, bad, stray);
   (void)hipFree(A.d); (void)hipFree(B.d); (void)hipFree(Cp.d); (void)hipFree(R.d); (void)hipFree(C.d); (void)hipFree(Bi.d); (void)hipFree(CS.d);
   (void)hipFree(dmin); (void)hipFree(dmout);
   return (bad || stray) ? 1 : 0;
@@ -201,6 +214,10 @@ int main(int argc, char** argv) {
       const int act = cfg == 4 ? 1 : 0;
       fails += run_case(s[0], s[1], s[2], s[1], bias, res, act, inplace);
       if (cfg == 3) fails += run_case(s[0], s[1], s[2], (long)s[1] * 3 + 8, bias, res, act, false);   // strided output rows
+      if (cfg == 4) {   // the ReLU feature sets with a NaN bias entry: kinds 12 and 13, the generic and the scalar branch
+        fails += run_case(s[0], s[1], s[2], s[1], true, false, 1, false, false, false, false, true);
+        fails += run_case(s[0], s[1], s[2], s[1], true, true, 1, false, false, false, false, true);
+      }
       if (cfg == 0) {
         fails += run_case(s[0], s[1], s[2], s[1], true, false, 2, false, false, false, true);   // FFN up, fp32 mode (kind 17)
         if (s[1] % 4 != 0) {   // the fused column sums need 16-byte rows: the launch must be refused (prep_epilogue), not run
@@ -224,6 +241,9 @@ int main(int argc, char** argv) {
     fails += run_planes_case(s[0], s[1], s[2], false, false, true, 0, false, false, false);    //  5 fp32 out + planes residual (8-byte loads)
     fails += run_planes_case(s[0], s[1], s[2], false, true, true, 0, false, false, false);     //  2 bias + planes residual -> fp32
     fails += run_planes_case(s[0], s[1], s[2], false, false, false, 0, false, false, false);   //  0 plain fp32 from planes operands
+    fails += run_planes_case(s[0], s[1], s[2], true, true, false, 1, false, true, false, true);   //  6 with a NaN bias entry
+    fails += run_planes_case(s[0], s[1], s[2], true, true, true, 1, false, true, false, true);    //  7 with a NaN bias entry
+    fails += run_planes_case(s[0], s[1], s[2], true, true, false, 1, false, false, false, true);  // 19 stem conv + BN + ReLU, NaN bias entry
   }
   printf("%d failing cases\n", fails);
   return fails != 0;

@@ -180,7 +180,7 @@ __device__ __forceinline__ void gemm_epilogue64_f32(f32x16 (&acc)[2][2], const E
           if (ep.C2) *reinterpret_cast<float4*>(ep.C2 + row * ep.ldc2 + col) = make_float4(v[0], v[1], v[2], v[3]);
           if (ep.act == 1) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.f);
+            for (int q = 0; q < 4; ++q) v[q] = relu_keep_nan(v[q]);
           } else if (ep.act == 2) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = gelu_erf(v[q]);
@@ -205,7 +205,7 @@ __device__ __forceinline__ void gemm_epilogue64_f32(f32x16 (&acc)[2][2], const E
             float x = v[q];
             if (ep.R) x += ep.R[row * ep.ldr + col + q];
             if (ep.C2) ep.C2[row * ep.ldc2 + col + q] = x;
-            if (ep.act == 1) x = fmaxf(x, 0.f);
+            if (ep.act == 1) x = relu_keep_nan(x);
             else if (ep.act == 2) x = gelu_erf(x);
             if (ep.auxmode == 1) x = ep.aux[row * ep.ldaux + col + q] > 0.f ? x : 0.f;
             else if (ep.auxmode == 2) x *= gelu_erf_grad(ep.aux[row * ep.ldaux + col + q]);

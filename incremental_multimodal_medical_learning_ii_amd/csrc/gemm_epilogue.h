@@ -250,7 +250,7 @@ __device__ __forceinline__ void epi_rows(f32x16 (*acc)[2][2], const EpiParams& e
       unsigned obits = 0;
       if (relu) {
 #pragma unroll
-        for (int q = 0; q < 8; ++q) { obits |= (v[q] > 0.f ? 1u : 0u) << q; v[q] = fmaxf(v[q], 0.f); }
+        for (int q = 0; q < 8; ++q) { obits |= (v[q] > 0.f ? 1u : 0u) << q; v[q] = relu_keep_nan(v[q]); }
       } else if (gelu) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) v[q] = gelu_erf(v[q]);

@@ -24,11 +24,12 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const float* __restrict
   float v[NV]; float q = 0.f;
 #pragma unroll
   for (int i = 0; i < NV; ++i) { const int c = lane + i * 64; v[i] = c < D ? x[row * D + c] : 0.f; q += v[i] * v[i]; }
-  const float n = sqrtf(wave_sum(q));
-  const float inv = 1.0f / fmaxf(n, eps);
+  const float n_raw = sqrtf(wave_sum(q));
+  const float n = n_raw < eps ? eps : n_raw;   // clamp_min by comparison: a NaN norm stays NaN (fmaxf would return eps), as F.normalize
+  const float inv = 1.0f / n;
 #pragma unroll
   for (int i = 0; i < NV; ++i) { const int c = lane + i * 64; if (c < D) xhat[row * ldh + c] = v[i] * inv; }
-  if (lane == 0 && norm) norm[row] = fmaxf(n, eps);
+  if (lane == 0 && norm) norm[row] = n;
 }
 
 // dx = (dxhat - xhat * <xhat, dxhat>) / norm
@@ -94,7 +95,9 @@ __global__ void lse_loss_kernel(const float* __restrict__ lse, const float* __re
 struct RowAcc {
   float m = -INFINITY, s = 0.f, pos = 0.f; int n = 0;
   __device__ __forceinline__ void rescale(float mx) {   // raise the running maximum to mx >= m
-    if (mx > m) { s *= expf(m - mx); m = mx; }          // (m = -inf: s is 0 and stays 0)
+    // (m = -inf: s is 0 and stays 0.)  A NaN takes the maximum over and stays: a thread whose only elements are NaN would otherwise
+    // keep m = -inf, and the merge below drops the sums of such threads (torch.logsumexp gives NaN for the row).
+    if (mx > m || mx != mx) { s *= expf(m - mx); m = mx; }
   }
   __device__ __forceinline__ void add(float x, bool match) {
     s += expf(x - m);
@@ -120,7 +123,7 @@ __global__ __launch_bounds__(256) void multipos_row_stats_kernel(const float* __
     tail = cols & ~3;
     for (int j = threadIdx.x * 4; j < tail; j += 1024) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(s + j);
-      a.rescale(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+      a.rescale(max_keep_nan(max_keep_nan(v[0], v[1]), max_keep_nan(v[2], v[3])));   // fmaxf would skip a NaN lane: see RowAcc::rescale
 #pragma unroll
       for (int q = 0; q < 4; ++q) a.add(v[q], keys_col[j + q] == kr);
     }
@@ -176,7 +179,7 @@ __global__ __launch_bounds__(256) void multipos_grad_kernel(float* __restrict__ 
 struct ScaledRowAcc {
   float mc = -INFINITY, M = -INFINITY, s = 0.f, pos = 0.f; int n = 0;
   __device__ __forceinline__ void rescale(float c, float sc) {
-    if (c > mc) { const float Mn = sc * c; s *= expf(M - Mn); mc = c; M = Mn; }   // (M = -inf: s is 0 and stays 0)
+    if (c > mc || c != c) { const float Mn = sc * c; s *= expf(M - Mn); mc = c; M = Mn; }   // (M = -inf: s is 0 and stays 0; NaN as in RowAcc)
   }
   __device__ __forceinline__ void add(float c, float sc, bool match) {
     s += expf(fmaf(sc, c, -M));
@@ -205,7 +208,7 @@ __global__ __launch_bounds__(256) void scaled_row_stats_kernel(const float* __re
     tail = cols & ~3;
     for (int j = threadIdx.x * 4; j < tail; j += 1024) {
       const f32x4 v = *reinterpret_cast<const f32x4*>(c + j);
-      a.rescale(fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])), sc);
+      a.rescale(max_keep_nan(max_keep_nan(v[0], v[1]), max_keep_nan(v[2], v[3])), sc);
 #pragma unroll
       for (int q = 0; q < 4; ++q) a.add(v[q], sc, KEYED ? keys_col[j + q] == kr : j + q == dcol);
     }

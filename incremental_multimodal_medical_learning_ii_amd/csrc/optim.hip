@@ -54,24 +54,26 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, l
   }
 }
 
-// stage 1: per-block min/max of |a-b|
+// stage 1: per-block min/max of |a-b|.  A NaN difference makes both NaN, as torch's min() / max() (fminf / fmaxf would skip it):
+// the threshold of stage 2 is then NaN, no element is below it, and nothing is restored (Trainer.myIncremental on the same input).
 __global__ __launch_bounds__(256) void absdiff_minmax_kernel(const float* __restrict__ a, const float* __restrict__ b, long n,
                                                              float* __restrict__ part) {
   __shared__ float sh[16];
   float mn = INFINITY, mx = -INFINITY;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const float d = fabsf(a[i] - b[i]);
-    mn = fminf(mn, d); mx = fmaxf(mx, d);
+    mn = min_keep_nan(mn, d); mx = max_keep_nan(mx, d);
   }
+  const int bad = __syncthreads_or(mn != mn);
   mn = block_min(mn, sh); mx = block_max(mx, sh);
-  if (threadIdx.x == 0) { part[2 * blockIdx.x] = mn; part[2 * blockIdx.x + 1] = mx; }
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = bad ? NAN : mn; part[2 * blockIdx.x + 1] = bad ? NAN : mx; }
 }
 // stage 2: every block re-derives the threshold from the partials, restores, counts.
 __global__ __launch_bounds__(256) void weight_reset_kernel(float* __restrict__ pnew, const float* __restrict__ pold, long n,
                                                            const float* __restrict__ part, int nparts, float threshold,
                                                            unsigned long long* __restrict__ counters) {
   float mn = INFINITY, mx = -INFINITY;
-  for (int i = 0; i < nparts; ++i) { mn = fminf(mn, part[2 * i]); mx = fmaxf(mx, part[2 * i + 1]); }
+  for (int i = 0; i < nparts; ++i) { mn = min_keep_nan(mn, part[2 * i]); mx = max_keep_nan(mx, part[2 * i + 1]); }
   const float to_reset = mn + threshold * (mx - mn);
   unsigned int cnt = 0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {

@@ -46,7 +46,9 @@ def _sentinel_bits(dtype, byte: int) -> int:
 
 
 def poison_fill(t: torch.Tensor, poison: str) -> torch.Tensor:
-    """nan: every element NaN.  alt: +1e30 / -1e30 alternating per element (fmaxf / fminf swallow a NaN, not these)."""
+    """nan: every element NaN.  alt: +1e30 / -1e30 alternating per element: a second poison that no operation can skip.  (The kernels
+    themselves keep a NaN that they read -- ReLU, max-pool, clamps and min / max reductions compare instead of calling fmaxf / fminf,
+    DESIGN.md 3.1; the row maxima of the softmax / log-sum-exp kernels still skip a NaN operand, it then arrives through the exponent.)"""
     if poison == "nan":
         t.fill_(float("nan"))
     elif poison == "alt":
