@@ -149,6 +149,37 @@ int cxrk_conv_bn_act_bwd_params_pl(const void* x, long xplane, const void* dy, l
 int cxrk_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, int Cpad, hipStream_t stream);
 int cxrk_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, hipStream_t stream);
 
+/* ---- augment (train mode, opt-in through ImageModel.augment_call / JointContrastiveTrainer(augment=...)) ----
+ * The same boundary transform with a random affine map (rotation, translation, zoom, horizontal flip; bilinear taps, zero fill)
+ * and a brightness / contrast jitter: the train-time transforms BioViL's image encoder was trained with, which the reference keeps
+ * commented out above `get_bio_vil_pipeline` (DataRetrieval.py).  It takes the place of cxrk_nchw_to_nhwc in front of the stem.
+ * Every random quantity of image n is a pure function of (seed, call counter, n = row_offset + index within the call).  Rule:
+ *   Philox4x32-10 (csrc/dropout.h), key = (seed & 0xffffffff, seed >> 32), two blocks b = 0, 1 per image with
+ *   counter = (b, n, 0, (counter & 0xffffff) << 8 | 0xF0)   (the low byte 0xF0 = layer 60, site 0 is no dropout word: site 0 exists at layer 0 only),
+ *   u_k = ((w_k >> 9) + 0.5) * 2^-23 for the eight output words w_0..w_7: 24 significant bits, so exactly an fp32 value in (0, 1);
+ *   phi = (2 u0 - 1) rotate_deg pi / 180;  tx = (2 u1 - 1) translate Wo;  ty = (2 u2 - 1) translate Ho;
+ *   z = exp(log zoom_lo + u3 (log zoom_hi - log zoom_lo));  flip iff u4 < flip_p;
+ *   b = 1 + (2 u5 - 1) brightness;  c = 1 + (2 u6 - 1) contrast;  u7 is reserved.
+ * Inverse map, pixel centres at + 0.5, F = diag(flip ? -1 : 1, 1), R(phi) = [cos -sin; sin cos]:
+ *   (xs, ys) = (Ws / 2, Hs / 2) + diag(Ws / Wo, Hs / Ho) (1 / z) R(phi) F (xo + 1/2 - Wo / 2 - tx, yo + 1/2 - Ho / 2 - ty)
+ * sampled bilinearly at (xs - 1/2, ys - 1/2), taps outside the source contributing zero (torch grid_sample, mode "bilinear",
+ * padding_mode "zeros", align_corners False), then v' = gain v + bias on the sampled value (fill included) with gain = b c,
+ * bias = b m (1 - c), m = the mean of source image n over all its elements, and with clamp01 v' clamped to [0, 1].
+ * augment_params: params[N][8] (an output, 16-byte aligned) = a00 a01 a02 a10 a11 a12 gain bias per image, with
+ *               xs = a00 xo + a01 yo + a02, ys = a10 xo + a11 yo + a12.  One block per image; m is summed by 256 threads over
+ *               elements e = thread, thread + 256, ... and then in a fixed order, so it does not depend on how a batch is cut.  The
+ *               source is not read when contrast == 0 (x may be NULL then).
+ * augment_nhwc:  x[N][C][Hs][Ws] (C = 3, or 1 replicated to three as ExpandChannels does) -> y[N][Ho][Wo][Cpad], padded channels 0;
+ *               Cpad % 4 == 0 and y, params 16-byte aligned (-1 otherwise); C other than 1 or 3: -4.  A tap of weight zero is left
+ *               out: an output is non-finite iff one of its taps of non-zero weight is (a NaN survives clamp01; -0 may become +0).
+ *               With the identity spec and Ho x Wo = Hs x Ws the output equals cxrk_nchw_to_nhwc's.
+ */
+int cxrk_augment_params(const float* x, int N, int C, int Hs, int Ws, int Ho, int Wo, float rotate_deg, float translate,
+                        float zoom_lo, float zoom_hi, float flip_p, float brightness, float contrast, unsigned long long seed,
+                        unsigned counter, long row_offset, float* params, hipStream_t stream);
+int cxrk_augment_nhwc(const float* x, const float* params, float* y, int N, int C, int Hs, int Ws, int Ho, int Wo, int Cpad,
+                      int clamp01, hipStream_t stream);
+
 /* maxpool — nn.MaxPool2d(3, stride 2, pad 1) of the ResNet stem (resnet.py:37). idx = winning tap per output. */
 int cxrk_maxpool_fwd(const float* x, float* y, unsigned char* idx, int N, int H, int W, int C, hipStream_t stream);
 int cxrk_maxpool_bwd(const float* dy, const unsigned char* idx, const float* x, float* dx, int N, int H, int W, int C,

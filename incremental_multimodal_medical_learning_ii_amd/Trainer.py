@@ -23,7 +23,9 @@ Two extensions behind the same entry points (both off unless asked for):
     pairs of the global batch with the same label vector / the same prompt tokens positives of each other (multi-positive InfoNCE,
     DESIGN.md §5.2; "labels" needs the fourth tensor of the batch); the default is one positive per row.  `"learn_temperature": True`
     (optionally `"log_scale_bounds": (lo, hi)`) makes the temperature a parameter: "temperature" is then its initial
-    value, `save` / `load` carry it as `logit_scale.pt`, and `train` logs `train/temperature` once per epoch.
+    value, `save` / `load` carry it as `logit_scale.pt`, and `train` logs `train/temperature` once per epoch.  `"augment": True | {...}`
+    (the fields of `augment.AugmentSpec`; True = a moderate default; optionally `"augment_seed"`) augments the images on the device
+    inside the training step; `val` / `test` never augment.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -159,7 +161,9 @@ class Trainer:
             self._joint = JointContrastiveTrainer(self.image_model, self.bert_encoder.model, lr=lr,
                                                   temperature=float(je.get("temperature", 0.07)), group=process_group, optim=OPTIM,
                                                   positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
-                                                  **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}))
+                                                  **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
+                                                  **({"augment": je["augment"], "augment_seed": je.get("augment_seed")}
+                                                     if je.get("augment") not in (None, False) else {}))
             print("*** JOINT ENCODER TRAINING (InfoNCE over the global batch): no adapters ***")
         params = []
         if self._joint is not None:

@@ -48,6 +48,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_bn_train_dz": (I, [P, L, P, L, P, P, P, P, L, L, I, P]),
     "cxrk_nchw_to_nhwc": (I, [P, P, I, I, I, I, I, P]),
     "cxrk_nhwc_to_nchw": (I, [P, P, I, I, I, I, P]),
+    "cxrk_augment_params": (I, [P, I, I, I, I, I, I, F, F, F, F, F, F, F, c_uint64, c_uint32, L, P, P]),
+    "cxrk_augment_nhwc": (I, [P, P, P, I, I, I, I, I, I, I, I, P]),
     "cxrk_maxpool_fwd": (I, [P, P, P, I, I, I, I, P]),
     "cxrk_maxpool_bwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "cxrk_maxpool_fwd_pl": (I, [P, L, P, L, P, I, I, I, I, P]),

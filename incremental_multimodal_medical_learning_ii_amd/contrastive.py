@@ -20,6 +20,12 @@ CLIP parametrises it, initialised from `temperature`; it sits in the flat buffer
 step, and is clamped to `log_scale_bounds` after it.  The loss kernels read theta on the device; its gradient travels in the flat
 gradient all-reduce (at the end of the "text" span): no new collective, no host sync.  `learn_temperature=False` (the default) creates no parameter and issues
 exactly the calls it always did.
+
+`augment=AugmentSpec(...)`: on-device image augmentation.  The trainer owns (seed, step counter) as `augment_state`
+and hands the image model one call descriptor per `step` (spec, seed, counter, this rank's first global row): the encoder's
+NCHW -> NHWC boundary transform then samples each image through its own random affine map and jitters brightness / contrast.  The
+draws are keyed by the global image index, so a sharded step augments exactly as the single-process step on the global batch does.
+`augment=None` (the default) issues exactly the calls it always did.
 """
 from __future__ import annotations
 
@@ -31,6 +37,7 @@ import torch
 from . import functional as Fh
 from . import kernels as K
 from . import optim as cxr_optim
+from .augment import AugmentCall, AugmentSpec, spec_from as _augment_spec_from
 
 
 # ----------------------------------------------------------------------------------------------------------------
@@ -120,7 +127,8 @@ class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
                  optim: str = "adam", positives: Optional[str] = None, learn_temperature: bool = False,
-                 log_scale_bounds: Tuple[float, float] = LOG_SCALE_BOUNDS):
+                 log_scale_bounds: Tuple[float, float] = LOG_SCALE_BOUNDS, augment: Optional[AugmentSpec] = None,
+                 augment_seed: Optional[int] = None):
         if positives not in POSITIVES:
             raise ValueError(f"positives must be None, 'labels' or 'text', got {positives!r}")
         self.logit_scale = None
@@ -132,6 +140,15 @@ class JointContrastiveTrainer:
                 raise ValueError(f"learn_temperature: the initial temperature must be positive, got {temperature!r}")
             self.log_scale_bounds = (lo, hi)
         self.positives = positives
+        self.augment = _augment_spec_from(augment)
+        self._augment, self._augment_version, self._augment_synced = None, 0, None
+        if self.augment is not None:
+            if augment_seed is None:     # one 64-bit seed from torch's default CPU generator (`torch.manual_seed` makes it repeatable)
+                w = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64)
+                augment_seed = (int(w[0]) << 32) | int(w[1])
+            self.augment_state = (augment_seed, 0)
+        elif augment_seed is not None:
+            raise ValueError("JointContrastiveTrainer: augment_seed given without an augment spec")
         self.image_model, self.text_model = image_model, text_model
         self.temperature, self.group = temperature, group
         import os
@@ -167,6 +184,7 @@ class JointContrastiveTrainer:
             self.rank = dist.get_rank(group)
         self._dropout_synced = None
         self.sync_dropout_state()
+        self.sync_augment_state()
         self._spans = self.reduce_spans(inamed, tparams) if self.world > 1 else {}
 
     def current_temperature(self) -> float:
@@ -192,6 +210,51 @@ class JointContrastiveTrainer:
         s, c = (int(v) for v in t.cpu())
         tm.dropout_state = (s & (2 ** 64 - 1), c)
         self._dropout_synced = tm._dropout_version
+
+    @property
+    def augment_state(self) -> Optional[Tuple[int, int]]:
+        """(seed, step counter) of the next augmented `step`; None without an augment spec.  Assign a pair to resume or repeat a
+        stream.  The kernels key the draws by the low 24 bits of the counter."""
+        return None if self._augment is None else (self._augment[0], self._augment[1])
+
+    @augment_state.setter
+    def augment_state(self, state: Tuple[int, int]) -> None:
+        if self.augment is None:
+            raise RuntimeError("augment_state: this trainer was constructed without an augment spec")
+        seed, counter = state
+        if int(counter) < 0:
+            raise ValueError("augment_state: the step counter must be >= 0")
+        self._augment = [int(seed) & (2 ** 64 - 1), int(counter)]
+        self._augment_version += 1
+
+    def sync_augment_state(self) -> None:
+        """Augmentation under data parallelism: every rank takes rank 0's (seed, counter), as `sync_dropout_state` does for the text
+        dropout; with the row offset of `step` the draws of a sharded step are those of the single-process step on the global batch.
+        Runs at construction and at the start of every `step`; it communicates only when `augment_state` was assigned since the last
+        time (on every rank, in the same program order)."""
+        if self.world == 1 or self._augment is None or self._augment_version == self._augment_synced:
+            return
+        import torch.distributed as dist
+        seed, counter = self._augment
+        dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
+        t = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed, counter], dtype=torch.int64, device=dev)
+        dist.broadcast(t, src=0 if self.group is None else dist.get_global_rank(self.group, 0), group=self.group)
+        s, c = (int(v) for v in t.cpu())
+        self._augment = [s & (2 ** 64 - 1), c]
+        self._augment_synced = self._augment_version
+
+    def _step_forward_loss(self, images, input_ids, attention_mask, labels, keys) -> torch.Tensor:
+        """`forward_loss` of one `step`: with an augment spec the image model carries this step's call descriptor while its forward
+        runs (row offset = this rank's first global row; the shards are equal and contiguous), and the counter advances once."""
+        if self._augment is None:
+            return self.forward_loss(images, input_ids, attention_mask, labels, keys)
+        seed, counter = self._augment
+        self._augment[1] = counter + 1
+        self.image_model.augment_call = AugmentCall(self.augment, seed, counter, self.rank * int(images.shape[0]))
+        try:
+            return self.forward_loss(images, input_ids, attention_mask, labels, keys)
+        finally:
+            self.image_model.augment_call = None
 
     def reduce_spans(self, inamed=None, tparams=None) -> dict:
         """{tag: (lo, hi)} element ranges of the flat gradient buffer that become complete together during `backward()`, in the
@@ -278,6 +341,7 @@ class JointContrastiveTrainer:
         collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog)."""
         self.optimizer.zero_grad()
         self.sync_dropout_state()
+        self.sync_augment_state()
         if self.world > 1 and self._spans:
             works, fired = [], []
 
@@ -293,14 +357,14 @@ class JointContrastiveTrainer:
 
             self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = on_ready
             try:
-                loss = self.forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
+                loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
             finally:
                 self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
             loss.backward()
             self.last_overlapped = tuple(fired)
             self.optimizer.all_reduce_grads(self.group, skip=[self._spans[t] for t in fired], pending=works)
         else:
-            loss = self.forward_loss(images, input_ids, attention_mask, labels, keys)
+            loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)
             loss.backward()
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)

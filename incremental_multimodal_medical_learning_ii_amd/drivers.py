@@ -121,12 +121,32 @@ def _setup(args, kind):
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine,
                              joint_encoders={"image_model": im, "temperature": args.temperature,
                                              "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None)),
-                                             "learn_temperature": bool(getattr(args, "learn_temperature", False))})
+                                             "learn_temperature": bool(getattr(args, "learn_temperature", False)),
+                                             "augment": augment_from_args(args)})
     else:
         from .health_multimodal.text import get_cxr_bert_inference
         engine = get_cxr_bert_inference(args.pretrained_text, device="cuda")
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine)
     return trainer, writer, train_loader, val_loader, test_loader
+
+
+AUG_FLAGS = {"aug_rotate": "rotate_deg", "aug_translate": "translate", "aug_zoom": "zoom", "aug_flip": "flip_p",
+             "aug_brightness": "brightness", "aug_contrast": "contrast"}
+
+
+def augment_from_args(args):
+    """The `--augment` / `--aug-*` flags -> None (no augmentation) or the dict of `augment.AugmentSpec` fields: `--augment` selects the
+    moderate default (+-10 degrees, 0.05, zoom 0.9..1.1, no flip, 0.2, 0.2), every `--aug-*` flag overrides one field of it."""
+    from .augment import DEFAULT_SPEC_ARGS
+    given = {field: getattr(args, flag) for flag, field in AUG_FLAGS.items() if getattr(args, flag, None) is not None}
+    if not getattr(args, "augment", False):
+        if given:
+            raise SystemExit("--aug-* flags set the ranges of the on-device augmentation and need --augment")
+        return None
+    spec = dict(DEFAULT_SPEC_ARGS)
+    spec.update(given)
+    spec["zoom"] = tuple(spec["zoom"])
+    return spec
 
 
 def zero_joint_bounds(args):
@@ -239,6 +259,15 @@ def make_parser():
     ap.add_argument("--learn-temperature", action="store_true",
                     help="--joint: learn the InfoNCE temperature (logit scale log(1/tau), initialised from --temperature, clamped to "
                          "[0, ln 100] after every step); default: the temperature is fixed")
+    ap.add_argument("--augment", action="store_true",
+                    help="--joint: augment the images on the device inside the training step (random affine + brightness / contrast, "
+                         "DESIGN.md 5.4); alone it selects +-10 degrees, translate 0.05, zoom 0.9..1.1, no flip, brightness / contrast 0.2")
+    ap.add_argument("--aug-rotate", type=float, default=None, metavar="DEG", help="--augment: rotation uniform in +-DEG degrees")
+    ap.add_argument("--aug-translate", type=float, default=None, metavar="FRAC", help="--augment: shift uniform in +-FRAC of the image size")
+    ap.add_argument("--aug-zoom", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--augment: zoom log-uniform in [LO, HI]")
+    ap.add_argument("--aug-flip", type=float, default=None, metavar="P", help="--augment: horizontal flip with probability P (default 0)")
+    ap.add_argument("--aug-brightness", type=float, default=None, metavar="B", help="--augment: brightness factor uniform in 1 +- B")
+    ap.add_argument("--aug-contrast", type=float, default=None, metavar="C", help="--augment: contrast factor uniform in 1 +- C")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -254,6 +283,10 @@ def main(argv=None):
     if args.learn_temperature and not args.joint:
         raise SystemExit("--learn-temperature makes the temperature of the north-star InfoNCE step a parameter and needs --joint (the "
                          "adapter schedules have no temperature)")
+    if args.augment and not args.joint:
+        raise SystemExit("--augment augments the images of the north-star step and needs --joint (the adapter schedules train on "
+                         "pre-computed image embeddings)")
+    augment_from_args(args)      # --aug-* without --augment
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)
     if int(os.environ.get("RANK", "0")) == 0:

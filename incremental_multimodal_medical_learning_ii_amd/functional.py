@@ -6,6 +6,7 @@
     group_mean                   prompt-embedding mean            Trainer.py:1665-1666
     posneg_bce_loss              pos-neg logits + BCEWithLogits   Trainer.py:575-583, ZERO_JOINT_BOUNDS.py:36
     infonce_loss                 north-star contrastive head (not in the reference), data-parallel aware
+    augment_images               on-device random affine + jitter (train-time transforms; no gradient)
 """
 from __future__ import annotations
 
@@ -389,3 +390,13 @@ def similarity_logits(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature:
     th, _ = K.l2norm_fwd(txt_emb.contiguous())
     out = torch.empty(ih.shape[0], th.shape[0], dtype=torch.float32, device=ih.device)
     return K.gemm(ih, th, out, ih.shape[0], th.shape[0], ih.shape[1], False, True, alpha=1.0 / temperature)
+
+
+@torch.no_grad()
+def augment_images(images: torch.Tensor, spec, seed: int, counter: int, row_offset: int = 0, cpad: int = 4) -> torch.Tensor:
+    """Random affine + brightness / contrast augmentation on the device (include/cxrk.h, "augment"):
+    images [N, 3 | 1, H, W] -> fp32 NHWC [N, Ho, Wo, cpad] (three channels, the padding zero), the tensor the ResNet stem reads.
+    Image i of the call is drawn for (seed, counter, row_offset + i) and for nothing else, so a batch cut anywhere gives the same
+    pixels.  No input gradient: `images` must not require grad."""
+    params = K.augment_params(images, spec, seed, counter, row_offset)
+    return K.augment_nhwc(images, cpad, params, spec.size_for(images.shape[2], images.shape[3]), spec.clamp01)

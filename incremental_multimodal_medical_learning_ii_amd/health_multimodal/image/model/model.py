@@ -91,6 +91,11 @@ class ImageModel(nn.Module):
         # as the gradients of "head" (projector + layer4), "layer3", "layer2", "stem" (layer1 + stem) become complete
         # (image_encoder._backward); set and cleared by the data-parallel trainer per step
         self.grad_ready_hook = None
+        # optional augment.AugmentCall (spec, seed, counter, row offset): a grad-enabled forward made while it is set samples its
+        # images through that call's random maps in place of the plain NCHW -> NHWC transform and may be given
+        # [B,1,H,W] images; no-grad forwards, `forward_stages`, `calibrate_batchnorm_` and the inference engines never augment.
+        # Set and cleared by the joint trainer per step.
+        self.augment_call = None
         if pretrained_model_path is not None:
             if not isinstance(pretrained_model_path, (str, Path)):
                 raise TypeError(f"Expected a string or Path, got {type(pretrained_model_path)}")
@@ -152,13 +157,16 @@ class ImageModel(nn.Module):
                                "(there is no CPU fallback; the CPU oracle lives in oracle/ and is test-only)")
         if x.dtype != torch.float32:
             raise ValueError(f"expected fp32 images, got {x.dtype}")
-        if x.dim() != 4 or x.shape[1] != 3:
+        augment = self.augment_call if torch.is_grad_enabled() else None
+        if x.dim() != 4 or not (x.shape[1] == 3 or (augment is not None and x.shape[1] == 1)):
             raise ValueError(f"ImageModel expects [B,3,H,W] input (ExpandChannels, transforms.py:12-38), got {tuple(x.shape)}")
+        if augment is not None and x.requires_grad:
+            raise ValueError("ImageModel.augment_call: the augmentation has no input gradient; pass images that do not require grad")
         momentum = self._bn_mode()
         self.prepare_()
         params, bufs = self._tensors()
         hook = self.grad_ready_hook if torch.is_grad_enabled() else None
-        meta = IE.EncodeMeta(self._specs, self._blocks, len(params), want_patch, hook, momentum)
+        meta = IE.EncodeMeta(self._specs, self._blocks, len(params), want_patch, hook, momentum, augment)
         with torch.set_grad_enabled(torch.is_grad_enabled() and not self.freeze_encoder):
             emb, patch = IE.ImageEncodeFn.apply(x, meta, *params, *bufs)
         if momentum is not None:       # the kernels updated running_mean / running_var in place; the counter is host bookkeeping

@@ -44,6 +44,7 @@ import torch
 
 from . import _lib
 from . import kernels as K
+from .augment import AugmentCall
 from .gradsink import GradSink
 from .kernels import Planes
 
@@ -111,6 +112,7 @@ class EncodeMeta(NamedTuple):
     want_patch: bool
     on_grads_ready: Optional[Callable] = None     # per-call hook of the backward (ImageModel.grad_ready_hook at forward time)
     bn_momentum: Optional[float] = None           # None: eval-mode BatchNorm; float: train mode (ImageModel.train())
+    augment: Optional[AugmentCall] = None         # on-device augmentation of this call (ImageModel.augment_call at forward time)
 
 
 def _filter_rsc(w: torch.Tensor) -> torch.Tensor:
@@ -287,13 +289,28 @@ def _proj_linear(pj1m, w3, b3, pl):
     return K.linear_fwd(pj1m, w3m, b3), None
 
 
+def _stem_input(x: torch.Tensor, augment: Optional[AugmentCall]) -> torch.Tensor:
+    """NCHW images -> the stem's NHWC input (3 channels zero-padded to 4): the plain layout transform, or the augmenting one"""
+    if augment is None:
+        return K.nchw_to_nhwc(x, 4)
+    sp = augment.spec
+    params = K.augment_params(x, sp, augment.seed, augment.counter, augment.row_offset)
+    return K.augment_nhwc(x, 4, params, sp.size_for(x.shape[2], x.shape[3]), sp.clamp01)
+
+
 def _forward(specs, blocks, p: Sequence[torch.Tensor], bufs: Sequence[torch.Tensor], x: torch.Tensor, save: bool,
-             want_patch: bool, stages: Optional[list] = None, keep_stem: bool = False, bn_momentum: Optional[float] = None):
+             want_patch: bool, stages: Optional[list] = None, keep_stem: bool = False, bn_momentum: Optional[float] = None,
+             augment: Optional[AugmentCall] = None):
     """bn_momentum: None = eval-mode BatchNorm (running statistics folded into the filters, the reference's only use of the encoder);
-    a float = train-mode BatchNorm with that momentum (batch statistics; `ImageModel.train()`).  -> (emb, patch, `_Saved` or None)"""
+    a float = train-mode BatchNorm with that momentum (batch statistics; `ImageModel.train()`).  augment: the boundary transform
+    NCHW -> NHWC samples the images through that call's random maps (csrc/augment.hip; 1-channel images are expanded to three) and
+    the trunk runs at the size it samples to; the augmented tensor is the stem input the backward reads, so nothing else changes.
+    -> (emb, patch, `_Saved` or None)"""
     N, C, H, W = x.shape
-    if C != 3:
+    if C != 3 and not (augment is not None and C == 1):
         raise ValueError(f"ImageModel expects 3-channel input (ExpandChannels, transforms.py:12-38), got {C}")
+    if augment is not None:
+        H, W = augment.spec.size_for(H, W)       # the trunk runs at the size the augmentation samples to
     pl = _planes_mode()
     fold = _Fold(specs, x.device, pl)
     train = bn_momentum is not None
@@ -306,7 +323,7 @@ def _forward(specs, blocks, p: Sequence[torch.Tensor], bufs: Sequence[torch.Tens
             return _conv_bn_train(i, specs[i], fold, p, bufs, x, residual, relu, N, H, W, want_mask, bn_momentum, st.bn if save else None)
         return _conv(i, specs[i], fold, x, residual, relu, N, H, W, want_mask)
 
-    pj1, h, w = _trunk(specs, blocks, unit, K.nchw_to_nhwc(x, 4), H, W, pl, st, keep_stem, stages)
+    pj1, h, w = _trunk(specs, blocks, unit, _stem_input(x, augment), H, W, pl, st, keep_stem, stages)
     pj2, w3p = _proj_linear(pj1.view(N * h * w, pj1.shape[-1]), p[3 * len(specs)], p[3 * len(specs) + 1], pl)
     if save:
         st.w3p = w3p
@@ -642,7 +659,7 @@ class ImageEncodeFn(torch.autograd.Function):
         p = [t.detach() for t in params]
         b = [t.detach() for t in bufs]
         emb, patch, state = _forward(meta.specs, meta.blocks, p, b, x.detach(), save, meta.want_patch, keep_stem=_capture is not None,
-                                     bn_momentum=meta.bn_momentum)
+                                     bn_momentum=meta.bn_momentum, augment=meta.augment)
         if save:
             ctx.state, ctx.p, ctx.b, ctx.meta, ctx.params = state, p, b, meta, params
             if _capture is not None:

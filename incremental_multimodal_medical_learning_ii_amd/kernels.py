@@ -809,6 +809,46 @@ def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _chk_images(x: torch.Tensor, name: str) -> torch.Tensor:
+    _chk(x, name)
+    if x.dim() != 4 or x.shape[1] not in (1, 3):
+        raise ValueError(f"{name}: expected [N, 3, H, W] or [N, 1, H, W] images, got shape {tuple(x.shape)}")
+    if x.requires_grad:
+        raise ValueError(f"{name}: the augmentation has no input gradient; pass images that do not require grad")
+    return x.contiguous()
+
+
+def augment_params(x: torch.Tensor, spec, seed: int, counter: int, row_offset: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Parameter rows [N, 8] (a00 a01 a02 a10 a11 a12 gain bias) of the images `x` under `spec` (augment.AugmentSpec), drawn for
+    (seed, counter, row_offset + i): include/cxrk.h, "augment".  The images are read only when spec.contrast != 0 (their means)."""
+    lib = _lib.load()
+    x = _chk_images(x, "augment_params.x")
+    N, C, Hs, Ws = x.shape
+    Ho, Wo = spec.size_for(Hs, Ws)
+    params = torch.empty(N, 8, dtype=torch.float32, device=x.device) if out is None else _chk_out(out, (N, 8), "augment_params.out")
+    check(lib.cxrk_augment_params(_p(x) if spec.contrast != 0 else None, N, C, Hs, Ws, Ho, Wo, spec.rotate_deg, spec.translate, spec.zoom[0],
+                                  spec.zoom[1], spec.flip_p, spec.brightness, spec.contrast, int(seed) & (2 ** 64 - 1),
+                                  int(counter) & 0xFFFFFFFF, int(row_offset), _p(params), _stream()), "cxrk_augment_params")
+    return params
+
+
+def augment_nhwc(x: torch.Tensor, cpad: int, params: torch.Tensor, out_size=None, clamp01: bool = False,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x [N, C, Hs, Ws] (C = 3, or 1 replicated to three) sampled through the inverse affine maps `params` (augment_params) ->
+    fp32 [N, Ho, Wo, cpad]; the augmenting form of `nchw_to_nhwc`.  `out`: a caller's tensor of that shape (its address is checked
+    by the library: 16-byte stores)."""
+    lib = _lib.load()
+    x = _chk_images(x, "augment_nhwc.x")
+    N, C, Hs, Ws = x.shape
+    Ho, Wo = (Hs, Ws) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    _chk(params, "augment_nhwc.params")
+    if tuple(params.shape) != (N, 8) or not params.is_contiguous():
+        raise ValueError(f"augment_nhwc.params: expected a contiguous [{N}, 8] tensor, got {tuple(params.shape)}")
+    y = torch.empty(N, Ho, Wo, cpad, dtype=torch.float32, device=x.device) if out is None else _chk_out(out, (N, Ho, Wo, cpad), "augment_nhwc.out")
+    check(lib.cxrk_augment_nhwc(_p(x), _p(params), _p(y), N, C, Hs, Ws, Ho, Wo, cpad, int(bool(clamp01)), _stream()), "cxrk_augment_nhwc")
+    return y
+
+
 def maxpool_fwd(x: torch.Tensor):
     lib = _lib.load()
     N, H, W, C = x.shape
