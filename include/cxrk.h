@@ -140,6 +140,11 @@ int cxrk_conv_bn_act_bwd_params(const float* x, const float* dy, const float* w,
                                 const float* rmean, const float* sumdy, float* dw, float* dgamma, float* dbeta,
                                 int accumulate, int N, int H, int W, int C, int Cpad, int Ko, int R, int S, int stride,
                                 int pad, float* ws, size_t ws_bytes, hipStream_t stream);
+/* Planes operands.  Which kernel takes which shapes: 3x3 / stride 1 / pad 1 with C = Ko = 64 and rows of <= 58 pixels go to the
+ * window-resident kernel (csrc/conv_halo_wgrad.h: x resident in an LDS ring for all nine taps, one block per split-K slab — the
+ * implicit GEMM's slabs, bit-identical result) unless CXRK_HALO=0 (read once) or CXRK_HALO_WGRAD=0 (read on every call); everything else is a split-K
+ * implicit GEMM on the LDS-DMA tiles (256 x 256 where the policy picks it, 64 x 256 for Ko <= 64, 128 x 128 otherwise).
+ * Both paths write the same slabs: cxrk_conv_wgrad_ws_bytes is one bound for both. */
 int cxrk_conv_bn_act_bwd_params_pl(const void* x, long xplane, const void* dy, long dyplane, const float* w, const float* scale,
                                    const float* rstd, const float* rmean, const float* sumdy, float* dw, float* dgamma,
                                    float* dbeta, int accumulate, int N, int H, int W, int C, int Ko, int R, int S, int stride,

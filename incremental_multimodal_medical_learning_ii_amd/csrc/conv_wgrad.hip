@@ -1,6 +1,7 @@
 // ResNet-50 image-encoder kernels, weight gradient: split-K implicit GEMM over the pixels, deterministic slab reduction that also
 // produces the BatchNorm gamma / beta gradients.
 #include "conv_common.h"
+#include "conv_halo_wgrad.h"
 
 using namespace cxrk;
 
@@ -92,6 +93,7 @@ extern "C" size_t cxrk_conv_wgrad_ws_bytes(int N, int H, int W, int C, int Ko, i
   int sk = wgrad_splitk(Ko, R * S * C, (long)N * g.Ho * g.Wo, false);   // upper bound over both storage formats
   const int sk2 = wgrad_splitk(Ko, R * S * C, (long)N * g.Ho * g.Wo, true);
   if (sk2 > sk) sk = sk2;
+  // (the window-resident kernel of conv_halo_wgrad.h writes the same slabs as the implicit GEMM: one bound covers both paths)
   return ((size_t)sk * (size_t)Ko * (size_t)(R * S * C) + (size_t)Ko * wgrad_dot_parts(R * S * C)) * sizeof(float);
 }
 
@@ -109,6 +111,9 @@ static int conv_bwd_params_impl(const typename FMT::T* x, long xplane, const typ
   CXRK_CHECK_ARG(Kl < (1L << 31));
   const int Kred = (int)Kl, Nc = R * S * Cpad;
   if ((long)H * W * Cpad * 4 * 3 >= (1L << 31)) return CXRK_ERR_UNSUPPORTED;  // a K-tile of 32 pixels spans <= 3 images
+  // 3x3 / stride 1 / 64 -> 64 on planes operands: the window-resident kernel, same slabs, bit-identical result (conv_halo_wgrad.h)
+  const bool window = FMT::PLANES && halo_wgrad_enabled() && halo_wgrad_shape(N, H, W, Cpad, Ko, R, S, stride, pad) &&
+                      halo_applies(H, W, Cpad, Ko, R, S, stride, pad);
   int sk = wgrad_splitk(Ko, Nc, Kl, FMT::PLANES);
   const size_t slab_floats = (size_t)sk * Ko * Nc;
   CXRK_CHECK_WS(ws, ws_bytes, (slab_floats + (size_t)Ko * wgrad_dot_parts(Nc)) * sizeof(float));
@@ -119,7 +124,10 @@ static int conv_bwd_params_impl(const typename FMT::T* x, long xplane, const typ
   // cancelling sum over 12.8 M pixels of an all-positive input, and was kept exact fp32 in round 1 for that reason; re-measured
   // in round 2 under imposed max-pool winners (r2k): split-bf16 passes the same 1e-3 gradient parity, 4.0 -> ~2 ms per step.
   const bool exact = false;
-  if (use_wide256(Ko, Nc, Kred, sk, FMT::PLANES)) {
+  if (window) {
+    if constexpr (FMT::PLANES) rc = launch_conv3x3_wgrad_window(x, xplane, dy, dyplane, ws, ep.slab_stride, Nc, Kred, H, W, sk, stream);
+    else return CXRK_ERR_UNSUPPORTED;
+  } else if (use_wide256(Ko, Nc, Kred, sk, FMT::PLANES)) {
     if constexpr (FMT::PLANES) {
       DmaDenseMC<256, 8>::P pa{dy, (long)Ko, Ko, Kred, dyplane}; DmaConvIm2colMC<256, 8>::P pb{x, g, Nc, Kred, xplane};
       rc = launch_gemm_pw<Pw256, DmaDenseMC<256, 8>, DmaConvIm2colMC<256, 8>>(pa, pb, ep, Ko, Nc, Kred, sk, stream);

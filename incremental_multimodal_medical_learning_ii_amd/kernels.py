@@ -6,6 +6,7 @@ falls back to torch arithmetic.
 """
 from __future__ import annotations
 
+import os
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -735,6 +736,19 @@ def conv1x1_s2_bwd_data_compact_pl(dy: Planes, w_scaled: Planes, N, H, W, C, Ko)
     return out.view(N, Ho, Wo, C)
 
 
+def _wgrad_window_takes(H, W, C, Ko, R, S, stride, pad) -> bool:
+    """Mirror of the library's dispatch (csrc/conv_wgrad.hip): the window-resident weight-gradient kernel takes the planes 3x3 /
+    stride 1 / pad 1 layers with 64 -> 64 channels and rows of <= 58 pixels unless CXRK_HALO=0 or CXRK_HALO_WGRAD=0."""
+    def off(name):
+        v = os.environ.get(name)
+        try:
+            return v is not None and int(v) == 0
+        except ValueError:
+            return True      # atoi() of a non-number is 0
+    return (R == 3 and S == 3 and stride == 1 and pad == 1 and C == 64 and Ko == 64 and 1 <= W <= 58 and H >= 1
+            and not off("CXRK_HALO") and not off("CXRK_HALO_WGRAD"))
+
+
 def conv_bwd_params_pl(x: Planes, dy: Planes, w, scale, rstd, rmean, sumdy, dw, dgamma, dbeta, accumulate, N, H, W, C, Ko, R, S, stride, pad):
     lib = _lib.load()
     ws = workspace(lib.cxrk_conv_wgrad_ws_bytes(N, H, W, C, Ko, R, S, stride, pad), x.device)
@@ -743,8 +757,11 @@ def conv_bwd_params_pl(x: Planes, dy: Planes, w, scale, rstd, rmean, sumdy, dw, 
         Ho, Wo = _conv_out(H, W, R, S, stride, pad)
         fl = 2.0 * N * Ho * Wo * Ko * R * S * C
         sk = lib.cxrk_gemm_wgrad_splitk(Ko, R * S * C, N * Ho * Wo, 1)
-        ev = profiler.bracket(_label("DenseMC", "ConvIm2colMC", "1,4" if Ko <= 64 else "2,2", Ko, R * S * C, N * Ho * Wo, sk, 0, planes=True),
-                              fl, 4.0 * (N * H * W * C + N * Ho * Wo * Ko + Ko * R * S * C))
+        if _wgrad_window_takes(H, W, C, Ko, R, S, stride, pad):
+            label = "conv3x3_wgrad_window_kernel"
+        else:
+            label = _label("DenseMC", "ConvIm2colMC", "1,4" if Ko <= 64 else "2,2", Ko, R * S * C, N * Ho * Wo, sk, 0, planes=True)
+        ev = profiler.bracket(label, fl, 4.0 * (N * H * W * C + N * Ho * Wo * Ko + Ko * R * S * C))
     check(lib.cxrk_conv_bn_act_bwd_params_pl(x.ptr(), x.plane, dy.ptr(), dy.plane, _p(w), _p(scale), _p(rstd), _p(rmean), _p(sumdy),
                                              _p(dw), _p(dgamma), _p(dbeta), int(accumulate), N, H, W, C, Ko, R, S, stride, pad, _p(ws),
                                              ws.numel() * 4, _stream()),

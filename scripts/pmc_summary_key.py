@@ -3,6 +3,8 @@ import re
 
 
 def key(k):
+    if "conv3x3_wgrad_window_kernel" in k:      # csrc/conv_halo_wgrad.h; the label of kernels.conv_bwd_params_pl for its shapes
+        return "conv3x3_wgrad_window_kernel"
     m = re.search(r"gemm_pw_kernel<cxrk::PwCfg<(\d), (\d), (\d)>, cxrk::(\w+)<[^>]*>, cxrk::(\w+)<[^>]*>\s*>", k)
     if m:
         cfg = {"244": "Pw256", "222": "Pw128", "412": "Pw256x64", "142": "Pw64x256"}.get(m.group(1) + m.group(2) + m.group(3), "Pw?")
