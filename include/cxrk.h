@@ -56,6 +56,13 @@ int cxrk_gemm_wgrad_splitk(int M, int N, int K, int planes);
 /* 1 when a launch of this GEMM shape takes the 256x256 tile (reporting only).  kind: 0 or 3 dense layer / weight gradient,
  * 1 convolution forward, 2 convolution data gradient. */
 int cxrk_gemm_wide_tile(int M, int N, long K, int splitk, int kind);
+/* What the last call of a GEMM-family entry point (cxrk_gemm_f32 / _pl, cxrk_conv_bn_act_fwd* / _bwd_data* / _bwd_params*) on the
+ * calling thread launched: the kernel instantiation as scripts/pmc_summary_key.py abbreviates its rocprofv3 name ("" if the call
+ * launched nothing; valid until the thread's next query), the number of MFMA kernel launches (reductions not counted), and whether
+ * the mainloop is the split-bf16 one.  Of several launches the label is that of the largest M*N*K (the first on ties). */
+const char* cxrk_last_launch_label(void);
+int cxrk_last_launch_count(void);
+int cxrk_last_launch_split_bf16(void);
 int cxrk_gemm_f32(int transA, int transB, int M, int N, int K, const float* A, long lda, const float* B, long ldb,
                   float* C, long ldc, const float* bias, const float* R, long ldr, const float* aux, long ldaux,
                   int auxmode, float* C2, long ldc2, int act, float alpha, int accumulate, int splitk, float* ws,

@@ -104,6 +104,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_weight_reset": (I, [P, P, L, F, P, P, Z, P]),
     "cxrk_gemm_wgrad_splitk": (I, [I, I, I, I]),
     "cxrk_gemm_wide_tile": (I, [I, I, L, I, I]),
+    "cxrk_last_launch_label": (c_char_p, []),
+    "cxrk_last_launch_count": (I, []),
+    "cxrk_last_launch_split_bf16": (I, []),
     "cxrk_set_precision": (I, [I]),
     "cxrk_get_precision": (I, []),
     "cxrk_set_wide_mode": (I, [I]),

@@ -31,28 +31,46 @@ __global__ __launch_bounds__(1024) void colsum_part_final_kernel(const float* __
 
 // ---- data gradient ---------------------------------------------------------------------------------------------------
 // dx[n][hi][wi][c] = mask( sum_{r,s,ko} dy[n][(hi+pad-r)/st][(wi+pad-s)/st][ko] * w_scaled[ko][r][s][c] + residual )
-// 64-row slabs of column-sum partials one data-gradient launch writes: its row tile (256 with the 256x256 / 256x64 tiles, else
-// 128) rounded up, in slabs.  K = contraction length of that launch (selects the tile exactly as the launch does).
-static int dgrad_tiles(int rows, int C, long K, bool planes) {
-  const bool t256 = use_wide256(rows, C, K, 1, planes, WIDE_MINK_DGRAD) || C <= 64;
-  return ceil_div(rows, t256 ? 256 : 128) * (t256 ? 4 : 2);
+// The 64 -> 64 3x3 layers on planes operands, where the 256x256 tile does not pay: the dy window resident in LDS (conv_halo.h)
+static bool dgrad_takes_halo(bool planes, int M, int H, int W, int C, int Ko, int R, int S, int stride, int pad) {
+  return planes && halo_applies(H, W, Ko, C, R, S, stride, pad) && pick_tile(CONV_DGRAD, M, C, (long)R * S * Ko, 1, true) != TILE_256;
 }
 
-// number of per-wave partial rows the fused column sum of a data-gradient launch produces (all parity classes)
-static long dgrad_colsum_parts(int N, int H, int W, int C, int stride, int Ko, int R, int S, int pad, bool planes) {
-  if (planes && halo_applies(H, W, Ko, C, R, S, stride, pad) && !use_wide256(N * H * W, C, (long)R * S * Ko, 1, planes, WIDE_MINK_DGRAD))
-    return (long)ceil_div(N * H * W, HALO_TM) * 8;      // conv_halo.h: one partial row per 32-row half of a 64-row block
-  if (stride == 1) return dgrad_tiles(N * H * W, C, (long)R * S * Ko, planes);
-  long t = 0;
+// Stride 2 runs as one launch per output-parity class (ph, pw), over the half-resolution grid Hs x Ws of that class's pixels and
+// only the taps that reach it.  Fills cls with the classes that have pixels (t.nr * t.ns == 0: no tap reaches the class, its
+// pixels are zero) and returns how many.  Tap lists are kept for R, S <= 3 (at most two taps per parity).
+struct S2Class { S2Taps t; int ph, pw, Hs, Ws; };
+static int s2_classes(int H, int W, int R, int S, int pad, S2Class (&cls)[4]) {
+  int n = 0;
   for (int ph = 0; ph < 2; ++ph)
     for (int pw = 0; pw < 2; ++pw) {
-      const int Hs = (H - ph + 1) / 2, Ws = (W - pw + 1) / 2;
-      int nr = 0, ns = 0;
-      for (int r = 0; r < R; ++r) if (((ph + pad - r) & 1) == 0) ++nr;
-      for (int q = 0; q < S; ++q) if (((pw + pad - q) & 1) == 0) ++ns;
-      if (Hs > 0 && Ws > 0 && nr > 0 && ns > 0) t += dgrad_tiles(N * Hs * Ws, C, (long)nr * ns * Ko, planes);
+      S2Class c{};
+      c.ph = ph; c.pw = pw; c.Hs = (H - ph + 1) / 2; c.Ws = (W - pw + 1) / 2;
+      if (c.Hs <= 0 || c.Ws <= 0) continue;
+      S2Taps& t = c.t;
+      for (int r = 0; r < R; ++r) if (((ph + pad - r) & 1) == 0) { if (t.nr < 2) { t.r[t.nr] = r; t.dr[t.nr] = (ph + pad - r) / 2; } ++t.nr; }
+      for (int q = 0; q < S; ++q) if (((pw + pad - q) & 1) == 0) { if (t.ns < 2) { t.s[t.ns] = q; t.ds[t.ns] = (pw + pad - q) / 2; } ++t.ns; }
+      cls[n++] = c;
     }
-  return t;
+  return n;
+}
+
+// number of per-wave partial rows the fused column sum of a data gradient produces (all its launches): asks the policy for the
+// tile of each launch with that launch's own shape
+static long dgrad_colsum_parts(int N, int H, int W, int C, int stride, int Ko, int R, int S, int pad, bool planes) {
+  if (stride == 1) {
+    if (dgrad_takes_halo(planes, N * H * W, H, W, C, Ko, R, S, stride, pad))
+      return (long)ceil_div(N * H * W, HALO_TM) * 8;      // conv_halo.h: one partial row per 32-row half of a 64-row block
+    return colsum_slabs(pick_tile(CONV_DGRAD, N * H * W, C, (long)R * S * Ko, 1, planes), N * H * W);
+  }
+  S2Class cls[4];
+  const int ncls = s2_classes(H, W, R, S, pad, cls);
+  long parts = 0;
+  for (int i = 0; i < ncls; ++i) {
+    const S2Class& c = cls[i];
+    if (c.t.nr * c.t.ns > 0) parts += colsum_slabs(pick_tile(CONV_DGRAD, N * c.Hs * c.Ws, C, (long)c.t.nr * c.t.ns * Ko, 1, planes), N * c.Hs * c.Ws);
+  }
+  return parts;
 }
 
 // `ep` carries output / residual / mask operands in either storage format; ep.colsum_part (optional) = partial buffer.
@@ -70,86 +88,41 @@ static int conv_bwd_data_impl(const typename FMT::T* dy, long dyplane, const typ
   if (!tile_span_ok((long)(H / stride) * (W / stride), (long)g.Ho * g.Wo * Ko)) return CXRK_ERR_UNSUPPORTED;
   int rc = 0;
   if (stride == 1) {
-    if (use_wide256(M, C, K, 1, FMT::PLANES, WIDE_MINK_DGRAD)) {
-      if constexpr (FMT::PLANES) {
-        DmaConvDgradKC<256, 8>::P pa{dy, g, M, K, dyplane}; DmaConvFilterMC<256, 8>::P pb{w, g, C, K, wplane};
-        rc = launch_gemm_pw<Pw256, DmaConvDgradKC<256, 8>, DmaConvFilterMC<256, 8>>(pa, pb, ep, M, C, K, 1, stream);
-      } else return CXRK_ERR_UNSUPPORTED;
-    } else if (FMT::PLANES && halo_applies(H, W, Ko, C, R, S, stride, pad)) {   // 64 -> 64: the dy window resident in LDS (conv_halo.h)
-      if constexpr (FMT::PLANES) {
-        DmaConvFilterMC<64, 4>::P pb{w, g, C, K, wplane};
-        rc = launch_conv3x3_halo<DmaConvFilterMC<64, 4>, true>(dy, dyplane, pb, ep, M, C, H, W, stream);
-      } else rc = CXRK_ERR_UNSUPPORTED;
-    } else if (C <= 64) {
-      if constexpr (FMT::PLANES) {
-        DmaConvDgradKC<256, 4>::P pa{dy, g, M, K, dyplane}; DmaConvFilterMC<64, 4>::P pb{w, g, C, K, wplane};
-        rc = launch_gemm_pw<Pw256x64, DmaConvDgradKC<256, 4>, DmaConvFilterMC<64, 4>>(pa, pb, ep, M, C, K, 1, stream);
-      } else {
-        typename ConvDgradKC<256, FMT>::P pa{dy, g, M, K, dyplane}; typename ConvFilterMC<64, FMT>::P pb{w, g, C, K, wplane};
-        rc = launch_gemm<ConvDgradKC<256, FMT>, ConvFilterMC<64, FMT>, 4, 1>(pa, pb, ep, M, C, K, 1, stream);
-      }
-    } else if constexpr (FMT::PLANES) {
-      DmaConvDgradKC<128, 4>::P pa{dy, g, M, K, dyplane}; DmaConvFilterMC<128, 4>::P pb{w, g, C, K, wplane};
-      rc = launch_gemm_pw<Pw128, DmaConvDgradKC<128, 4>, DmaConvFilterMC<128, 4>>(pa, pb, ep, M, C, K, 1, stream);
-    } else {
-      typename ConvDgradKC<128, FMT>::P pa{dy, g, M, K, dyplane}; typename ConvFilterMC<128, FMT>::P pb{w, g, C, K, wplane};
-      rc = launch_gemm<ConvDgradKC<128, FMT>, ConvFilterMC<128, FMT>, 2, 2>(pa, pb, ep, M, C, K, 1, stream);
-    }
+    auto mka = [&](auto t) { return typename decltype(t)::type::P{dy, g, M, K, dyplane}; };
+    auto mkb = [&](auto t) { return typename decltype(t)::type::P{w, g, C, K, wplane}; };
+    if constexpr (FMT::PLANES) {
+      if (dgrad_takes_halo(true, M, H, W, C, Ko, R, S, stride, pad))
+        rc = launch_conv3x3_halo<DmaConvFilterMC<64, 4>, true>(dy, dyplane, mkb(LoaderTag<DmaConvFilterMC<64, 4>>{}), ep, M, C, H, W, stream);
+      else rc = launch_gemm_pw<CONV_DGRAD, DmaConvDgradKC, DmaConvFilterMC>(mka, mkb, ep, M, C, K, 1, stream);
+    } else rc = launch_gemm<CONV_DGRAD, ConvDgradKC, ConvFilterMC>(mka, mkb, ep, M, C, K, 1, stream);
     return rc < 0 ? rc : CXRK_OK;
   }
-  // stride 2: one launch per output-parity class, only over the taps that reach it
   CXRK_CHECK_ARG(R <= 3 && S <= 3);
-  long part_off = 0;
-  bool zeroed = false;
-  for (int pass = 0; pass < 2; ++pass) {
-    for (int ph = 0; ph < 2; ++ph) {
-      for (int pw = 0; pw < 2; ++pw) {
-        S2Taps t{};
-        for (int r = 0; r < R; ++r) if (((ph + pad - r) & 1) == 0) { t.r[t.nr] = r; t.dr[t.nr] = (ph + pad - r) / 2; ++t.nr; }
-        for (int q = 0; q < S; ++q) if (((pw + pad - q) & 1) == 0) { t.s[t.ns] = q; t.ds[t.ns] = (pw + pad - q) / 2; ++t.ns; }
-        const int Hs = (H - ph + 1) / 2, Ws = (W - pw + 1) / 2;
-        if (Hs <= 0 || Ws <= 0) continue;
-        if (pass == 0) {
-          if (t.nr == 0 || t.ns == 0) {
-            // no tap reaches this class: its pixels are exactly zero.  Only the plain form is supported there.
-            CXRK_CHECK_ARG(!has_side);
-            if (!zeroed) {
-              void* base = ep.Cp ? static_cast<void*>(ep.Cp) : static_cast<void*>(ep.C);
-              if (hipMemsetAsync(base, 0, (size_t)M * C * (ep.Cp ? 2 : 4), stream) != hipSuccess) return CXRK_ERR_LAUNCH;
-              if (ep.Cp && hipMemsetAsync(ep.Cp + ep.cplane, 0, (size_t)M * C * 2, stream) != hipSuccess) return CXRK_ERR_LAUNCH;
-              zeroed = true;
-            }
-          }
-          continue;
-        }
-        if (t.nr == 0 || t.ns == 0) continue;
-        const int Ms = N * Hs * Ws, Ks = t.nr * t.ns * Ko;
-        EpiParams e2 = ep;
-        if (ep.colsum_part) { e2.colsum_part = ep.colsum_part + part_off * C; part_off += dgrad_tiles(Ms, C, Ks, FMT::PLANES); }
-        e2.rm_on = 1; e2.rm_Hs = Hs; e2.rm_Ws = Ws; e2.rm_H = H; e2.rm_W = W; e2.rm_ph = ph; e2.rm_pw = pw;
-        if (use_wide256(Ms, C, Ks, 1, FMT::PLANES, WIDE_MINK_DGRAD)) {
-          if constexpr (FMT::PLANES) {
-            DmaConvDgradS2KC<256, 8>::P pa{dy, g, t, Hs, Ws, Ms, Ks, dyplane}; DmaConvFilterS2MC<256, 8>::P pb{w, g, t, C, Ks, wplane};
-            rc = launch_gemm_pw<Pw256, DmaConvDgradS2KC<256, 8>, DmaConvFilterS2MC<256, 8>>(pa, pb, e2, Ms, C, Ks, 1, stream);
-          } else return CXRK_ERR_UNSUPPORTED;
-        } else if (C <= 64) {
-          if constexpr (FMT::PLANES) {
-            DmaConvDgradS2KC<256, 4>::P pa{dy, g, t, Hs, Ws, Ms, Ks, dyplane}; DmaConvFilterS2MC<64, 4>::P pb{w, g, t, C, Ks, wplane};
-            rc = launch_gemm_pw<Pw256x64, DmaConvDgradS2KC<256, 4>, DmaConvFilterS2MC<64, 4>>(pa, pb, e2, Ms, C, Ks, 1, stream);
-          } else {
-            typename ConvDgradS2KC<256, FMT>::P pa{dy, g, t, Hs, Ws, Ms, Ks, dyplane}; typename ConvFilterS2MC<64, FMT>::P pb{w, g, t, C, Ks, wplane};
-            rc = launch_gemm<ConvDgradS2KC<256, FMT>, ConvFilterS2MC<64, FMT>, 4, 1>(pa, pb, e2, Ms, C, Ks, 1, stream);
-          }
-        } else if constexpr (FMT::PLANES) {
-          DmaConvDgradS2KC<128, 4>::P pa{dy, g, t, Hs, Ws, Ms, Ks, dyplane}; DmaConvFilterS2MC<128, 4>::P pb{w, g, t, C, Ks, wplane};
-          rc = launch_gemm_pw<Pw128, DmaConvDgradS2KC<128, 4>, DmaConvFilterS2MC<128, 4>>(pa, pb, e2, Ms, C, Ks, 1, stream);
-        } else {
-          typename ConvDgradS2KC<128, FMT>::P pa{dy, g, t, Hs, Ws, Ms, Ks, dyplane}; typename ConvFilterS2MC<128, FMT>::P pb{w, g, t, C, Ks, wplane};
-          rc = launch_gemm<ConvDgradS2KC<128, FMT>, ConvFilterS2MC<128, FMT>, 2, 2>(pa, pb, e2, Ms, C, Ks, 1, stream);
-        }
-        if (rc < 0) return rc;
-      }
+  S2Class cls[4];
+  const int ncls = s2_classes(H, W, R, S, pad, cls);
+  for (int i = 0; i < ncls; ++i)
+    if (cls[i].t.nr * cls[i].t.ns == 0) {
+      // no tap reaches this class: its pixels are exactly zero.  Only the plain form is supported there.
+      CXRK_CHECK_ARG(!has_side);
+      void* base = ep.Cp ? static_cast<void*>(ep.Cp) : static_cast<void*>(ep.C);
+      if (hipMemsetAsync(base, 0, (size_t)M * C * (ep.Cp ? 2 : 4), stream) != hipSuccess) return CXRK_ERR_LAUNCH;
+      if (ep.Cp && hipMemsetAsync(ep.Cp + ep.cplane, 0, (size_t)M * C * 2, stream) != hipSuccess) return CXRK_ERR_LAUNCH;
+      break;
     }
+  long part_off = 0;
+  for (int i = 0; i < ncls; ++i) {
+    const S2Class& c = cls[i];
+    const S2Taps& t = c.t;
+    if (t.nr * t.ns == 0) continue;
+    const int Hs = c.Hs, Ws = c.Ws, Ms = N * Hs * Ws, Ks = t.nr * t.ns * Ko;
+    EpiParams e2 = ep;
+    if (ep.colsum_part) { e2.colsum_part = ep.colsum_part + part_off * C; part_off += colsum_slabs(pick_tile(CONV_DGRAD, Ms, C, Ks, 1, FMT::PLANES), Ms); }
+    e2.rm_on = 1; e2.rm_Hs = Hs; e2.rm_Ws = Ws; e2.rm_H = H; e2.rm_W = W; e2.rm_ph = c.ph; e2.rm_pw = c.pw;
+    auto mka = [&](auto l) { return typename decltype(l)::type::P{dy, g, t, Hs, Ws, Ms, Ks, dyplane}; };
+    auto mkb = [&](auto l) { return typename decltype(l)::type::P{w, g, t, C, Ks, wplane}; };
+    if constexpr (FMT::PLANES) rc = launch_gemm_pw<CONV_DGRAD, DmaConvDgradS2KC, DmaConvFilterS2MC>(mka, mkb, e2, Ms, C, Ks, 1, stream);
+    else rc = launch_gemm<CONV_DGRAD, ConvDgradS2KC, ConvFilterS2MC>(mka, mkb, e2, Ms, C, Ks, 1, stream);
+    if (rc < 0) return rc;
   }
   return CXRK_OK;
 }
@@ -183,6 +156,7 @@ extern "C" size_t cxrk_conv_bwd_data_colsum_ws_bytes(int N, int H, int W, int C,
 extern "C" int cxrk_conv_bn_act_bwd_data(const float* dy, const float* w_scaled, const float* residual,
                                          const float* relu_src, float* dx, int N, int H, int W, int C, int Ko, int R, int S,
                                          int stride, int pad, float* sums, float* ws, size_t ws_bytes, hipStream_t stream) {
+  last_launch = {};
   CXRK_CHECK_ARG(dx);
   EpiParams ep{};
   ep.C = dx; ep.ldc = C; ep.R = residual; ep.ldr = C; ep.alpha = 1.f;
@@ -208,6 +182,7 @@ extern "C" int cxrk_conv_bn_act_bwd_data_pl(const void* dy, long dyplane, const 
                                             long rplane, const unsigned char* maskin, void* dx, long dxplane, int N, int H, int W,
                                             int C, int Ko, int R, int S, int stride, int pad, float* sums, float* ws,
                                             size_t ws_bytes, hipStream_t stream) {
+  last_launch = {};
   return conv_bwd_data_pl_impl(dy, dyplane, w_scaled, wplane, residual, rplane, 0, maskin, dx, dxplane, N, H, W, C, Ko, R, S, stride, pad, sums, ws,
                                ws_bytes, stream);
 }
@@ -218,6 +193,7 @@ extern "C" int cxrk_conv_bn_act_bwd_data_pl_s2res(const void* dy, long dyplane, 
                                                   long rplane, const unsigned char* maskin, void* dx, long dxplane, int N, int H, int W,
                                                   int C, int Ko, int R, int S, int stride, int pad, float* sums, float* ws,
                                                   size_t ws_bytes, hipStream_t stream) {
+  last_launch = {};
   CXRK_CHECK_ARG(residual_s2 && stride == 1);
   // 32-bit byte offsets into the compact tensor (gemm_epilogue.h)
   if ((long)N * ((H + 1) / 2) * ((W + 1) / 2) * C * 2 >= (1L << 31)) return CXRK_ERR_UNSUPPORTED;

@@ -270,6 +270,7 @@ static int launch_conv3x3_halo(const unsigned short* x, long xplane, const typen
   int nslot = halo_cus() / 8; if (nslot < 1) nslot = 1; if (nslot > per_xcd) nslot = per_xcd;
   hipLaunchKernelGGL((conv3x3_halo_kernel<LB, DGRAD>), dim3((unsigned)(8 * nslot)), dim3(768), 0, stream, x, xplane, pb, e, M, N, H, W, nMt);
   CXRK_LAUNCH_CHECK();
+  note_launch({"conv3x3_halo_kernel", DGRAD ? "dgrad" : "fwd", nullptr, nullptr, 0, 0, 1}, (double)M * N * 9 * HALO_CH);
   return 1;
 }
 

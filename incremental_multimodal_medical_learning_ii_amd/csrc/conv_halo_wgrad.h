@@ -299,10 +299,13 @@ static int launch_conv3x3_wgrad_window(const unsigned short* x, long xplane, con
   hipLaunchKernelGGL(conv3x3_wgrad_window_kernel<false>, dim3((unsigned)nfull), dim3(WG_NT), 0, stream, x, xplane, dy, dyplane, slabs, slab_stride,
                      ldc, M, H, W, nKt, tiles, 0);
   CXRK_LAUNCH_CHECK();
+  const LaunchLabel label{"conv3x3_wgrad_window_kernel", nullptr, nullptr, nullptr, 0, 0, 1};
+  note_launch(label, 64.0 * ldc * 32 * tiles * nfull);
   if (splitk > nfull) {
     hipLaunchKernelGGL(conv3x3_wgrad_window_kernel<true>, dim3((unsigned)(3 * (splitk - nfull))), dim3(WG_NT), 0, stream, x, xplane, dy, dyplane,
                        slabs, slab_stride, ldc, M, H, W, nKt, tiles, nfull);
     CXRK_LAUNCH_CHECK();
+    note_launch(label, 64.0 * ldc * 32 * tiles * (splitk - nfull));
   }
   return splitk;
 }

@@ -123,30 +123,12 @@ static int conv_bwd_params_impl(const typename FMT::T* x, long xplane, const typ
   // The stem (fp32 operands, Cpad = 4) follows the process-wide precision like every other contraction: its weight gradient is a
   // cancelling sum over 12.8 M pixels of an all-positive input, and was kept exact fp32 in round 1 for that reason; re-measured
   // in round 2 under imposed max-pool winners (r2k): split-bf16 passes the same 1e-3 gradient parity, 4.0 -> ~2 ms per step.
-  const bool exact = false;
-  if (window) {
-    if constexpr (FMT::PLANES) rc = launch_conv3x3_wgrad_window(x, xplane, dy, dyplane, ws, ep.slab_stride, Nc, Kred, H, W, sk, stream);
-    else return CXRK_ERR_UNSUPPORTED;
-  } else if (use_wide256(Ko, Nc, Kred, sk, FMT::PLANES)) {
-    if constexpr (FMT::PLANES) {
-      DmaDenseMC<256, 8>::P pa{dy, (long)Ko, Ko, Kred, dyplane}; DmaConvIm2colMC<256, 8>::P pb{x, g, Nc, Kred, xplane};
-      rc = launch_gemm_pw<Pw256, DmaDenseMC<256, 8>, DmaConvIm2colMC<256, 8>>(pa, pb, ep, Ko, Nc, Kred, sk, stream);
-    } else return CXRK_ERR_UNSUPPORTED;
-  } else if (Ko <= 64) {
-    if constexpr (FMT::PLANES) {
-      DmaDenseMC<64, 4>::P pa{dy, (long)Ko, Ko, Kred, dyplane}; DmaConvIm2colMC<256, 4>::P pb{x, g, Nc, Kred, xplane};
-      rc = launch_gemm_pw<Pw64x256, DmaDenseMC<64, 4>, DmaConvIm2colMC<256, 4>>(pa, pb, ep, Ko, Nc, Kred, sk, stream);
-    } else {
-      typename DenseMC<64, FMT>::P pa{dy, (long)Ko, Ko, Kred, dyplane}; typename ConvIm2colMC<256, FMT>::P pb{x, g, Nc, Kred, xplane};
-      rc = launch_gemm<DenseMC<64, FMT>, ConvIm2colMC<256, FMT>, 1, 4>(pa, pb, ep, Ko, Nc, Kred, sk, stream, exact);
-    }
-  } else if constexpr (FMT::PLANES) {
-    DmaDenseMC<128, 4>::P pa{dy, (long)Ko, Ko, Kred, dyplane}; DmaConvIm2colMC<128, 4>::P pb{x, g, Nc, Kred, xplane};
-    rc = launch_gemm_pw<Pw128, DmaDenseMC<128, 4>, DmaConvIm2colMC<128, 4>>(pa, pb, ep, Ko, Nc, Kred, sk, stream);
-  } else {
-    typename DenseMC<128, FMT>::P pa{dy, (long)Ko, Ko, Kred, dyplane}; typename ConvIm2colMC<128, FMT>::P pb{x, g, Nc, Kred, xplane};
-    rc = launch_gemm<DenseMC<128, FMT>, ConvIm2colMC<128, FMT>, 2, 2>(pa, pb, ep, Ko, Nc, Kred, sk, stream, exact);
-  }
+  auto mka = [&](auto t) { return typename decltype(t)::type::P{dy, (long)Ko, Ko, Kred, dyplane}; };
+  auto mkb = [&](auto t) { return typename decltype(t)::type::P{x, g, Nc, Kred, xplane}; };
+  if constexpr (FMT::PLANES) {
+    if (window) rc = launch_conv3x3_wgrad_window(x, xplane, dy, dyplane, ws, ep.slab_stride, Nc, Kred, H, W, sk, stream);
+    else rc = launch_gemm_pw<CONV_WGRAD, DmaDenseMC, DmaConvIm2colMC>(mka, mkb, ep, Ko, Nc, Kred, sk, stream);
+  } else rc = launch_gemm<CONV_WGRAD, DenseMC, ConvIm2colMC>(mka, mkb, ep, Ko, Nc, Kred, sk, stream);
   if (rc < 0) return rc;
   const int sg_log2 = rc >= 64 ? 4 : (rc >= 8 ? 2 : 0);  // slab groups per block: 16 / 4 / 1
   const int ny = ceil_div(Nc, 4 * (256 >> sg_log2));
@@ -167,6 +149,7 @@ extern "C" int cxrk_conv_bn_act_bwd_params(const float* x, const float* dy, cons
                                            float* dgamma, float* dbeta, int accumulate, int N, int H, int W, int C,
                                            int Cpad, int Ko, int R, int S, int stride, int pad, float* ws, size_t ws_bytes,
                                            hipStream_t stream) {
+  last_launch = {};
   return conv_bwd_params_impl<F32>(x, 0, dy, 0, w, scale, rstd, rmean, sumdy, dw, dgamma, dbeta, accumulate, N, H, W, C, Cpad, Ko, R, S,
                                    stride, pad, ws, ws_bytes, stream);
 }
@@ -175,6 +158,7 @@ extern "C" int cxrk_conv_bn_act_bwd_params_pl(const void* x, long xplane, const 
                                               float* dw, float* dgamma, float* dbeta, int accumulate, int N, int H, int W, int C,
                                               int Ko, int R, int S, int stride, int pad, float* ws, size_t ws_bytes,
                                               hipStream_t stream) {
+  last_launch = {};
   return conv_bwd_params_impl<PL>(static_cast<const unsigned short*>(x), xplane, static_cast<const unsigned short*>(dy), dyplane, w, scale,
                                   rstd, rmean, sumdy, dw, dgamma, dbeta, accumulate, N, H, W, C, C, Ko, R, S, stride, pad, ws, ws_bytes,
                                   stream);

@@ -1,4 +1,4 @@
-// Shared by gemm_f32.hip / gemm_pl.hip: tile dispatch on the 128x128-class tiles and the split-K slab reduction.
+// Shared by gemm_f32.hip / gemm_pl.hip: the split-K slab reduction.
 #pragma once
 #include "cxrk.h"
 #include "gemm_core.h"
@@ -21,21 +21,6 @@ static __global__ void splitk_reduce_kernel(const float* __restrict__ ws, int ns
 }
 
 
-// Tile dispatch on the 128x128-class tiles (fp32 or planes operands).
-template <class FMT, template <int, class, int> class LAT, template <int, class, int> class LBT>
-static int dense_small(const typename FMT::T* A, long lda, long aplane, const typename FMT::T* B, long ldb, long bplane,
-                       const EpiParams& ep, int M, int N, int K, int splitk, hipStream_t stream) {
-  if (N <= 64) {
-    typename LAT<256, FMT, NTHREADS>::P pa{A, lda, M, K, aplane}; typename LBT<64, FMT, NTHREADS>::P pb{B, ldb, N, K, bplane};
-    return launch_gemm<LAT<256, FMT, NTHREADS>, LBT<64, FMT, NTHREADS>, 4, 1>(pa, pb, ep, M, N, K, splitk, stream);
-  }
-  if (M <= 64) {
-    typename LAT<64, FMT, NTHREADS>::P pa{A, lda, M, K, aplane}; typename LBT<256, FMT, NTHREADS>::P pb{B, ldb, N, K, bplane};
-    return launch_gemm<LAT<64, FMT, NTHREADS>, LBT<256, FMT, NTHREADS>, 1, 4>(pa, pb, ep, M, N, K, splitk, stream);
-  }
-  typename LAT<128, FMT, NTHREADS>::P pa{A, lda, M, K, aplane}; typename LBT<128, FMT, NTHREADS>::P pb{B, ldb, N, K, bplane};
-  return launch_gemm<LAT<128, FMT, NTHREADS>, LBT<128, FMT, NTHREADS>, 2, 2>(pa, pb, ep, M, N, K, splitk, stream);
-}
 static int finish_splitk(int rc, int splitk, int M, int N, float* ws, float* C, long ldc, float alpha, int accumulate,
                          hipStream_t stream) {
   if (rc < 0) return rc;

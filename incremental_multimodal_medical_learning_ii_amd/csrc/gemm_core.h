@@ -517,6 +517,22 @@ static inline bool prep_epilogue(EpiParams& e, int M, int N, int splitk) {
   return true;
 }
 
+// What the last GEMM-family entry point called on this thread launched (cxrk_last_launch_label / _count / _split_bf16, for the
+// host's per-launch timings).  The entry point resets the record, every MFMA launcher notes its launch: a few words, static
+// strings only — the label text is put together when it is asked for.  Of several launches (stride-2 parity classes, the two grids
+// of the window weight gradient) the one with the largest M*N*K names the entry point's work, the first one on ties.
+struct LaunchLabel {
+  const char *kernel, *cfg, *la, *lb;   // kernel<cfg,la,lb,wm,wn>, absent parts null / 0
+  int wm, wn;                           // wave tile of the register-staged kernels
+  int split_bf16;                       // the mainloop runs on the bf16 MFMA (three products per term), not the fp32 one
+};
+struct LaunchRecord { LaunchLabel label; double work; int count; };
+inline thread_local LaunchRecord last_launch{};
+static inline void note_launch(const LaunchLabel& l, double work) {
+  LaunchRecord& r = last_launch;
+  if (r.count++ == 0 || work > r.work) { r.label = l; r.work = work; }
+}
+
 // Host launcher.  splitk > 1 writes plain partial slabs (caller reduces them).
 template <class LA, class LB, int WM, int WN>
 static int launch_gemm(const typename LA::P& pa, const typename LB::P& pb, const EpiParams& ep, int M, int N, int K,
@@ -544,8 +560,10 @@ static int launch_gemm(const typename LA::P& pa, const typename LB::P& pb, const
   else
     hipLaunchKernelGGL((gemm_f32_kernel<LA, LB, WM, WN>), grid, dim3(NTHREADS), 0, stream, pa, pb, e, M, N, K, nMt, nNt, splitk, kchunk);
   CXRK_LAUNCH_CHECK();
+  note_launch({split ? "gemm_x3_kernel" : "gemm_f32_kernel", nullptr, LA::NAME, LB::NAME, WM, WN, split}, (double)M * N * K);
   return splitk;  // >= 1: number of slabs actually written
 }
 
 }  // namespace cxrk
 #include "gemm_pw.h"
+#include "gemm_dispatch.h"

@@ -7,6 +7,7 @@ extern "C" int cxrk_gemm_f32(int transA, int transB, int M, int N, int K, const 
                              long ldb, float* C, long ldc, const float* bias, const float* R, long ldr,
                              const float* aux, long ldaux, int auxmode, float* C2, long ldc2, int act, float alpha,
                              int accumulate, int splitk, float* ws, size_t ws_bytes, hipStream_t stream) {
+  last_launch = {};
   CXRK_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0);
   CXRK_CHECK_ARG(aligned16(A) && aligned16(B) && (lda % 4 == 0) && (ldb % 4 == 0));
   CXRK_CHECK_ARG(transA ? (M % 4 == 0) : (K % 4 == 0));
@@ -28,11 +29,13 @@ extern "C" int cxrk_gemm_f32(int transA, int transB, int M, int N, int K, const 
     ep.C = C; ep.ldc = ldc; ep.bias = bias; ep.aux = aux; ep.ldaux = ldaux; ep.auxmode = auxmode;
     ep.C2 = C2; ep.ldc2 = ldc2; ep.act = act;
   }
+  auto mka = [&](auto t) { return typename decltype(t)::type::P{A, lda, M, K, 0}; };
+  auto mkb = [&](auto t) { return typename decltype(t)::type::P{B, ldb, N, K, 0}; };
   int rc;
-  if (!transA && transB) rc = dense_small<F32, DenseKC, DenseKC>(A, lda, 0, B, ldb, 0, ep, M, N, K, splitk, stream);
-  else if (!transA && !transB) rc = dense_small<F32, DenseKC, DenseMC>(A, lda, 0, B, ldb, 0, ep, M, N, K, splitk, stream);
-  else if (transA && !transB) rc = dense_small<F32, DenseMC, DenseMC>(A, lda, 0, B, ldb, 0, ep, M, N, K, splitk, stream);
-  else rc = dense_small<F32, DenseMC, DenseKC>(A, lda, 0, B, ldb, 0, ep, M, N, K, splitk, stream);
+  if (!transA && transB) rc = launch_gemm<DENSE, DenseKC, DenseKC>(mka, mkb, ep, M, N, K, splitk, stream);
+  else if (!transA && !transB) rc = launch_gemm<DENSE, DenseKC, DenseMC>(mka, mkb, ep, M, N, K, splitk, stream);
+  else if (transA && !transB) rc = launch_gemm<DENSE, DenseMC, DenseMC>(mka, mkb, ep, M, N, K, splitk, stream);
+  else rc = launch_gemm<DENSE, DenseMC, DenseKC>(mka, mkb, ep, M, N, K, splitk, stream);
   return finish_splitk(rc, splitk, M, N, ws, C, ldc, alpha, accumulate, stream);
 }
 

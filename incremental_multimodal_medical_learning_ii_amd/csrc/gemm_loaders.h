@@ -170,6 +170,7 @@ struct DenseKC : KCGeom<TILE, FMT, NT> {
   typedef KCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RP; using G::KQ; using G::LD;
+  static constexpr const char* NAME = "DenseKC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* ptr; long ld; int rows; int K; long plane; };
   const T* bp; long plane; unsigned voff[NVR]; int kq, r0, K;
   __device__ __forceinline__ void init(const P& p, int idx0, int tid) {
@@ -199,6 +200,7 @@ struct DenseMC : MCGeom<TILE, FMT, NT> {
   typedef MCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RPP; using G::VPR; using G::LD; using G::LDT;
+  static constexpr const char* NAME = "DenseMC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* ptr; long ld; int cols; int K; long plane; };
   const T* bp; long ld_, plane; unsigned voff[NVR];
   int cq, kr0, K;
@@ -239,6 +241,7 @@ struct ConvIm2colKC : KCGeom<TILE, FMT, NT> {
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RP; using G::KQ; using G::LD;
   static_assert(TAPWISE || !FMT::PLANES, "the per-lane-tap gather exists for the fp32 stem only");
+  static constexpr const char* NAME = "ConvIm2colKC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* x; ConvGeom g; int rows; int K; long plane; };
   const T* bp; long plane;
   unsigned off[NVR];                // byte offset of (row, tap 0, c = EPL*kq) from bp   [TAPWISE: >= 0 by construction]
@@ -308,6 +311,7 @@ struct ConvDgradKC : KCGeom<TILE, FMT, NT> {
   typedef KCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RP; using G::KQ; using G::LD;
+  static constexpr const char* NAME = "ConvDgradKC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* dy; ConvGeom g; int rows; int K; long plane; };
   const T* bp; long plane; unsigned off[NVR], inv[NVR];
   int kq, r0, Wo, Ko, R, S;
@@ -353,6 +357,7 @@ struct ConvFilterMC : MCGeom<TILE, FMT, NT> {
   typedef MCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RPP; using G::VPR; using G::LD; using G::LDT;
+  static constexpr const char* NAME = "ConvFilterMC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* w; ConvGeom g; int cols; int K; long plane; };
   const T* bp; long plane; unsigned voff[NVR]; int cq, kr0, Ko, C; long RSC;
   int tap, tk, knext;
@@ -390,6 +395,7 @@ struct ConvDgradS2KC : KCGeom<TILE, FMT, NT> {
   typedef KCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RP; using G::KQ; using G::LD;
+  static constexpr const char* NAME = "ConvDgradS2KC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* dy; ConvGeom g; S2Taps t; int Hs, Ws; int rows; int K; long plane; };
   const T* bp; long plane; unsigned off[NVR], inv[NVR];
   int kq, r0, Wo, Ko; S2Taps t;
@@ -439,6 +445,7 @@ struct ConvFilterS2MC : MCGeom<TILE, FMT, NT> {
   typedef MCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RPP; using G::VPR; using G::LD; using G::LDT;
+  static constexpr const char* NAME = "ConvFilterS2MC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* w; ConvGeom g; S2Taps t; int cols; int K; long plane; };
   const T* bp; long plane; unsigned voff[NVR]; int cq, kr0, Ko, C, S; long RSC; S2Taps t;
   int ti, tk, knext;
@@ -480,6 +487,7 @@ struct ConvIm2colMC : MCGeom<TILE, FMT, NT> {
   typedef MCGeom<TILE, FMT, NT> G;
   typedef typename FMT::T T; typedef typename FMT::V V;
   using G::NV; using G::NVR; using G::RPP; using G::VPR; using G::LD; using G::LDT;
+  static constexpr const char* NAME = "ConvIm2colMC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const T* x; ConvGeom g; int cols; int K; long plane; };
   const T* x; long plane; int cq, kr0, K, H, W, C, Ho, Wo, st, dh, dw, cc, bias; bool ok;
   bool linear, halo;

@@ -172,10 +172,26 @@ extern "C" int cxrk_gemm_wgrad_splitk(int M, int N, int K, int planes) { return 
 
 // 1 when a launch of this shape on planes operands takes the 256x256 kernel.  kind: 0 / 3 = dense layer or weight gradient
 // (3 = with a fused epilogue; same policy), 1 = convolution forward, 2 = convolution data gradient.
-// (Reporting only: lets the host label its launch timings by mainloop.)
+// (Reporting only: the policy's answer for a shape, without a launch.)
 extern "C" int cxrk_gemm_wide_tile(int M, int N, long K, int splitk, int kind) {
-  return use_wide256(M, N, K, splitk, true, kind == 1 ? WIDE_MINK_FPROP : (kind == 2 ? WIDE_MINK_DGRAD : WIDE_MINK_PLAIN));
+  return pick_tile(kind == 1 ? CONV_FPROP : (kind == 2 ? CONV_DGRAD : DENSE), M, N, K, splitk, true) == TILE_256;
 }
+
+// What the last GEMM-family entry point called on this thread launched (LaunchRecord, gemm_core.h).  The label is the kernel
+// instantiation as scripts/pmc_summary_key.py abbreviates rocprofv3's name; "" when nothing was launched.
+extern "C" const char* cxrk_last_launch_label(void) {
+  static thread_local char buf[128];
+  const LaunchLabel& l = last_launch.label;
+  int n = snprintf(buf, sizeof buf, "%s", last_launch.count ? l.kernel : "");
+  const char* sep = "<";
+  for (const char* part : {l.cfg, l.la, l.lb})
+    if (part) { n += snprintf(buf + n, sizeof buf - n, "%s%s", sep, part); sep = ","; }
+  if (l.wm) n += snprintf(buf + n, sizeof buf - n, ",%d,%d", l.wm, l.wn);
+  if (sep[0] == ',') snprintf(buf + n, sizeof buf - n, ">");
+  return buf;
+}
+extern "C" int cxrk_last_launch_count(void) { return last_launch.count; }
+extern "C" int cxrk_last_launch_split_bf16(void) { return last_launch.label.split_bf16; }
 
 extern "C" size_t cxrk_gemm_splitk_ws_bytes(int M, int N, int splitk) {
   return splitk > 1 ? (size_t)splitk * (size_t)M * (size_t)N * sizeof(float) : 0;

@@ -4,30 +4,6 @@
 
 using namespace cxrk;
 
-template <template <int, int> class DLA, template <int, int> class DLB>
-static int dense_planes(const unsigned short* A, long lda, long aplane, const unsigned short* B, long ldb, long bplane, const EpiParams& ep,
-                        int M, int N, int K, int splitk, hipStream_t stream) {
-  if (use_wide256(M, N, K, splitk, true)) {
-    typename DLA<256, 8>::P pa{A, lda, M, K, aplane}; typename DLB<256, 8>::P pb{B, ldb, N, K, bplane};
-    return launch_gemm_pw<Pw256, DLA<256, 8>, DLB<256, 8>>(pa, pb, ep, M, N, K, splitk, stream);
-  }
-  if (N <= 64) {
-    typename DLA<256, 4>::P pa{A, lda, M, K, aplane}; typename DLB<64, 4>::P pb{B, ldb, N, K, bplane};
-    return launch_gemm_pw<Pw256x64, DLA<256, 4>, DLB<64, 4>>(pa, pb, ep, M, N, K, splitk, stream);
-  }
-  if (M <= 64) {
-    typename DLA<64, 4>::P pa{A, lda, M, K, aplane}; typename DLB<256, 4>::P pb{B, ldb, N, K, bplane};
-    return launch_gemm_pw<Pw64x256, DLA<64, 4>, DLB<256, 4>>(pa, pb, ep, M, N, K, splitk, stream);
-  }
-  typename DLA<128, 4>::P pa{A, lda, M, K, aplane}; typename DLB<128, 4>::P pb{B, ldb, N, K, bplane};
-  return launch_gemm_pw<Pw128, DLA<128, 4>, DLB<128, 4>>(pa, pb, ep, M, N, K, splitk, stream);
-}
-
-// Row tile the dispatch above uses (the fused column sums come as one partial row per 64 output rows of the padded row tiling).
-static int dense_planes_row_tile(int M, int N, int K, int splitk) {
-  if (use_wide256(M, N, K, splitk, true) || N <= 64) return 256;
-  return M <= 64 ? 64 : 128;
-}
 extern "C" size_t cxrk_gemm_pl_colsum_ws_bytes(int M, int N) { return (size_t)(ceil_div(M, 64) + 4) * N * sizeof(float); }
 
 namespace {
@@ -62,6 +38,7 @@ extern "C" int cxrk_gemm_pl(int transA, int transB, int M, int N, int K, const v
                             const unsigned char* maskin, long ldmaskin, unsigned char* maskout, long ldmaskout, float* C2,
                             long ldc2, int act, float alpha, int accumulate, int splitk, float* colsum, int colsum_accumulate,
                             float* ws, size_t ws_bytes, hipStream_t stream) {
+  last_launch = {};
   CXRK_CHECK_ARG(A && B && (C || Cp) && M > 0 && N > 0 && K > 0);
   CXRK_CHECK_ARG(aligned16(A) && aligned16(B) && (lda % 8 == 0) && (ldb % 8 == 0) && (aplane % 8 == 0) && (bplane % 8 == 0));
   CXRK_CHECK_ARG(transA ? (M % 8 == 0) : (K % 8 == 0));
@@ -91,14 +68,15 @@ extern "C" int cxrk_gemm_pl(int transA, int transB, int M, int N, int K, const v
   }
   const unsigned short* Ap = static_cast<const unsigned short*>(A);
   const unsigned short* Bp = static_cast<const unsigned short*>(B);
+  auto mka = [&](auto t) { return typename decltype(t)::type::P{Ap, lda, M, K, aplane}; };
+  auto mkb = [&](auto t) { return typename decltype(t)::type::P{Bp, ldb, N, K, bplane}; };
   int rc;
-  if (!transA && transB) rc = dense_planes<DmaDenseKC, DmaDenseKC>(Ap, lda, aplane, Bp, ldb, bplane, ep, M, N, K, splitk, stream);
-  else if (!transA && !transB) rc = dense_planes<DmaDenseKC, DmaDenseMC>(Ap, lda, aplane, Bp, ldb, bplane, ep, M, N, K, splitk, stream);
-  else rc = dense_planes<DmaDenseMC, DmaDenseMC>(Ap, lda, aplane, Bp, ldb, bplane, ep, M, N, K, splitk, stream);
+  if (!transA && transB) rc = launch_gemm_pw<DENSE, DmaDenseKC, DmaDenseKC>(mka, mkb, ep, M, N, K, splitk, stream);
+  else if (!transA && !transB) rc = launch_gemm_pw<DENSE, DmaDenseKC, DmaDenseMC>(mka, mkb, ep, M, N, K, splitk, stream);
+  else rc = launch_gemm_pw<DENSE, DmaDenseMC, DmaDenseMC>(mka, mkb, ep, M, N, K, splitk, stream);
   if (colsum) {
     if (rc < 0) return rc;
-    const int tm = dense_planes_row_tile(M, N, K, splitk);
-    const int nparts = ceil_div(M, tm) * (tm / 64);
+    const int nparts = colsum_slabs(pick_tile(DENSE, M, N, K, splitk, true), M);   // one partial row per 64 rows of the launch's padded row tiling
     hipLaunchKernelGGL(colsum_parts_kernel, dim3(ceil_div(N, 64)), dim3(1024), 0, stream, ws, nparts, N, colsum, colsum_accumulate);
     CXRK_LAUNCH_CHECK();
     return CXRK_OK;

@@ -76,6 +76,7 @@ template <int TILE, int NW>
 struct DmaDenseKC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = true;
+  static constexpr const char* NAME = "DmaDenseKC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* ptr; long ld; int rows; int K; long plane; };
   const unsigned short* bp; long plane; static constexpr int RW = TILE / NW, NP = RW / 16;
   unsigned voff[NP]; int kq8, K, wave;
@@ -109,6 +110,7 @@ template <int TILE, int NW>
 struct DmaDenseMC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = false;
+  static constexpr const char* NAME = "DmaDenseMC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* ptr; long ld; int cols; int K; long plane; };
   static constexpr int RB = 2 * TILE, KPP = 1024 / RB, LPR = RB / 16, NP = 32 / KPP / NW;
   static_assert(NP >= 1, "tile too small for this wave count");
@@ -145,6 +147,7 @@ template <int TILE, int NW>
 struct DmaConvIm2colKC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = true;
+  static constexpr const char* NAME = "DmaConvIm2colKC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* x; ConvGeom g; int rows; int K; long plane; };
   const unsigned short* bp; long plane; static constexpr int RW = TILE / NW, NP = RW / 16;
   unsigned off[NP], inv[NP]; int kq8, W, C, S, wave;
@@ -190,6 +193,7 @@ template <int TILE, int NW>
 struct DmaConvDgradKC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = true;
+  static constexpr const char* NAME = "DmaConvDgradKC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* dy; ConvGeom g; int rows; int K; long plane; };
   const unsigned short* bp; long plane; static constexpr int RW = TILE / NW, NP = RW / 16;
   unsigned off[NP], inv[NP]; int kq8, Wo, Ko, R, S, wave;
@@ -232,6 +236,7 @@ template <int TILE, int NW>
 struct DmaConvDgradS2KC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = true;
+  static constexpr const char* NAME = "DmaConvDgradS2KC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* dy; ConvGeom g; S2Taps t; int Hs, Ws; int rows; int K; long plane; };
   const unsigned short* bp; long plane; static constexpr int RW = TILE / NW, NP = RW / 16;
   unsigned off[NP], inv[NP]; int kq8, Wo, Ko, wave; S2Taps t;
@@ -284,6 +289,7 @@ template <int TILE, int NW>
 struct DmaConvFilterMC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = false;
+  static constexpr const char* NAME = "DmaConvFilterMC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* w; ConvGeom g; int cols; int K; long plane; };
   static constexpr int RB = 2 * TILE, KPP = 1024 / RB, LPR = RB / 16, NP = 32 / KPP / NW;
   const unsigned short* bp; long plane, RSC; unsigned voff[NP]; int Ko, C, wave;
@@ -318,6 +324,7 @@ template <int TILE, int NW>
 struct DmaConvFilterS2MC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = false;
+  static constexpr const char* NAME = "DmaConvFilterS2MC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* w; ConvGeom g; S2Taps t; int cols; int K; long plane; };
   static constexpr int RB = 2 * TILE, KPP = 1024 / RB, LPR = RB / 16, NP = 32 / KPP / NW;
   const unsigned short* bp; long plane, RSC; unsigned voff[NP]; int Ko, C, S, wave; S2Taps t;
@@ -355,6 +362,7 @@ template <int TILE, int NW>
 struct DmaConvIm2colMC {
   static constexpr int PLANEB = pw_plane_bytes<TILE>();
   static constexpr bool KC = false;
+  static constexpr const char* NAME = "DmaConvIm2colMC";   // launch labels (LaunchRecord, gemm_core.h)
   struct P { const unsigned short* x; ConvGeom g; int cols; int K; long plane; };
   static constexpr int RB = 2 * TILE, KPP = 1024 / RB, LPR = RB / 16, NP = 32 / KPP / NW;
   const unsigned short* x; long plane; int K, H, W, C, Ho, Wo, st, bias, wave; bool linear, halo;
@@ -449,6 +457,7 @@ struct PwCfg {
   static constexpr int WGM = WGM_, WGN = WGN_, WTM = WTM_, WTN = 2;
   static constexpr int NW = WGM * WGN, NT = 64 * NW;
   static constexpr int TM = WGM * WTM * 32, TN = WGN * WTN * 32;
+  static constexpr const char* NAME = TM == 256 ? (TN == 256 ? "Pw256" : "Pw256x64") : (TN == 256 ? "Pw64x256" : "Pw128");   // the typedefs below
   static constexpr int PLANE_A = pw_plane_bytes<TM>(), PLANE_B = pw_plane_bytes<TN>();
   static constexpr int STAGE = 2 * (PLANE_A + PLANE_B);        // A hi | A lo | B hi | B lo
   static constexpr int BLOCKS_PER_CU = (2 * STAGE <= 80 * 1024 && NW <= 4) ? 2 : 1;
@@ -635,6 +644,7 @@ static int launch_gemm_pw(const typename LA::P& pa, const typename LB::P& pb, co
   if (!prep_epilogue(e, M, N, splitk) || !e.fast) return CXRK_ERR_ARG;
   hipLaunchKernelGGL((gemm_pw_kernel<CFG, LA, LB>), grid, dim3(CFG::NT), 0, stream, pa, pb, e, M, N, K, nMt, nNt, splitk, kchunk);
   CXRK_LAUNCH_CHECK();
+  note_launch({"gemm_pw_kernel", CFG::NAME, LA::NAME, LB::NAME, 0, 0, 1}, (double)M * N * K);
   return splitk;
 }
 

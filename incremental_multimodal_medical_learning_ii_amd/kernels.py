@@ -6,7 +6,6 @@ falls back to torch arithmetic.
 """
 from __future__ import annotations
 
-import os
 from typing import NamedTuple, Optional, Tuple
 
 import torch
@@ -135,15 +134,17 @@ def _pl2d(t: Planes, name: str):
 
 class LaunchProfiler:
     """Optional per-launch timing of the MFMA GEMM family with HIP events recorded on the launch stream
-    (bench.py's `roofline` object).  Off by default; when on, every GEMM / implicit-GEMM launch is bracketed by two
-    events and tagged with its kernel instantiation (the name rocprofv3 reports, scripts/pmc_summary_key.py), its algorithmic
-    FLOPs (2*M*N*K) and its algorithmic HBM bytes (every operand and side input read once, every output written once)."""
+    (bench.py's `roofline` object).  Off by default; when on, every GEMM / implicit-GEMM entry point is bracketed by two
+    events and tagged with its algorithmic FLOPs (2*M*N*K), its algorithmic HBM bytes (every operand and side input read once,
+    every output written once) and what the library says it launched (`cxrk_last_launch_label` / `_count` / `_split_bf16`): the
+    kernel instantiation under the name rocprofv3 reports (scripts/pmc_summary_key.py), the number of MFMA launches, and the
+    mainloop's number format.  Tile choice and kernel names exist in the library only (csrc/gemm_dispatch.h)."""
 
     PEAK_BF16X3, PEAK_F32, PEAK_HBM = 2500e12 / 3.0, 157.3e12, 8.0e12   # /opt/skills/guides/MI355X_MICROARCH.md (bench.py's constants)
 
     def __init__(self):
         self.on = False
-        self.rows = []  # (key, flops, bytes, start_event, end_event, kernel launches inside the bracket)
+        self.rows = []  # [key, flops, bytes, start_event, end_event, MFMA launches inside the bracket, split-bf16 mainloop]
 
     def start(self):
         self.on, self.rows = True, []
@@ -151,54 +152,39 @@ class LaunchProfiler:
     def stop(self):
         self.on = False
 
-    def bracket(self, key: str, flops: float, nbytes: float = 0.0, sub: int = 1):
-        """`sub`: kernel launches inside the bracket (a stride-2 data gradient is one launch per output-parity class)"""
+    def bracket(self, flops: float, nbytes: float = 0.0):
+        """Opens a row in front of a library call; `end` closes it.  None when the profiler is off."""
         if not self.on:
             return None
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        self.rows.append((key, flops, nbytes, a, b, sub))
-        return b
+        row = [None, flops, nbytes, a, b, 0, False]
+        self.rows.append(row)
+        return row
+
+    def end(self, row):
+        """Behind the library call, on the thread that made it (the library's launch record is per thread)."""
+        if row is None:
+            return
+        row[4].record()
+        lib = _lib.load()
+        row[0], row[5], row[6] = lib.cxrk_last_launch_label().decode(), lib.cxrk_last_launch_count(), bool(lib.cxrk_last_launch_split_bf16())
 
     def summary(self):
         """{kernel: {"launches", "flops", "bytes", "ms"}} — call after torch.cuda.synchronize()."""
         out = {}
-        for key, flops, nbytes, a, b, sub in self.rows:
+        for key, flops, nbytes, a, b, sub, split in self.rows:
             d = out.setdefault(key, {"launches": 0, "flops": 0.0, "bytes": 0.0, "ms": 0.0, "floor_ms": 0.0})
             d["launches"] += sub
             d["flops"] += flops
             d["bytes"] += nbytes
             d["ms"] += a.elapsed_time(b)
             # the launch's own binding roof: max(FLOPs / MFMA peak of its mainloop, algorithmic bytes / HBM peak)
-            peak = self.PEAK_BF16X3 if (key.startswith("gemm_pw") or key.startswith("gemm_x3")) else self.PEAK_F32
-            d["floor_ms"] += 1e3 * max(flops / peak, nbytes / self.PEAK_HBM)
+            d["floor_ms"] += 1e3 * max(flops / (self.PEAK_BF16X3 if split else self.PEAK_F32), nbytes / self.PEAK_HBM)
         return out
 
 
 profiler = LaunchProfiler()
-
-
-def _tile(M: int, N: int) -> str:
-    return "4,1" if N <= 64 else ("1,4" if M <= 64 else "2,2")
-
-
-def _kern(flops: float, exact: bool = False) -> str:
-    """Name of the mainloop a launch runs (mirrors launch_gemm's policy in csrc/gemm_core.h)."""
-    split = _lib.get_precision() == "split_bf16" and not exact and flops >= 1073741824.0
-    return "gemm_x3_kernel" if split else "gemm_f32_kernel"
-
-
-def _label(la: str, lb: str, tile: str, M: int, N: int, K: int, splitk: int, kind: int, exact: bool = False,
-           planes: bool = False) -> str:
-    """Profiler key of a launch: mainloop<A loader,B loader,tile>.  Planes operands take the LDS-DMA pipelined kernel: 256x256
-    tiles when the library's policy picks them, 256x64 / 64x256 (two blocks per CU) where the output has <= 64 columns / rows,
-    128x128 (two blocks per CU) otherwise."""
-    if planes:
-        if _lib.load().cxrk_gemm_wide_tile(M, N, K, splitk, kind):
-            return f"gemm_pw_kernel<Pw256,Dma{la},Dma{lb}>"
-        cfg = {"2,2": "Pw128", "4,1": "Pw256x64", "1,4": "Pw64x256"}[tile]
-        return f"gemm_pw_kernel<{cfg},Dma{la},Dma{lb}>"
-    return f"{_kern(2.0 * M * N * K, exact)}<{la},{lb},{tile}>"
 
 
 class _Workspace:
@@ -257,16 +243,13 @@ def gemm(a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, M: int, N: int, K:
         wsb = lib.cxrk_gemm_splitk_ws_bytes(M, N, splitk)
         ws = workspace(wsb, out.device)
         wsb = ws.numel() * 4
-    plain = bias is None and residual is None and aux is None and preact_out is None and act == 0
-    ev = profiler.bracket(_label(f"Dense{'MC' if trans_a else 'KC'}", f"Dense{'KC' if trans_b else 'MC'}", _tile(M, N), M, N, K, splitk,
-                                 0 if (plain or splitk > 1) else 3), 2.0 * M * N * K,
+    ev = profiler.bracket(2.0 * M * N * K,
                           4.0 * (M * K + N * K + M * N * (1 + (residual is not None) + (aux is not None) + (preact_out is not None)
                                                        + int(bool(accumulate))))) if profiler.on else None
     rc = lib.cxrk_gemm_f32(int(trans_a), int(trans_b), M, N, K, _p(a), lda, _p(b), ldb, _p(out), ldc, _p(bias),
                            _p(residual), ldr, _p(aux), ldaux, auxmode, _p(preact_out), ldc2, act, float(alpha),
                            int(accumulate), int(splitk), _p(ws), wsb, _stream())
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
     check(rc, f"cxrk_gemm_f32(M={M},N={N},K={K},tA={trans_a},tB={trans_b})")
     return out
 
@@ -361,16 +344,13 @@ def gemm_pl(a: Planes, b: Planes, M: int, N: int, K: int, trans_a: bool, trans_b
         wsb = ws.numel() * 4
     if colsum is not None and splitk > 1:
         raise ValueError("gemm_pl: fused column sums need splitk == 1")
-    plain = bias is None and residual is None and aux is None and maskin is None and preact_out is None and act == 0
-    ev = profiler.bracket(_label(f"Dense{'MC' if trans_a else 'KC'}", f"Dense{'KC' if trans_b else 'MC'}", _tile(M, N), M, N, K, splitk,
-                                 0 if (plain or splitk > 1) else 3, planes=True), 2.0 * M * N * K,
+    ev = profiler.bracket(2.0 * M * N * K,
                           4.0 * (M * K + N * K + M * N * (1 + (residual is not None) + (aux is not None) + (preact_out is not None)
                                                        + int(bool(accumulate)))) + M * N / 8.0 * ((maskin is not None) + (maskout is not None))) if profiler.on else None
     rc = lib.cxrk_gemm_pl(int(trans_a), int(trans_b), M, N, K, ap, lda, apl, bp, ldb, bpl, C, Cp, ldc, cpl, _p(bias), R, Rp, ldr, rpl,
                           _p(aux), ldaux, auxmode, _p(maskin), ldmi, _p(maskout), ldmo, _p(preact_out), ldc2, act, float(alpha),
                           int(accumulate), int(splitk), _p(colsum), int(colsum_accumulate), _p(ws), wsb, _stream())
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
     check(rc, f"cxrk_gemm_pl(M={M},N={N},K={K},tA={trans_a},tB={trans_b})")
     return out
 
@@ -589,29 +569,16 @@ def conv_fwd(x, w_scaled, shift, residual, y, N, H, W, C, Ko, R, S, stride, pad,
     if profiler.on:
         Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
         fl = 2.0 * N * Ho * Wo * Ko * R * S * C
-        ev = profiler.bracket(_label("ConvIm2colKC", "DenseKC", "4,1" if Ko <= 64 else "2,2", N * Ho * Wo, Ko, R * S * C, 1,
-                                     1 if C % 32 == 0 else 3), fl,
-                              4.0 * (N * H * W * C + Ko * R * S * C + N * Ho * Wo * Ko * (1 + (residual is not None))))
+        ev = profiler.bracket(fl, 4.0 * (N * H * W * C + Ko * R * S * C + N * Ho * Wo * Ko * (1 + (residual is not None))))
     rc = lib.cxrk_conv_bn_act_fwd(_p(_chk(x, "conv.x")), _p(w_scaled), _p(shift), _p(residual), _p(y), N, H, W, C, Ko,
                                   R, S, stride, pad, int(relu), _stream())
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
     check(rc, f"cxrk_conv_bn_act_fwd(N={N},H={H},W={W},C={C},Ko={Ko},R={R},s={stride})")
     return y
 
 
 def _conv_out(H, W, R, S, stride, pad):
     return (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
-
-
-def _dgrad_label(N, H, W, Ko, R, S, stride):
-    """(A loader, B loader, GEMM rows, GEMM K, kernel launches) of a data gradient as the library runs it: stride 1 = one launch over
-    all pixels; stride 2 = one launch per output-parity class that a tap reaches (4 for a 3x3, 1 for a 1x1), each over a quarter of the
-    pixels with that class's taps (csrc/conv_dgrad.hip) — a different kernel instantiation, labelled as such."""
-    if stride == 1:
-        return "ConvDgradKC", "ConvFilterMC", N * H * W, R * S * Ko, 1
-    classes = 4 if R > 1 else 1
-    return "ConvDgradS2KC", "ConvFilterS2MC", N * ((H + 1) // 2) * ((W + 1) // 2), Ko * max(1, (R * S) // 4), classes
 
 
 def conv_bwd_data(dy, w_scaled, residual, relu_src, dx, N, H, W, C, Ko, R, S, stride, pad, sums=None):
@@ -623,13 +590,10 @@ def conv_bwd_data(dy, w_scaled, residual, relu_src, dx, N, H, W, C, Ko, R, S, st
     if profiler.on:  # algorithmic FLOPs of a data gradient = those of the forward conv (stride-2 zero taps are waste)
         Ho, Wo = _conv_out(H, W, R, S, stride, pad)
         fl = 2.0 * N * Ho * Wo * Ko * R * S * C
-        la, lb, Ml, Kl, sub = _dgrad_label(N, H, W, Ko, R, S, stride)
-        ev = profiler.bracket(_label(la, lb, "4,1" if C <= 64 else "2,2", Ml, C, Kl, 1, 2), fl,
-                              4.0 * (N * Ho * Wo * Ko + Ko * R * S * C + N * H * W * C * (1 + (residual is not None) + (relu_src is not None))), sub)
+        ev = profiler.bracket(fl, 4.0 * (N * Ho * Wo * Ko + Ko * R * S * C + N * H * W * C * (1 + (residual is not None) + (relu_src is not None))))
     rc = lib.cxrk_conv_bn_act_bwd_data(_p(_chk(dy, "conv.dy")), _p(w_scaled), _p(residual), _p(relu_src), _p(dx), N, H,
                                        W, C, Ko, R, S, stride, pad, _p(sums), _p(ws), ws.numel() * 4 if ws is not None else 0, _stream())
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
     check(rc, f"cxrk_conv_bn_act_bwd_data(N={N},H={H},W={W},C={C},Ko={Ko},R={R},s={stride})")
     return dx
 
@@ -643,15 +607,12 @@ def conv_bwd_params(x, dy, w, scale, rstd, rmean, sumdy, dw, dgamma, dbeta, accu
     if profiler.on:
         Ho, Wo = _conv_out(H, W, R, S, stride, pad)
         fl = 2.0 * N * Ho * Wo * Ko * R * S * Cpad
-        sk = lib.cxrk_gemm_wgrad_splitk(Ko, R * S * Cpad, N * Ho * Wo, 0)
-        ev = profiler.bracket(_label("DenseMC", "ConvIm2colMC", "1,4" if Ko <= 64 else "2,2", Ko, R * S * Cpad, N * Ho * Wo, sk, 0,
-                                     False), fl, 4.0 * (N * H * W * Cpad + N * Ho * Wo * Ko + Ko * R * S * Cpad))
+        ev = profiler.bracket(fl, 4.0 * (N * H * W * Cpad + N * Ho * Wo * Ko + Ko * R * S * Cpad))
     check(lib.cxrk_conv_bn_act_bwd_params(_p(_chk(x, "conv.x")), _p(_chk(dy, "conv.dy")), _p(w), _p(scale), _p(rstd),
                                           _p(rmean), _p(sumdy), _p(dw), _p(dgamma), _p(dbeta), int(accumulate), N, H, W,
                                           C, Cpad, Ko, R, S, stride, pad, _p(ws), ws.numel() * 4, _stream()),
           f"cxrk_conv_bn_act_bwd_params(N={N},H={H},W={W},C={C},Ko={Ko},R={R},s={stride})")
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
 
 
 # ---- planes storage (split-bf16 mode of the image encoder) -------------------------------------------------------------------
@@ -675,11 +636,7 @@ def conv_fwd_pl(x, w_scaled, shift, residual: Optional[Planes], y: Planes, masko
         Ho, Wo = _conv_out(H, W, R, S, stride, pad)
         fl = 2.0 * N * Ho * Wo * Ko * R * S * C
         nb = 4.0 * (N * H * W * C + Ko * R * S * C + N * Ho * Wo * Ko * (1 + (residual is not None))) + (N * Ho * Wo * Ko / 8.0 if maskout is not None else 0.0)
-        if in_planes:
-            key = _label("ConvIm2colKC", "DenseKC", "4,1" if Ko <= 64 else "2,2", N * Ho * Wo, Ko, R * S * C, 1, 1, planes=True)
-        else:
-            key = _label("ConvIm2colKC", "DenseKC", "4,1" if Ko <= 64 else "2,2", N * Ho * Wo, Ko, R * S * C, 1, 3)
-        ev = profiler.bracket(key, fl, nb)
+        ev = profiler.bracket(fl, nb)
     if maskout is not None:
         _chk(maskout, "conv.maskout", torch.uint8)
     xp, xpl = (x.ptr(), x.plane) if in_planes else (_p(_chk(x, "conv.x")), 0)
@@ -687,8 +644,7 @@ def conv_fwd_pl(x, w_scaled, shift, residual: Optional[Planes], y: Planes, masko
     rc = lib.cxrk_conv_bn_act_fwd_pl(xp, xpl, wp, wpl, int(in_planes), _p(shift), residual.ptr() if residual is not None else None,
                                      residual.plane if residual is not None else 0, y.ptr(), y.plane, _p(maskout), N, H, W, C, Ko, R, S,
                                      stride, pad, int(relu), _stream())
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
     check(rc, f"cxrk_conv_bn_act_fwd_pl(N={N},H={H},W={W},C={C},Ko={Ko},R={R},s={stride})")
     return y
 
@@ -707,16 +663,13 @@ def conv_bwd_data_pl(dy: Planes, w_scaled: Planes, residual: Optional[Planes], m
     if profiler.on:
         Ho, Wo = _conv_out(H, W, R, S, stride, pad)
         fl = 2.0 * N * Ho * Wo * Ko * R * S * C
-        la, lb, Ml, Kl, sub = _dgrad_label(N, H, W, Ko, R, S, stride)
-        ev = profiler.bracket(_label(la, lb, "4,1" if C <= 64 else "2,2", Ml, C, Kl, 1, 2, planes=True), fl,
-                              4.0 * (N * Ho * Wo * Ko + Ko * R * S * C + N * H * W * C * (1 + (0.0 if residual is None else 0.25 if residual_s2 else 1.0)))
-                              + (N * H * W * C / 8.0 if maskin is not None else 0.0), sub)
+        ev = profiler.bracket(fl, 4.0 * (N * Ho * Wo * Ko + Ko * R * S * C + N * H * W * C * (1 + (0.0 if residual is None else 0.25 if residual_s2 else 1.0)))
+                              + (N * H * W * C / 8.0 if maskin is not None else 0.0))
     fn = lib.cxrk_conv_bn_act_bwd_data_pl_s2res if residual_s2 else lib.cxrk_conv_bn_act_bwd_data_pl
     rc = fn(dy.ptr(), dy.plane, w_scaled.ptr(), w_scaled.plane, residual.ptr() if residual is not None else None,
                                           residual.plane if residual is not None else 0, _p(maskin), dx.ptr(), dx.plane, N, H, W, C, Ko, R, S,
                                           stride, pad, _p(sums), _p(ws), ws.numel() * 4 if ws is not None else 0, _stream())
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
     check(rc, f"cxrk_conv_bn_act_bwd_data_pl{'_s2res' if residual_s2 else ''}(N={N},H={H},W={W},C={C},Ko={Ko},R={R},s={stride})")
     return dx
 
@@ -736,19 +689,6 @@ def conv1x1_s2_bwd_data_compact_pl(dy: Planes, w_scaled: Planes, N, H, W, C, Ko)
     return out.view(N, Ho, Wo, C)
 
 
-def _wgrad_window_takes(H, W, C, Ko, R, S, stride, pad) -> bool:
-    """Mirror of the library's dispatch (csrc/conv_wgrad.hip): the window-resident weight-gradient kernel takes the planes 3x3 /
-    stride 1 / pad 1 layers with 64 -> 64 channels and rows of <= 58 pixels unless CXRK_HALO=0 or CXRK_HALO_WGRAD=0."""
-    def off(name):
-        v = os.environ.get(name)
-        try:
-            return v is not None and int(v) == 0
-        except ValueError:
-            return True      # atoi() of a non-number is 0
-    return (R == 3 and S == 3 and stride == 1 and pad == 1 and C == 64 and Ko == 64 and 1 <= W <= 58 and H >= 1
-            and not off("CXRK_HALO") and not off("CXRK_HALO_WGRAD"))
-
-
 def conv_bwd_params_pl(x: Planes, dy: Planes, w, scale, rstd, rmean, sumdy, dw, dgamma, dbeta, accumulate, N, H, W, C, Ko, R, S, stride, pad):
     lib = _lib.load()
     ws = workspace(lib.cxrk_conv_wgrad_ws_bytes(N, H, W, C, Ko, R, S, stride, pad), x.device)
@@ -756,18 +696,12 @@ def conv_bwd_params_pl(x: Planes, dy: Planes, w, scale, rstd, rmean, sumdy, dw, 
     if profiler.on:
         Ho, Wo = _conv_out(H, W, R, S, stride, pad)
         fl = 2.0 * N * Ho * Wo * Ko * R * S * C
-        sk = lib.cxrk_gemm_wgrad_splitk(Ko, R * S * C, N * Ho * Wo, 1)
-        if _wgrad_window_takes(H, W, C, Ko, R, S, stride, pad):
-            label = "conv3x3_wgrad_window_kernel"
-        else:
-            label = _label("DenseMC", "ConvIm2colMC", "1,4" if Ko <= 64 else "2,2", Ko, R * S * C, N * Ho * Wo, sk, 0, planes=True)
-        ev = profiler.bracket(label, fl, 4.0 * (N * H * W * C + N * Ho * Wo * Ko + Ko * R * S * C))
+        ev = profiler.bracket(fl, 4.0 * (N * H * W * C + N * Ho * Wo * Ko + Ko * R * S * C))
     check(lib.cxrk_conv_bn_act_bwd_params_pl(x.ptr(), x.plane, dy.ptr(), dy.plane, _p(w), _p(scale), _p(rstd), _p(rmean), _p(sumdy),
                                              _p(dw), _p(dgamma), _p(dbeta), int(accumulate), N, H, W, C, Ko, R, S, stride, pad, _p(ws),
                                              ws.numel() * 4, _stream()),
           f"cxrk_conv_bn_act_bwd_params_pl(N={N},H={H},W={W},C={C},Ko={Ko},R={R},s={stride})")
-    if ev is not None:
-        ev.record()
+    profiler.end(ev)
 
 
 def maxpool_fwd_pl(x: Planes):

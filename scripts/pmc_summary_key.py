@@ -1,10 +1,14 @@
-"""rocprofv3 kernel name -> bench.py launch label (shared by pmc_summary.py and pmc_sq_summary.py)."""
+"""rocprofv3 kernel name -> the library's launch label (cxrk_last_launch_label, the keys of bench.py's roofline table); shared by
+pmc_summary.py and pmc_sq_summary.py."""
 import re
 
 
 def key(k):
-    if "conv3x3_wgrad_window_kernel" in k:      # csrc/conv_halo_wgrad.h; the label of kernels.conv_bwd_params_pl for its shapes
+    if "conv3x3_wgrad_window_kernel" in k:      # csrc/conv_halo_wgrad.h
         return "conv3x3_wgrad_window_kernel"
+    m = re.search(r"conv3x3_halo_kernel<.*,\s*(?:\(bool\))?(true|false|1|0)\s*>", k)   # csrc/conv_halo.h: <filter loader, DGRAD>
+    if m:
+        return f"conv3x3_halo_kernel<{'dgrad' if m.group(1) in ('true', '1') else 'fwd'}>"
     m = re.search(r"gemm_pw_kernel<cxrk::PwCfg<(\d), (\d), (\d)>, cxrk::(\w+)<[^>]*>, cxrk::(\w+)<[^>]*>\s*>", k)
     if m:
         cfg = {"244": "Pw256", "222": "Pw128", "412": "Pw256x64", "142": "Pw64x256"}.get(m.group(1) + m.group(2) + m.group(3), "Pw?")

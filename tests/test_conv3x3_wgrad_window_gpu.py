@@ -154,11 +154,14 @@ def test_tap_masks_exact(shape, switch):
 @pytest.mark.parametrize("shape", [(3, 56, 56), (2, 5, 33), (40, 2, 2)])
 def test_both_paths_one_process(shape, switch):
     ref = _case(*shape)["ref"]
+    label = _lib.load().cxrk_last_launch_label
     switch("0")
     gemm = _run(*shape)
+    assert label() == b"gemm_pw_kernel<Pw64x256,DmaDenseMC,DmaConvIm2colMC>"   # the paths are bit-identical: only this tells them apart
     _check(gemm, ref, "implicit GEMM (CXRK_HALO_WGRAD=0)")
     switch("1")
     window = _run(*shape)
+    assert label() == b"conv3x3_wgrad_window_kernel"
     _check(window, ref, "window kernel (CXRK_HALO_WGRAD=1)")
     # the window kernel writes the implicit GEMM's split-K slabs with every element's products added in the same order, and
     # the slab reduction is shared: more than "equal up to summation order", the two paths agree bit for bit
