@@ -393,6 +393,23 @@ int cxrk_bce_posneg_fwd_bwd(const float* cosv, const float* labels, long B, int 
 int cxrk_eval_score(const float* cosv, long B, int C, int pred_diff, float* score, float* pred, hipStream_t stream);
 int cxrk_group_mean_fwd(const float* in, int G, int n, int D, float* out, hipStream_t stream);
 int cxrk_group_mean_bwd(const float* dout, int G, int n, int D, float* din, hipStream_t stream);
+/* retrieval_ranks — image<->text retrieval evaluation over a whole gallery (Recall@K, median / mean rank; not in the reference, the
+ * standard check of a contrastive model) WITHOUT the [N][M] similarity block: 128 x 128 tiles of s(i,j) = sum_k Q[i][k] G[j][k] are
+ * formed and consumed in registers (csrc/retrieval.hip).  Q rows are ldq >= D floats apart, G rows ldg >= D; the padding is never read.
+ *   positives of row i: keys_q == keys_g == NULL: the one column i + diag_off (the data-parallel shard convention of
+ *     cxrk_infonce_row_lse; 0 <= diag_off, diag_off + N <= M); otherwise every column j with keys_g[j] == keys_q[i] (all 64 bits).
+ *   pos[i]     = the largest s(i,j) over the positives (-inf when the row has none);
+ *   greater[i] = the number of non-positive columns with s(i,j) >  pos[i];
+ *   ties[i]    = the number of non-positive columns with s(i,j) == pos[i].
+ * All three outputs ([N]) are fully defined by the call: nothing is zeroed by the caller, there is no workspace.
+ * Exact fp32 in BOTH precision modes (a metric must not move with CXRK_PRECISION): v_mfma_f32_32x32x2_f32, k ascending, no split
+ * over k, so s(i,j) is a function of row i of Q and row j of G alone — two identical gallery rows tie bit for bit, and the result
+ * does not depend on the grid (integer atomics only).
+ * Non-finite: +-Inf compare as numbers.  A row whose best positive is NaN (pos keeps the NaN), or that meets a NaN score in a
+ * non-positive column, gets greater[i] = ties[i] = -1: a NaN never turns into a plausible rank.
+ * -1 for N, M, D < 1, ld < D, exactly one key pointer NULL, or (pair form) diag_off outside [0, M - N]. */
+int cxrk_retrieval_ranks(const float* Q, long ldq, int N, const float* G, long ldg, int M, int D, int diag_off,
+                         const long long* keys_q, const long long* keys_g, float* pos, int* greater, int* ties, hipStream_t stream);
 /* out = alpha * (alpha_dev ? *alpha_dev : 1) * x * (mask_src > 0): nn.ReLU backward (models.py:10) and chain-rule scaling
  * by an upstream scalar gradient that lives on the device. */
 int cxrk_scale_mask(const float* x, const float* mask_src, const float* alpha_dev, float alpha, long n, float* out,

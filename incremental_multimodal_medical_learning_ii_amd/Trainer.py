@@ -25,7 +25,9 @@ Two extensions behind the same entry points (both off unless asked for):
     (optionally `"log_scale_bounds": (lo, hi)`) makes the temperature a parameter: "temperature" is then its initial
     value, `save` / `load` carry it as `logit_scale.pt`, and `train` logs `train/temperature` once per epoch.  `"augment": True | {...}`
     (the fields of `augment.AugmentSpec`; True = a moderate default; optionally `"augment_seed"`) augments the images on the device
-    inside the training step; `val` / `test` never augment.
+    inside the training step; `val` / `test` never augment.  `"retrieval": True | (k, ...)` makes `val` / `test`
+    also encode each batch's reports and add image<->text retrieval over the whole split (Recall@K, median / mean rank, both
+    directions) to the returned dict and the writer as `Retrieval/i2t R@1`, ...; off by default.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -152,6 +154,8 @@ class Trainer:
         self.rank = dist.get_rank(process_group) if self.world > 1 else 0
         self._joint = None
         self.image_model = None
+        self._retrieval_ks = None          # joint_encoders={..., "retrieval": True | (k, ...)}: val / test add Retrieval/* metrics
+        self._retrieval_result = None
         if joint_encoders is not None:
             from .contrastive import JointContrastiveTrainer
             je = dict(joint_encoders) if isinstance(joint_encoders, dict) else {"image_model": joint_encoders[0], "temperature": joint_encoders[1]}
@@ -165,6 +169,7 @@ class Trainer:
                                                   **({"augment": je["augment"], "augment_seed": je.get("augment_seed")}
                                                      if je.get("augment") not in (None, False) else {}))
             print("*** JOINT ENCODER TRAINING (InfoNCE over the global batch): no adapters ***")
+            self._retrieval_ks = self._parse_retrieval(je.get("retrieval"))
         params = []
         if self._joint is not None:
             self.image_adapter = self.text_adapter = None
@@ -699,11 +704,59 @@ class Trainer:
         if self._joint is not None and self._joint.logit_scale is not None and self.writer is not None:
             self.writer.add_scalar('train/temperature', self._joint.current_temperature(), epoch)
 
+    @staticmethod
+    def _parse_retrieval(opt):
+        """the "retrieval" entry of `joint_encoders`: None / False -> off (None), True -> Recall@1/5/10, a sequence of positive
+        integers -> those cut-offs"""
+        from .contrastive import RETRIEVAL_KS, check_ks
+        if opt is None or opt is False:
+            return None
+        if opt is True:
+            return RETRIEVAL_KS
+        if isinstance(opt, int):
+            opt = (opt,)
+        return check_ks(opt)
+
+    def _retrieval_collect(self, acc, batch, new_embs):
+        """one evaluation batch of the retrieval set: this rank's shard of the image embeddings `_eval_loop` already has, and the
+        paired reports through the text encoder (under no_grad, eval mode: no dropout, no augmentation)"""
+        n = new_embs.shape[0]
+        if self.world > 1 and n % self.world:
+            raise ValueError(f"retrieval evaluation shards each batch evenly: {n} rows over {self.world} ranks (use drop_last)")
+        lo, hi = self._shard(n) if self.world > 1 else (0, n)
+        ids, mask = batch[1][lo:hi], batch[2][lo:hi]
+        keys = self._joint.pair_keys(ids, mask, batch[3][lo:hi] if self._joint.positives == "labels" else None)
+        acc[0].append(new_embs[lo:hi])
+        acc[1].append(self.bert_encoder.model.get_projected_text_embeddings(ids.to(self.device), mask.to(self.device),
+                                                                            normalize_embeddings=False))
+        if keys is not None:
+            acc[2].append(keys.to(self.device))
+
+    def _retrieval_finish(self, acc):
+        from .contrastive import retrieval_metrics
+        if not acc[0]:
+            return None
+        return retrieval_metrics(torch.cat(acc[0]).contiguous(), torch.cat(acc[1]).contiguous(),
+                                 torch.cat(acc[2]).contiguous() if acc[2] else None, self._retrieval_ks, self._joint._dist_group())
+
+    def _add_retrieval(self, m, val_test, epoch):
+        """`Retrieval/i2t R@1` ... `Retrieval/t2i n` of the last `_eval_loop`, into the returned dict and the writer"""
+        res, self._retrieval_result = self._retrieval_result, None
+        if res is None:
+            return m
+        for direction, d in res.items():
+            for k, v in d.items():
+                m[f"Retrieval/{direction} {k}"] = v
+                if self.writer is not None:
+                    self.writer.add_scalar(f"{val_test}/Retrieval/{direction} {k}", v, epoch)
+        return m
+
     @torch.no_grad()
     def _eval_loop(self, loader, criterion, epoch, log_tag):
         self._set_mode(False)
         y_true, y_pred, y_score = [], [], []
         batch_idx = 0
+        acc = ([], [], []) if self._joint is not None and self._retrieval_ks is not None else None
         for batch in loader:
             batch_idx += 1
             labels = batch[-1].to(self.device)
@@ -711,6 +764,8 @@ class Trainer:
                 if len(batch) < 4:
                     raise ValueError("joint-encoder evaluation needs (images, input_ids, attention_mask, labels) batches")
                 new_embs = self.image_model(batch[0].to(self.device))   # (under no_grad: the whole loop is)
+                if acc is not None:
+                    self._retrieval_collect(acc, batch, new_embs)
             else:
                 embs = batch[0].to(self.device)
                 new_embs = self.image_adapter(embs) if self._has_img else embs
@@ -726,17 +781,18 @@ class Trainer:
             y_true.append(labels.cpu().numpy())
             y_pred.append(pred.cpu().numpy())
             y_score.append(score.cpu().numpy())
+        self._retrieval_result = self._retrieval_finish(acc) if acc is not None else None
         return np.concatenate(y_true), np.concatenate(y_pred), np.concatenate(y_score)
 
     def val(self, val_loader, criterion, epoch, epochs, mode="joint", tasks_order=None):
         """`Trainer.py:773-866`: scores (pos+1)/2 or (pos-neg+2)/4, predictions argmax([neg,pos]), BCE logged."""
         y_true, y_pred, y_score = self._eval_loop(val_loader, criterion, epoch, "val")
-        return self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "val", epochs, tasks_order)
+        return self._add_retrieval(self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "val", epochs, tasks_order), "val", epoch)
 
     def test(self, test_loader, criterion, epoch, epochs, mode="joint", tasks_order=None, plot_tsne_array=None):
         """`Trainer.py:989-1062` (the t-SNE / heat-map plots that follow there are out of scope)."""
         y_true, y_pred, y_score = self._eval_loop(test_loader, None, epoch, None)
-        return self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "test", epochs, tasks_order)
+        return self._add_retrieval(self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "test", epochs, tasks_order), "test", epoch)
 
     @torch.no_grad()
     def evaluate_model(self, y_true, y_pred, y_score, mode, epoch, val_test, epochs, tasks_order):

@@ -97,6 +97,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_eval_score": (I, [P, L, I, I, P, P, P]),
     "cxrk_group_mean_fwd": (I, [P, I, I, I, P, P]),
     "cxrk_group_mean_bwd": (I, [P, I, I, I, P, P]),
+    "cxrk_retrieval_ranks": (I, [P, L, I, P, L, I, I, I, P, P, P, P, P, P]),
     "cxrk_scale_mask": (I, [P, P, P, F, L, P, P]),
     "cxrk_adam_fused": (I, [P, P, P, P, L, F, F, F, F, F, I, F, P]),
     "cxrk_sgd": (I, [P, P, L, F, F, F, P]),

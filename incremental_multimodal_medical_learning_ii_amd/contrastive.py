@@ -119,6 +119,82 @@ def keys_from_tokens(input_ids: torch.Tensor, attention_mask: torch.Tensor) -> t
     return row_keys(input_ids, attention_mask)
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# retrieval evaluation
+# ----------------------------------------------------------------------------------------------------------------
+RETRIEVAL_KS = (1, 5, 10)
+
+
+def check_ks(ks) -> Tuple[int, ...]:
+    """the cut-offs of Recall@K: a non-empty sequence of distinct integers >= 1 (bools and floats are refused), returned as a tuple"""
+    try:
+        ks = tuple(ks)
+    except TypeError:
+        raise ValueError(f"ks must be a sequence of positive integers, got {ks!r}") from None
+    if not ks or any(isinstance(k, bool) or not isinstance(k, int) or k < 1 for k in ks) or len(set(ks)) != len(ks):
+        raise ValueError(f"ks must be a non-empty sequence of distinct integers >= 1, got {ks!r}")
+    return ks
+
+
+def rank_metrics(greater, ties, ks=RETRIEVAL_KS) -> dict:
+    """Recall@K, median and mean rank of one retrieval direction from the two integer vectors of `kernels.retrieval_ranks`
+    (host arithmetic; any integer tensors / arrays of one length n >= 1).  Query i has `greater[i]` gallery rows that beat its best
+    positive and `ties[i]` that equal it exactly.  The rule for ties:
+
+        R@k and median_rank use the PESSIMISTIC rank  1 + greater + ties   (every tied row is counted as ahead),
+        mean_rank uses the expected rank under a random order of the tied rows,  1 + greater + ties / 2.
+
+    With the pessimistic rule a collapsed model (all embeddings equal: every score ties) gets rank M and R@k = 0 for k < M; the
+    optimistic rule would report 100 %.  R@k is a fraction in [0, 1].  If any row carries the -1 flag (it met a NaN score), every
+    metric of the direction is nan: a diverged model must not report a plausible number.  Returns {"R@k"..., "median_rank",
+    "mean_rank", "n"}."""
+    import numpy as np
+    ks = check_ks(ks)
+    g = np.asarray(greater.cpu() if isinstance(greater, torch.Tensor) else greater).astype(np.int64).reshape(-1)
+    t = np.asarray(ties.cpu() if isinstance(ties, torch.Tensor) else ties).astype(np.int64).reshape(-1)
+    if g.shape != t.shape or g.size == 0:
+        raise ValueError(f"rank_metrics: greater and ties must be two vectors of one length >= 1, got {g.shape} and {t.shape}")
+    out = {}
+    if bool((g < 0).any() or (t < 0).any()):
+        for k in ks:
+            out[f"R@{k}"] = float("nan")
+        out["median_rank"] = out["mean_rank"] = float("nan")
+    else:
+        worst = 1 + g + t
+        for k in ks:
+            out[f"R@{k}"] = float((worst <= k).mean())
+        out["median_rank"] = float(np.median(worst))
+        out["mean_rank"] = float((1.0 + g + 0.5 * t).mean())
+    out["n"] = int(g.size)
+    return out
+
+
+@torch.no_grad()
+def retrieval_metrics(img_emb: torch.Tensor, txt_emb: torch.Tensor, keys: Optional[torch.Tensor] = None, ks=RETRIEVAL_KS, group=None,
+                      normalize: bool = True) -> dict:
+    """Image->text and text->image retrieval over the whole evaluation set: {"i2t": {...}, "t2i": {...}}, each the dict of
+    `rank_metrics` (R@k for k in `ks`, median_rank, mean_rank, n; the tie rule is written there).  "i2t" uses the images as queries
+    and the reports as the gallery, "t2i" the reverse.  `img_emb` / `txt_emb` [N,D] are this rank's paired rows, on the GPU; scores
+    are cosines (`normalize=False`: plain dot products of the rows as given).  Without `keys` the positive of a query is its own
+    pair; with `keys` (int64 [N]) every pair of the set with the same key is (`keys_from_labels` / `keys_from_tokens`), and the
+    rank is that of the best one.  Every query is scored against the WHOLE gallery by `functional.retrieval_ranks`, which never
+    forms the [N, M] block.
+
+    Under a process `group` each rank passes its shard (equal sizes): the gallery rows and keys are all-gathered, each rank ranks
+    its own queries, and the [N, 2] integer results are all-gathered (one gather per direction), so every rank returns the same
+    dict, computed over all ranks' queries."""
+    ks = check_ks(ks)
+    out = {}
+    for name, q, g in (("i2t", img_emb, txt_emb), ("t2i", txt_emb, img_emb)):
+        _, greater, ties = Fh.retrieval_ranks(q, g, keys=keys, group=group, normalize=normalize)
+        gt = torch.stack((greater, ties), dim=1).contiguous()
+        if group is not None:
+            gt = Fh._all_gather_rows(gt, group)
+        gt = gt.cpu()
+        out[name] = rank_metrics(gt[:, 0], gt[:, 1], ks)
+    return out
+
+
 POSITIVES = (None, "labels", "text")
 LOG_SCALE_BOUNDS = (0.0, math.log(100.0))     # CLIP / open_clip: tau in [0.01, 1]
 
@@ -372,3 +448,47 @@ class JointContrastiveTrainer:
         if self.logit_scale is not None:
             K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)
         return loss.detach()
+
+    def _dist_group(self):
+        """the group to hand to the collectives of an evaluation: None in a single process, else this trainer's (the default group
+        spelled out, because `functional.retrieval_ranks` takes `group=None` as "not distributed")"""
+        if self.world == 1:
+            return None
+        if self.group is not None:
+            return self.group
+        import torch.distributed as dist
+        return dist.group.WORLD
+
+    @torch.no_grad()
+    def evaluate_retrieval(self, batches, ks=RETRIEVAL_KS, return_embeddings: bool = False):
+        """Image<->text retrieval of the two encoders over an evaluation set: `batches` yields
+        `(images, input_ids, attention_mask[, labels])` — under data parallelism THIS rank's rows, the same number on every rank.
+        Both encoders run in eval mode under no_grad (no augmentation, no dropout; the modules' previous modes are restored), the
+        projected embeddings stay on the device ([N, D] each), and `retrieval_metrics` ranks every image against all reports and
+        every report against all images once at the end.  With `positives` set the pairs' keys (`pair_keys`) define the positives.
+        Nothing of the training state moves: parameters, optimiser, dropout and augment counters are left as they are.
+        Returns the metrics dict, or (metrics, image embeddings, text embeddings) with `return_embeddings`."""
+        ks = check_ks(ks)
+        dev = next(self.image_model.parameters()).device
+        modes = [(m, m.training) for model in (self.image_model, self.text_model) for m in model.modules()]
+        imgs, txts, keys = [], [], []
+        try:
+            self.image_model.eval()
+            self.text_model.eval()
+            for batch in batches:
+                if len(batch) < 3:
+                    raise ValueError(f"evaluate_retrieval expects (images, input_ids, attention_mask[, labels]) batches, got {len(batch)} tensors")
+                images, ids, mask = batch[0], batch[1], batch[2]
+                k = self.pair_keys(ids, mask, batch[3] if len(batch) > 3 else None)
+                if k is not None:
+                    keys.append(k.to(dev))
+                imgs.append(self.image_model(images.to(dev)))
+                txts.append(self.text_model.get_projected_text_embeddings(ids.to(dev), mask.to(dev), normalize_embeddings=False))
+        finally:
+            for m, flag in modes:
+                m.training = flag
+        if not imgs:
+            raise ValueError("evaluate_retrieval: no batches")
+        img, txt = torch.cat(imgs).contiguous(), torch.cat(txts).contiguous()
+        metrics = retrieval_metrics(img, txt, torch.cat(keys).contiguous() if keys else None, ks, self._dist_group())
+        return (metrics, img, txt) if return_embeddings else metrics

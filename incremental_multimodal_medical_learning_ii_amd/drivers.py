@@ -122,12 +122,21 @@ def _setup(args, kind):
                              joint_encoders={"image_model": im, "temperature": args.temperature,
                                              "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None)),
                                              "learn_temperature": bool(getattr(args, "learn_temperature", False)),
-                                             "augment": augment_from_args(args)})
+                                             "augment": augment_from_args(args),
+                                             "retrieval": retrieval_from_args(args)})
     else:
         from .health_multimodal.text import get_cxr_bert_inference
         engine = get_cxr_bert_inference(args.pretrained_text, device="cuda")
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine)
     return trainer, writer, train_loader, val_loader, test_loader
+
+
+def retrieval_from_args(args):
+    """`--retrieval [K ...]` -> None (off), True (Recall@1/5/10) or the tuple of cut-offs given"""
+    ks = getattr(args, "retrieval", None)
+    if ks is None:
+        return None
+    return True if len(ks) == 0 else tuple(ks)
 
 
 AUG_FLAGS = {"aug_rotate": "rotate_deg", "aug_translate": "translate", "aug_zoom": "zoom", "aug_flip": "flip_p",
@@ -268,6 +277,9 @@ def make_parser():
     ap.add_argument("--aug-flip", type=float, default=None, metavar="P", help="--augment: horizontal flip with probability P (default 0)")
     ap.add_argument("--aug-brightness", type=float, default=None, metavar="B", help="--augment: brightness factor uniform in 1 +- B")
     ap.add_argument("--aug-contrast", type=float, default=None, metavar="C", help="--augment: contrast factor uniform in 1 +- C")
+    ap.add_argument("--retrieval", type=int, nargs="*", default=None, metavar="K",
+                    help="--joint: val / test also report image<->text retrieval over the whole split (Recall@K, median / mean rank, "
+                         "both directions, DESIGN.md 5.5); without values K = 1 5 10")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -286,6 +298,9 @@ def main(argv=None):
     if args.augment and not args.joint:
         raise SystemExit("--augment augments the images of the north-star step and needs --joint (the adapter schedules train on "
                          "pre-computed image embeddings)")
+    if args.retrieval is not None and not args.joint:
+        raise SystemExit("--retrieval ranks the reports of the evaluation batches against their images and needs --joint (the adapter "
+                         "schedules evaluate on pre-computed image embeddings without reports)")
     augment_from_args(args)      # --aug-* without --augment
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)

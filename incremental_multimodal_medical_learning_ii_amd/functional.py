@@ -393,6 +393,41 @@ def similarity_logits(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature:
 
 
 @torch.no_grad()
+def retrieval_ranks(queries: torch.Tensor, gallery: torch.Tensor, keys: Optional[torch.Tensor] = None, group=None,
+                    normalize: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Ranks of this rank's `queries` [B,D] against the WHOLE gallery (include/cxrk.h, "retrieval_ranks"): returns
+    (pos fp32 [B], greater int32 [B], ties int32 [B]) — the best positive score of each query and the number of non-positive
+    gallery rows that beat / equal it (-1 / -1 for a row that met a NaN).  The [B, M] score block is never formed.
+
+    `gallery` [B,D] holds this rank's rows, paired with the queries row by row.  Without `keys` the one positive of query i is
+    gallery row i; with `keys` (int64 [B], one per local pair) every gallery row of the global set with the query's key is.
+    With a process `group`, the gallery rows (and the keys) of all ranks are gathered, rank-major, and the positives of this
+    rank's queries sit at `rank * B` (the shard convention of `infonce_loss`): one [B,D] and at most one [B] all-gather.
+    `normalize`: L2-normalise both sides first (cosine scores).  No autograd."""
+    q, g = queries.detach().contiguous(), gallery.detach().contiguous()
+    if q.dim() != 2 or tuple(g.shape) != tuple(q.shape):
+        raise ValueError(f"retrieval_ranks: queries are {tuple(q.shape)} but this rank's gallery rows {tuple(g.shape)} "
+                         f"(they are paired row by row)")
+    B = q.shape[0]
+    if keys is not None:
+        if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64 or tuple(keys.shape) != (B,) or keys.device != q.device:
+            raise ValueError(f"retrieval_ranks: keys must be an int64 [{B}] tensor on {q.device}, got "
+                             f"{getattr(keys, 'dtype', type(keys).__name__)} {tuple(getattr(keys, 'shape', ()))}")
+        keys = keys.detach().contiguous()
+    if normalize:
+        q, g = K.l2norm_fwd(q)[0], K.l2norm_fwd(g)[0]
+    off, g_all, keys_all = 0, g, keys
+    if group is not None:
+        import torch.distributed as dist
+        off = dist.get_rank(group) * B
+        g_all = _all_gather_rows(g, group)
+        keys_all = _all_gather_rows(keys, group) if keys is not None else None
+    if keys is None:
+        return K.retrieval_ranks(q, g_all, diag_off=off)
+    return K.retrieval_ranks(q, g_all, keys_q=keys, keys_g=keys_all)
+
+
+@torch.no_grad()
 def augment_images(images: torch.Tensor, spec, seed: int, counter: int, row_offset: int = 0, cpad: int = 4) -> torch.Tensor:
     """Random affine + brightness / contrast augmentation on the device (include/cxrk.h, "augment"):
     images [N, 3 | 1, H, W] -> fp32 NHWC [N, Ho, Wo, cpad] (three channels, the padding zero), the tensor the ResNet stem reads.

@@ -1111,6 +1111,35 @@ def multipos_grad_inplace(S, keys_row, keys_col, n_row, lse_row, lse_col):
     return S
 
 
+def retrieval_ranks(Q, G, diag_off: int = 0, keys_q=None, keys_g=None):
+    """(pos, greater, ties), each [N], of the queries Q [N,D] against the whole gallery G [M,D] without the [N,M] score block
+    (include/cxrk.h, "retrieval_ranks").  The positives of row i: column i + diag_off, or, with keys, every column j with
+    keys_g[j] == keys_q[i].  pos fp32 = the best positive score; greater / ties int32 = the non-positive columns that beat / equal
+    it; both -1 for a row that met a NaN.  Exact fp32 whatever the precision mode.  Rows may be strided (stride(0) >= D)."""
+    lib = _lib.load()
+    _chk(Q, "retrieval.Q"), _chk(G, "retrieval.G")
+    if Q.dim() != 2 or G.dim() != 2 or Q.shape[1] != G.shape[1]:
+        raise ValueError(f"retrieval_ranks: expected Q [N,D] and G [M,D], got {tuple(Q.shape)} and {tuple(G.shape)}")
+    if G.device != Q.device:
+        raise ValueError(f"retrieval_ranks: Q is on {Q.device} but G on {G.device}")
+    N, D = Q.shape
+    M = G.shape[0]
+    if (D > 1 and (Q.stride(1) != 1 or G.stride(1) != 1)) or (N > 1 and Q.stride(0) < D) or (M > 1 and G.stride(0) < D):
+        raise ValueError(f"retrieval_ranks: columns must be contiguous and rows at least D apart, got strides {Q.stride()} and {G.stride()}")
+    if (keys_q is None) != (keys_g is None):
+        raise ValueError("retrieval_ranks: keys_q and keys_g go together (both or neither)")
+    if keys_q is not None:
+        _keys(keys_q, N, "retrieval.keys_q"), _keys(keys_g, M, "retrieval.keys_g")
+    pos = torch.empty(N, dtype=torch.float32, device=Q.device)
+    greater = torch.empty(N, dtype=torch.int32, device=Q.device)
+    ties = torch.empty(N, dtype=torch.int32, device=Q.device)
+    ldq = Q.stride(0) if N > 1 else max(D, Q.stride(0))
+    ldg = G.stride(0) if M > 1 else max(D, G.stride(0))
+    check(lib.cxrk_retrieval_ranks(_p(Q), ldq, N, _p(G), ldg, M, D, int(diag_off), _p(keys_q), _p(keys_g), _p(pos), _p(greater),
+                                   _p(ties), _stream()), "cxrk_retrieval_ranks")
+    return pos, greater, ties
+
+
 def _log_scale(t):
     _chk(t, "log_scale")
     if t.numel() != 1 or t.dim() > 1:
