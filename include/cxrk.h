@@ -336,6 +336,22 @@ int cxrk_gelu_bwd(const float* dy, const float* pre, long n, float* dx, hipStrea
  *              caller provides rows * nchunk floats and every one of them is written (an output, not scratch memory).
  * logit_scale_grad: dtheta[0] = (accumulate ? dtheta[0] : 0) + upstream[0] * scale * (sum partials1[0..n1) + sum partials2[0..n2));
  *              one block, fixed order; upstream is a device scalar; partials2 may be NULL with n2 = 0.
+ * sigmoid_pairs: the pairwise sigmoid loss (SigLIP): the reference's BCE-with-logits criterion (ZERO_JOINT_BOUNDS.py:36,
+ *              Trainer.py:575-582) carried to every pair of the block, nothing normalised over the batch.  The block holds the
+ *              unscaled cosines C; log_scale points at theta = log(1/tau) and bias at b, one fp32 each, read on the device.  With
+ *              t = exp(theta) and x = fma(t, c, b):  l = softplus(-x) for a positive pair, softplus(x) otherwise;
+ *              g = dl/dx = -sigmoid(-x) or sigmoid(x); the positive branch is never formed as sigmoid(x) - 1.
+ *              fwd_bwd_inplace turns C into t * g in ONE pass.  Positives: keys_row and keys_col both NULL: the one positive of row i
+ *              is column diag_off + i (0 <= diag_off, diag_off + rows <= cols); both given: the columns j with keys_col[j] ==
+ *              keys_row[i] (a row may have none; diag_off is ignored); exactly one NULL: -1.  partials == NULL: no sums are formed.
+ *              Otherwise partials holds 3 * rows * nchunk floats, nchunk = ceil(cols / 1024), as three planes of rows * nchunk:
+ *              plane 0 sum l, plane 1 sum g * (t c) (= g * (x - b)), plane 2 sum g; entry [i * nchunk + k] of a plane sums over
+ *              columns [1024 k, 1024 (k+1)) of row i in a fixed order (no atomics).  Every one of them is written (an output of the
+ *              caller, not scratch memory).  Exact fp32 in both precision modes; 16-byte accesses where ld % 4 == 0 and C is
+ *              16-byte aligned, scalar otherwise.  A NaN cosine makes its own element and its row's three sums non-finite and
+ *              touches nothing else; at +-Inf, g * (t c) may be 0 * Inf (the "0 or NaN" clause above).
+ * sigmoid_pairs_loss: loss_out[0] = (accumulate ? loss_out[0] : 0) + scale * sum partials[0..n); one block, fixed order (plane 0 with
+ *              scale 1/Bg gives the loss; logit_scale_grad on plane 1 gives d theta and on plane 2 d b, with partials2 = NULL).
  * clamp_inplace: x[i] = min(max(x[i], lo), hi) for lo <= hi; a NaN stays a NaN.
  * pairwise_cosine: torchmetrics pairwise_cosine_similarity as called by Trainer.myCosineSimilarity (Trainer.py:1682-1704).
  * pairwise_cosine_max: the MAX_EMB branch of the same function (Trainer.py:1691-1693): y holds G groups of Pg prompt
@@ -374,6 +390,10 @@ int cxrk_multipos_grad_scaled_inplace(float* C, long ld, int rows, int cols, con
                                       const float* log_scale, float* partials, hipStream_t stream);
 int cxrk_logit_scale_grad(const float* partials1, long n1, const float* partials2, long n2, const float* upstream, float scale,
                           float* dtheta, int accumulate, hipStream_t stream);
+int cxrk_sigmoid_pairs_fwd_bwd_inplace(float* C, long ld, int rows, int cols, int diag_off, const long long* keys_row,
+                                       const long long* keys_col, const float* log_scale, const float* bias, float* partials,
+                                       hipStream_t stream);
+int cxrk_sigmoid_pairs_loss(const float* partials, long n, float scale, float* loss_out, int accumulate, hipStream_t stream);
 int cxrk_clamp_inplace(float* x, long n, float lo, float hi, hipStream_t stream);
 int cxrk_pairwise_cosine_fwd(const float* x, const float* y, long B, int P, int D, float* cosv, float* xnorm,
                              float* ynorm, hipStream_t stream);

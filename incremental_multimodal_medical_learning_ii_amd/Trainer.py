@@ -23,7 +23,10 @@ Two extensions behind the same entry points (both off unless asked for):
     pairs of the global batch with the same label vector / the same prompt tokens positives of each other (multi-positive InfoNCE,
     DESIGN.md §5.2; "labels" needs the fourth tensor of the batch); the default is one positive per row.  `"learn_temperature": True`
     (optionally `"log_scale_bounds": (lo, hi)`) makes the temperature a parameter: "temperature" is then its initial
-    value, `save` / `load` carry it as `logit_scale.pt`, and `train` logs `train/temperature` once per epoch.  `"augment": True | {...}`
+    value, `save` / `load` carry it as `logit_scale.pt`, and `train` logs `train/temperature` once per epoch.
+    `"contrastive_loss": "sigmoid"` (optionally `"sigmoid_bias": b`, default -10) trains with the pairwise sigmoid loss instead of
+    InfoNCE; with "learn_temperature" its bias is learned too (`logit_bias` in `logit_scale.pt`, `train/bias`).
+    `"augment": True | {...}`
     (the fields of `augment.AugmentSpec`; True = a moderate default; optionally `"augment_seed"`) augments the images on the device
     inside the training step; `val` / `test` never augment.  `"retrieval": True | (k, ...)` makes `val` / `test`
     also encode each batch's reports and add image<->text retrieval over the whole split (Recall@K, median / mean rank, both
@@ -166,9 +169,12 @@ class Trainer:
                                                   temperature=float(je.get("temperature", 0.07)), group=process_group, optim=OPTIM,
                                                   positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
                                                   **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
+                                                  **({"loss": je["contrastive_loss"]} if "contrastive_loss" in je else {}),
+                                                  **({"sigmoid_bias": je["sigmoid_bias"]} if je.get("sigmoid_bias") is not None else {}),
                                                   **({"augment": je["augment"], "augment_seed": je.get("augment_seed")}
                                                      if je.get("augment") not in (None, False) else {}))
-            print("*** JOINT ENCODER TRAINING (InfoNCE over the global batch): no adapters ***")
+            print("*** JOINT ENCODER TRAINING (%s over the global batch): no adapters ***"
+                  % ("pairwise sigmoid loss" if self._joint.loss == "sigmoid" else "InfoNCE"))
             self._retrieval_ks = self._parse_retrieval(je.get("retrieval"))
         params = []
         if self._joint is not None:
@@ -703,6 +709,8 @@ class Trainer:
         """the learned temperature, once per epoch (the one read-back of the logit scale; never inside the step loop)"""
         if self._joint is not None and self._joint.logit_scale is not None and self.writer is not None:
             self.writer.add_scalar('train/temperature', self._joint.current_temperature(), epoch)
+            if self._joint.logit_bias is not None:
+                self.writer.add_scalar('train/bias', self._joint.current_bias(), epoch)
 
     @staticmethod
     def _parse_retrieval(opt):
@@ -839,9 +847,10 @@ class Trainer:
             flat, base = self.optimizer.flat_p, self.optimizer.flat_p.data_ptr()
             for p in self.optimizer.params:
                 o, n = (p.data_ptr() - base) // 4, p.numel()
-                if p is self._joint.logit_scale:
+                if p is self._joint.logit_scale or p is self._joint.logit_bias:
                     # one element: min = max of |new - old|, so `d < min + threshold * (max - min)` never holds and the learned
-                    # temperature is never restored; said here instead of left to that arithmetic, and counted as updated
+                    # temperature (or the sigmoid loss's bias) is never restored; said here instead of left to that arithmetic, and
+                    # counted as updated
                     self._reset_total += n
                     continue
                 K.weight_reset(flat[o:o + n], self._flat_copy[o:o + n], threshold, self._reset_counters)
@@ -891,7 +900,10 @@ class Trainer:
             torch.save(self.image_model.state_dict(), os.path.join(self.writer.log_dir, 'image_model.pt'))
             torch.save(self.bert_encoder.model.state_dict(), os.path.join(self.writer.log_dir, 'text_model.pt'))
             if self._joint.logit_scale is not None:
-                torch.save({"logit_scale": self._joint.logit_scale.detach().cpu()}, os.path.join(self.writer.log_dir, 'logit_scale.pt'))
+                sd = {"logit_scale": self._joint.logit_scale.detach().cpu()}
+                if self._joint.logit_bias is not None:
+                    sd["logit_bias"] = self._joint.logit_bias.detach().cpu()
+                torch.save(sd, os.path.join(self.writer.log_dir, 'logit_scale.pt'))
         if hasattr(self.writer, "flush"):
             self.writer.flush()
 
@@ -921,5 +933,10 @@ class Trainer:
                         own[k].copy_(v)
             if self._joint.logit_scale is not None:
                 sd = torch.load(os.path.join(self.writer.log_dir, 'logit_scale.pt'), map_location="cpu", weights_only=True)
+                if self._joint.logit_bias is not None and "logit_bias" not in sd:
+                    raise ValueError(f"{os.path.join(self.writer.log_dir, 'logit_scale.pt')}: no 'logit_bias' entry; this trainer learns "
+                                     f"the sigmoid loss's bias with the logit scale (the file was written by an InfoNCE run)")
                 self._joint.logit_scale.data.copy_(sd["logit_scale"].reshape(1))
+                if self._joint.logit_bias is not None:
+                    self._joint.logit_bias.data.copy_(sd["logit_bias"].reshape(1))
             self._bert_cache.clear()

@@ -21,6 +21,12 @@ step, and is clamped to `log_scale_bounds` after it.  The loss kernels read thet
 gradient all-reduce (at the end of the "text" span): no new collective, no host sync.  `learn_temperature=False` (the default) creates no parameter and issues
 exactly the calls it always did.
 
+`loss="sigmoid"`: the pairwise sigmoid loss in place of InfoNCE: every (image, report) pair of the global batch is a
+binary problem on x = exp(theta) * cos + b.  With `learn_temperature` theta AND the bias b (`logit_bias`, initialised from
+`sigmoid_bias`) are parameters, appended behind the text parameters in that order; otherwise both are device constants made at
+construction.  Nothing is normalised over the batch, so the step has no log-sum-exp all-gather.  `loss="infonce"` (the default)
+issues exactly the calls it always did.
+
 `augment=AugmentSpec(...)`: on-device image augmentation.  The trainer owns (seed, step counter) as `augment_state`
 and hands the image model one call descriptor per `step` (spec, seed, counter, this rank's first global row): the encoder's
 NCHW -> NHWC boundary transform then samples each image through its own random affine map and jitters brightness / contrast.  The
@@ -196,6 +202,8 @@ def retrieval_metrics(img_emb: torch.Tensor, txt_emb: torch.Tensor, keys: Option
 
 
 POSITIVES = (None, "labels", "text")
+LOSSES = ("infonce", "sigmoid")
+SIGMOID_BIAS = -10.0                          # SigLIP's initial bias: the Bg^2 - Bg negatives start out nearly free
 LOG_SCALE_BOUNDS = (0.0, math.log(100.0))     # CLIP / open_clip: tau in [0.01, 1]
 
 
@@ -204,10 +212,23 @@ class JointContrastiveTrainer:
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
                  optim: str = "adam", positives: Optional[str] = None, learn_temperature: bool = False,
                  log_scale_bounds: Tuple[float, float] = LOG_SCALE_BOUNDS, augment: Optional[AugmentSpec] = None,
-                 augment_seed: Optional[int] = None):
+                 augment_seed: Optional[int] = None, loss: str = "infonce", sigmoid_bias: Optional[float] = None):
         if positives not in POSITIVES:
             raise ValueError(f"positives must be None, 'labels' or 'text', got {positives!r}")
+        if loss not in LOSSES:
+            raise ValueError(f"loss must be 'infonce' or 'sigmoid', got {loss!r}")
+        if loss != "sigmoid" and sigmoid_bias is not None:
+            raise ValueError(f"sigmoid_bias is the bias of loss='sigmoid'; it was given with loss={loss!r}")
+        if loss == "sigmoid":
+            sigmoid_bias = SIGMOID_BIAS if sigmoid_bias is None else float(sigmoid_bias)
+            if not math.isfinite(sigmoid_bias):
+                raise ValueError(f"sigmoid_bias must be finite, got {sigmoid_bias!r}")
+            if not temperature > 0:
+                raise ValueError(f"loss='sigmoid': the temperature must be positive, got {temperature!r}")
+        self.loss = loss
         self.logit_scale = None
+        self.logit_bias = None
+        self._sigmoid_consts = None
         if learn_temperature:
             lo, hi = (float(v) for v in log_scale_bounds)
             if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
@@ -246,6 +267,14 @@ class JointContrastiveTrainer:
             dev = next(image_model.parameters()).device
             self.logit_scale = torch.nn.Parameter(torch.tensor([math.log(1.0 / float(temperature))], dtype=torch.float32, device=dev))
             tparams = tparams + [self.logit_scale]
+            if loss == "sigmoid":    # the bias is learned with the scale, and follows it: "text" runs on over both slots
+                self.logit_bias = torch.nn.Parameter(torch.tensor([sigmoid_bias], dtype=torch.float32, device=dev))
+                tparams = tparams + [self.logit_bias]
+        elif loss == "sigmoid":
+            # fixed theta and b: two device constants made once, here; no parameter and no per-step host-to-device copy
+            dev = next(image_model.parameters()).device
+            self._sigmoid_consts = (torch.tensor([math.log(1.0 / float(temperature))], dtype=torch.float32, device=dev),
+                                    torch.tensor([sigmoid_bias], dtype=torch.float32, device=dev))
         if optim == "adam":          # the reference's `optim.Adam(params, lr)` / `optim.SGD(params, lr)` (Trainer.py:172-178)
             self.optimizer = cxr_optim.Adam(params + tparams, lr=lr)
         elif optim == "sgd":
@@ -268,6 +297,13 @@ class JointContrastiveTrainer:
         if self.logit_scale is None:
             return float(self.temperature)
         return math.exp(-float(self.logit_scale.detach().cpu()))
+
+    def current_bias(self) -> Optional[float]:
+        """b of the sigmoid loss as a host float (None with loss="infonce"): a host sync when b is learned, and only when called."""
+        if self.loss != "sigmoid":
+            return None
+        b = self.logit_bias if self.logit_bias is not None else self._sigmoid_consts[1]
+        return float(b.detach().cpu())
 
     def sync_dropout_state(self) -> None:
         """Text dropout under data parallelism: every rank takes rank 0's (seed, counter), so that with the row offset of
@@ -348,6 +384,8 @@ class JointContrastiveTrainer:
             tparams = [p for p in self.text_model.parameters() if id(p) in ids]
             if self.logit_scale is not None:
                 tparams.append(self.logit_scale)
+            if self.logit_bias is not None:
+                tparams.append(self.logit_bias)
         groups = {"text": list(tparams)}
         for n, p in inamed:
             groups.setdefault(stage_of_param(n), []).append(p)
@@ -397,6 +435,9 @@ class JointContrastiveTrainer:
         return self._loss(img, txt, keys)
 
     def _loss(self, img, txt, keys):
+        if self.loss == "sigmoid":
+            theta, b = (self.logit_scale, self.logit_bias) if self.logit_scale is not None else self._sigmoid_consts
+            return Fh.sigmoid_pairs_loss(img, txt, theta, b, self.group, keys=keys)
         if self.logit_scale is not None:
             return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys, log_scale=self.logit_scale)
         if keys is None:

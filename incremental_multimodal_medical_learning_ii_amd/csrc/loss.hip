@@ -3,6 +3,7 @@
 //  * InfoNCE pieces on a materialised logits block S[B][Bg] (the logits GEMMs run on the shared MFMA mainloop):
 //    row log-sum-exp + diagonal pick, and the in-place softmax-gradient transform; their multi-positive (keyed) forms; and the
 //    forms with a learnable temperature (device logit scale, fused d theta partial sums)
+//  * pairwise sigmoid loss on the same block: forward, gradient and the partial sums of loss / d theta / d b in one pass
 //  * torchmetrics-style pairwise cosine fwd/bwd (reference Trainer.myCosineSimilarity, Trainer.py:1682-1704)
 //  * pos-neg logits + BCE-with-logits(mean) fwd+bwd in one pass (Trainer.py:575-583, ZERO_JOINT_BOUNDS.py:36)
 //  * eval scoring (Trainer.py:797-837)
@@ -289,6 +290,74 @@ __global__ __launch_bounds__(256) void logit_scale_grad_kernel(const float* __re
   for (long i = threadIdx.x; i < n2; i += 256) s2 += part2[i];
   const float s = block_sum(s1, sh) + block_sum(s2, sh);
   if (threadIdx.x == 0) { const float v = upstream[0] * scale * s; dtheta[0] = accumulate ? dtheta[0] + v : v; }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// pairwise sigmoid loss: every (row, column) pair is a binary problem on x = fma(t, c, b), t = exp(theta); theta and b on the device.
+// ---------------------------------------------------------------------------------------------------------------
+// One element: l = softplus(-x) for a positive pair, softplus(x) otherwise; g = dl/dx = -sigmoid(-x) or sigmoid(x).  With
+// e = exp(-|x|) and r = 1 / (1 + e):  softplus(y) = max(y, 0) + log1p(e),  sigmoid(x) = x >= 0 ? r : e * r.  The positive branch is
+// -sigmoid(-x), never sigmoid(x) - 1 (which cancels to 0 from x ~ 17 on).  A NaN x makes e, and so l and g, NaN.
+template <bool SUMS>
+__device__ __forceinline__ float sigmoid_pair(float t, float cv, float b, bool pos, float& sl, float& sgx, float& sg) {
+  const float x = fmaf(t, cv, b);
+  const float e = expf(-fabsf(x));
+  const float r = 1.f / (1.f + e);
+  const float er = e * r;
+  const float g = pos ? -(x >= 0.f ? er : r) : (x >= 0.f ? r : er);
+  if (SUMS) {
+    const float y = pos ? -x : x;
+    sl += (y > 0.f ? y : 0.f) + log1pf(e);
+    sgx += g * (t * cv);
+    sg += g;
+  }
+  return t * g;
+}
+
+// In place on C: C[i][j] <- t * g_ij.  grid (rows, ceil(cols / 1024)), a thread owns 4 consecutive columns as in scaled_grad_kernel.
+// SUMS: part holds three planes of gridDim.x * gridDim.y floats (sum l, sum g * (t c), sum g); entry [i * gridDim.y + chunk] of each is
+// the block_sum (fixed order) over the chunk's columns of row i.  No thread leaves before the block sums.
+template <bool VEC, bool KEYED, bool SUMS>
+__global__ __launch_bounds__(256) void sigmoid_pairs_kernel(float* __restrict__ C, long ld, int cols, int diag_off,
+                                                            const long long* __restrict__ keys_row,
+                                                            const long long* __restrict__ keys_col,
+                                                            const float* __restrict__ log_scale, const float* __restrict__ bias,
+                                                            float* __restrict__ part) {
+  __shared__ float sh[16];
+  const long i = blockIdx.x;
+  const int j0 = (blockIdx.y * 256 + threadIdx.x) * 4;
+  float* c = C + i * ld;
+  const float t = expf(log_scale[0]), b = bias[0];
+  const long long kr = KEYED ? keys_row[i] : 0;
+  const int dcol = diag_off + (int)i;
+  float sl = 0.f, sgx = 0.f, sg = 0.f;
+  if (VEC && j0 + 4 <= cols) {
+    f32x4 v = *reinterpret_cast<const f32x4*>(c + j0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      v[q] = sigmoid_pair<SUMS>(t, v[q], b, KEYED ? keys_col[j0 + q] == kr : j0 + q == dcol, sl, sgx, sg);
+    *reinterpret_cast<f32x4*>(c + j0) = v;
+  } else if (j0 < cols) {
+    const int j1 = min(j0 + 4, cols);
+    for (int j = j0; j < j1; ++j) c[j] = sigmoid_pair<SUMS>(t, c[j], b, KEYED ? keys_col[j] == kr : j == dcol, sl, sgx, sg);
+  }
+  if (SUMS) {
+    const long plane = (long)gridDim.x * gridDim.y, at = i * gridDim.y + blockIdx.y;
+    sl = block_sum(sl, sh);
+    sgx = block_sum(sgx, sh);
+    sg = block_sum(sg, sh);
+    if (threadIdx.x == 0) { part[at] = sl; part[plane + at] = sgx; part[2 * plane + at] = sg; }
+  }
+}
+
+// out[0] (+)= scale * sum part[0..n); single block, fixed order.
+__global__ __launch_bounds__(256) void sigmoid_pairs_loss_kernel(const float* __restrict__ part, long n, float scale,
+                                                                 float* __restrict__ out, int accumulate) {
+  __shared__ float sh[16];
+  float s = 0.f;
+  for (long i = threadIdx.x; i < n; i += 256) s += part[i];
+  s = block_sum(s, sh);
+  if (threadIdx.x == 0) out[0] = accumulate ? out[0] + s * scale : s * scale;
 }
 
 // x <- min(max(x, lo), hi) by comparisons, which are false for a NaN: a NaN stays a NaN (fminf / fmaxf would return the bound).
@@ -629,6 +698,41 @@ extern "C" int cxrk_logit_scale_grad(const float* partials1, long n1, const floa
   CXRK_CHECK_ARG(partials1 && n1 > 0 && n2 >= 0 && (partials2 || n2 == 0) && upstream && dtheta);
   hipLaunchKernelGGL(logit_scale_grad_kernel, dim3(1), dim3(256), 0, stream, partials1, n1, partials2, n2, upstream, scale, dtheta,
                      accumulate);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+template <bool KEYED, bool SUMS>
+static int sigmoid_pairs(float* C, long ld, int rows, int cols, int diag_off, const long long* keys_row, const long long* keys_col,
+                         const float* log_scale, const float* bias, float* partials, hipStream_t stream) {
+  const dim3 grid(rows, (unsigned)((cols + 1023) / 1024));
+  if (ld % 4 == 0 && aligned16(C))
+    hipLaunchKernelGGL((sigmoid_pairs_kernel<true, KEYED, SUMS>), grid, dim3(256), 0, stream, C, ld, cols, diag_off, keys_row, keys_col,
+                       log_scale, bias, partials);
+  else
+    hipLaunchKernelGGL((sigmoid_pairs_kernel<false, KEYED, SUMS>), grid, dim3(256), 0, stream, C, ld, cols, diag_off, keys_row, keys_col,
+                       log_scale, bias, partials);
+  CXRK_LAUNCH_CHECK();
+  return CXRK_OK;
+}
+
+extern "C" int cxrk_sigmoid_pairs_fwd_bwd_inplace(float* C, long ld, int rows, int cols, int diag_off, const long long* keys_row,
+                                                  const long long* keys_col, const float* log_scale, const float* bias,
+                                                  float* partials, hipStream_t stream) {
+  CXRK_CHECK_ARG(C && log_scale && bias && rows > 0 && cols > 0 && ld >= cols && (keys_row == nullptr) == (keys_col == nullptr));
+  if (keys_row) {
+    return partials ? sigmoid_pairs<true, true>(C, ld, rows, cols, 0, keys_row, keys_col, log_scale, bias, partials, stream)
+                    : sigmoid_pairs<true, false>(C, ld, rows, cols, 0, keys_row, keys_col, log_scale, bias, nullptr, stream);
+  }
+  CXRK_CHECK_ARG(diag_off >= 0 && diag_off + rows <= cols);
+  return partials ? sigmoid_pairs<false, true>(C, ld, rows, cols, diag_off, nullptr, nullptr, log_scale, bias, partials, stream)
+                  : sigmoid_pairs<false, false>(C, ld, rows, cols, diag_off, nullptr, nullptr, log_scale, bias, nullptr, stream);
+}
+
+extern "C" int cxrk_sigmoid_pairs_loss(const float* partials, long n, float scale, float* loss_out, int accumulate,
+                                       hipStream_t stream) {
+  CXRK_CHECK_ARG(partials && n > 0 && loss_out);
+  hipLaunchKernelGGL(sigmoid_pairs_loss_kernel, dim3(1), dim3(256), 0, stream, partials, n, scale, loss_out, accumulate);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }

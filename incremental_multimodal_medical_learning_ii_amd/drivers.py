@@ -122,6 +122,8 @@ def _setup(args, kind):
                              joint_encoders={"image_model": im, "temperature": args.temperature,
                                              "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None)),
                                              "learn_temperature": bool(getattr(args, "learn_temperature", False)),
+                                             "contrastive_loss": getattr(args, "contrastive_loss", None) or "infonce",
+                                             "sigmoid_bias": getattr(args, "sigmoid_bias", None),
                                              "augment": augment_from_args(args),
                                              "retrieval": retrieval_from_args(args)})
     else:
@@ -268,6 +270,11 @@ def make_parser():
     ap.add_argument("--learn-temperature", action="store_true",
                     help="--joint: learn the InfoNCE temperature (logit scale log(1/tau), initialised from --temperature, clamped to "
                          "[0, ln 100] after every step); default: the temperature is fixed")
+    ap.add_argument("--contrastive-loss", default=None, choices=["infonce", "sigmoid"],
+                    help="--joint: the loss of the north-star step: softmax InfoNCE (infonce, default) or the pairwise sigmoid loss "
+                         "(sigmoid, DESIGN.md 5.6); with --learn-temperature the sigmoid loss learns its bias too")
+    ap.add_argument("--sigmoid-bias", type=float, default=None, metavar="B",
+                    help="--contrastive-loss sigmoid: the (initial) bias b of the logits exp(theta) * cos + b; default -10")
     ap.add_argument("--augment", action="store_true",
                     help="--joint: augment the images on the device inside the training step (random affine + brightness / contrast, "
                          "DESIGN.md 5.4); alone it selects +-10 degrees, translate 0.05, zoom 0.9..1.1, no flip, brightness / contrast 0.2")
@@ -295,6 +302,15 @@ def main(argv=None):
     if args.learn_temperature and not args.joint:
         raise SystemExit("--learn-temperature makes the temperature of the north-star InfoNCE step a parameter and needs --joint (the "
                          "adapter schedules have no temperature)")
+    if args.contrastive_loss is not None and not args.joint:
+        raise SystemExit("--contrastive-loss selects the loss of the north-star step and needs --joint (the adapter schedules train "
+                         "with the pos-neg BCE loss)")
+    if args.sigmoid_bias is not None and not args.joint:
+        raise SystemExit("--sigmoid-bias is the bias of the north-star step's pairwise sigmoid loss and needs --joint "
+                         "--contrastive-loss sigmoid")
+    if args.sigmoid_bias is not None and args.contrastive_loss != "sigmoid":
+        raise SystemExit("--sigmoid-bias is the bias of the pairwise sigmoid loss and needs --contrastive-loss sigmoid (InfoNCE has "
+                         "no bias)")
     if args.augment and not args.joint:
         raise SystemExit("--augment augments the images of the north-star step and needs --joint (the adapter schedules train on "
                          "pre-computed image embeddings)")

@@ -383,6 +383,124 @@ def infonce_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: floa
     return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys, log_scale)
 
 
+def _device_scalar(t, name: str, device) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"sigmoid_pairs_loss: {name} must be an fp32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.numel() != 1 or t.dim() > 1:
+        raise ValueError(f"sigmoid_pairs_loss: {name} must be 0-d or have shape (1,), got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"sigmoid_pairs_loss: {name} is on {t.device} but the embeddings on {device}")
+    return t.detach()
+
+
+class _SigmoidPairs(torch.autograd.Function):
+    """Pairwise sigmoid loss (SigLIP) over the GLOBAL batch: with C = I_hat T_hat^T, t = exp(theta), x = t C + b,
+        L = 1/Bg sum_ij softplus(-x_ij) [pair (i,j) positive] + softplus(x_ij) [negative],      g = dl/dx,
+        dL/dC = t g / Bg,    dL/dtheta = 1/Bg sum g (x - b),    dL/db = 1/Bg sum g.
+    Positives: j is i's pair, or, with `keys`, every pair of equal keys.  Nothing is normalised over the batch, so there is no
+    log-sum-exp to exchange: the data-parallel step issues the embedding all-gather (plus the keys'), and the scalar all-reduce
+    of the reported loss.  One fused kernel per block does forward and backward: S1 = local images x all texts carries the
+    complete rows of g, so it also yields the loss and the d theta / d b partial sums; S2 = local texts x all images is the
+    transpose coverage that the text gradient needs and yields no sums.  A key belongs to a pair, so S2 uses the same row and
+    column keys.  Summed over the ranks the S1 blocks cover every (i, j) once: the sum all-reduce of the flat gradient buffer
+    completes d theta and d b."""
+
+    @staticmethod
+    def forward(ctx, img, txt, log_scale, logit_bias, group, keys=None):
+        import torch.distributed as dist
+        dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        img, txt = img.detach().contiguous(), txt.detach().contiguous()
+        if img.dim() != 2 or tuple(txt.shape) != tuple(img.shape):
+            raise ValueError(f"sigmoid_pairs_loss: image embeddings are {tuple(img.shape)} but text embeddings {tuple(txt.shape)}")
+        B, D = img.shape
+        world_ = dist.get_world_size(group) if dist_on else 1
+        # every check runs HERE, before any collective is issued (see _InfoNCE.forward)
+        if (B * world_) % 4 != 0 or D % 4 != 0:
+            raise ValueError(f"sigmoid_pairs_loss: global batch {B * world_} (= {B} rows x {world_} ranks) and embedding size {D} must "
+                             f"be multiples of 4 (drop or pad the ragged last batch)")
+        if keys is not None:
+            if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
+                raise ValueError(f"sigmoid_pairs_loss: keys must be an int64 tensor, got {getattr(keys, 'dtype', type(keys).__name__)}")
+            if tuple(keys.shape) != (B,):
+                raise ValueError(f"sigmoid_pairs_loss: keys must have shape ({B},), one per local row, got {tuple(keys.shape)}")
+            if keys.device != img.device:
+                raise ValueError(f"sigmoid_pairs_loss: keys are on {keys.device} but the embeddings on {img.device}")
+            keys = keys.detach().contiguous()
+        theta = _device_scalar(log_scale, "log_scale", img.device)
+        bias = _device_scalar(logit_bias, "logit_bias", img.device)
+        if dist_on:
+            rank, world = dist.get_rank(group), dist.get_world_size(group)
+            send = torch.empty(B, 2 * D, dtype=torch.float32, device=img.device)
+            ih, inorm = K.l2norm_fwd(img, out=send[:, :D])
+            th, tnorm = K.l2norm_fwd(txt, out=send[:, D:])
+            both = _all_gather_rows(send, group)                           # [Bg, 2D]
+            keys_all = _all_gather_rows(keys, group) if keys is not None else None      # [Bg] int64
+            ih_all, th_all = both[:, :D], both[:, D:]
+        else:
+            rank, world = 0, 1
+            ih, inorm = K.l2norm_fwd(img)
+            th, tnorm = K.l2norm_fwd(txt)
+            ih_all, th_all = ih, th
+            keys_all = keys
+        Bg = B * world
+        off = rank * B
+        S1 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local images x all texts
+        S2 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local texts  x all images
+        K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=1.0)
+        K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=1.0)
+        # forward and backward of the head in one pass per block: S <- t * g
+        _, parts = K.sigmoid_pairs_fwd_bwd_inplace(S1, off, keys, keys_all, theta, bias)
+        K.sigmoid_pairs_fwd_bwd_inplace(S2, off, keys, keys_all, theta, bias, partials=False)
+        loss = K.sigmoid_pairs_loss(parts[0], 1.0 / Bg)
+        if dist_on:
+            dist.all_reduce(loss, group=group)
+        # the two scalars are saved as the inputs themselves (their `.grad` is written in backward; autograd's version check
+        # refuses one that was updated in place in between)
+        ctx.save_for_backward(S1, S2, parts, ih, th, ih_all, th_all, inorm, tnorm, log_scale, logit_bias)
+        ctx.Bg = Bg
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        S1, S2, parts, ih, th, ih_all, th_all, inorm, tnorm, log_scale, logit_bias = ctx.saved_tensors
+        Bg = ctx.Bg
+        B, D = ih.shape
+        dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
+        dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
+        K.gemm(S1, th_all, dih, B, D, Bg, False, False, alpha=1.0 / Bg)
+        K.gemm(S2, ih_all, dth, B, D, Bg, False, False, alpha=1.0 / Bg)
+        di = K.l2norm_bwd(dih, ih, inorm)
+        dt = K.l2norm_bwd(dth, th, tnorm)
+        g = gloss.reshape(()).contiguous()
+        grads = [None, None]
+        for k, (p, plane) in enumerate(((log_scale, parts[1]), (logit_bias, parts[2]))):
+            if not ctx.needs_input_grad[2 + k]:
+                continue
+            # straight into a leaf parameter's `.grad` (the flat gradient buffer's slot); a non-leaf gets a fresh tensor
+            if p.is_leaf:
+                sink = GradSink([p])
+                dst, accumulate = sink.dst(0)
+                K.logit_scale_grad(plane, None, g, 1.0 / Bg, dst, accumulate)
+                grads[k] = sink.result()[0]
+            else:
+                grads[k] = torch.empty_like(p)
+                K.logit_scale_grad(plane, None, g, 1.0 / Bg, grads[k], False)
+        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), grads[0], grads[1], None, None
+
+
+def sigmoid_pairs_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, log_scale: torch.Tensor, logit_bias: torch.Tensor, group=None,
+                       keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Pairwise sigmoid loss over the global batch (all ranks of `group`, or the default group when initialised): every (image,
+    report) pair is an independent binary problem on x = exp(log_scale) * cos + logit_bias, summed and divided by the global batch
+    size (= `F.binary_cross_entropy_with_logits(x, positive, reduction="sum") / Bg`).
+
+    `log_scale` (theta = log(1/tau)) and `logit_bias` are 0-d or [1] fp32 tensors on the embeddings' device, read on the device;
+    each may be a parameter (its gradient is produced, written straight into a leaf's own `.grad` where it has one) or a plain
+    constant.  `keys`: as in `infonce_loss`: pairs with equal keys are positives of each other; None: only a pair's own two
+    halves are.  A row may have no positive at all.  The scalars must not be updated in place between forward and backward."""
+    return _SigmoidPairs.apply(img_emb, txt_emb, log_scale, logit_bias, group, keys)
+
+
 @torch.no_grad()
 def similarity_logits(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
     """normalize(img) @ normalize(txt).T / tau — the zero-shot score matrix (trash/lower_bound_mcs.py:79-117)."""

@@ -1213,6 +1213,59 @@ def logit_scale_grad(part1, part2, upstream, scale: float, out, accumulate: bool
     return out
 
 
+def sigmoid_partials_numel(rows: int, cols: int) -> int:
+    """floats of the `partials` output of `sigmoid_pairs_fwd_bwd_inplace`: three planes of rows * ceil(cols / 1024) (include/cxrk.h)"""
+    return 3 * scaled_partials_numel(rows, cols)
+
+
+def _scalar(t, what):
+    _chk(t, what)
+    if t.numel() != 1 or t.dim() > 1:
+        raise ValueError(f"{what} must be a 0-d or [1] fp32 tensor, got shape {tuple(t.shape)}")
+    return t
+
+
+def sigmoid_pairs_fwd_bwd_inplace(C, diag_off, keys_row, keys_col, log_scale, bias, partials: bool = True):
+    """C <- exp(log_scale) * g in place, g the gradient of the pairwise sigmoid loss on x = exp(log_scale) * C + bias (both device
+    scalars: no host sync).  Positives: column diag_off + i of row i, or, with keys (both or neither), the columns whose key equals
+    the row's.  Returns (C, partials): with `partials` a fresh [3, rows * ceil(cols / 1024)] tensor whose planes sum to the loss
+    terms, g * (x - bias) and g (for `sigmoid_pairs_loss` / `logit_scale_grad`); without, None and no sums are formed."""
+    lib = _lib.load()
+    _chk(C, "sigmoid_pairs.C")
+    if C.dim() != 2 or (C.shape[1] > 1 and C.stride(1) != 1):
+        raise ValueError(f"sigmoid_pairs.C must be a 2-d block with contiguous columns, got shape {tuple(C.shape)} strides {C.stride()}")
+    rows, cols = C.shape
+    if (keys_row is None) != (keys_col is None):
+        raise ValueError("sigmoid_pairs: keys_row and keys_col go together (both or neither)")
+    if keys_row is not None:
+        _keys(keys_row, rows, "sigmoid_pairs.keys_row"), _keys(keys_col, cols, "sigmoid_pairs.keys_col")
+    part = torch.empty(3, scaled_partials_numel(rows, cols), dtype=torch.float32, device=C.device) if partials else None
+    ld = C.stride(0) if rows > 1 else max(cols, C.stride(0))
+    check(lib.cxrk_sigmoid_pairs_fwd_bwd_inplace(_p(C), ld, rows, cols, int(diag_off), _p(keys_row), _p(keys_col),
+                                                 _p(_scalar(log_scale, "sigmoid_pairs.log_scale")), _p(_scalar(bias, "sigmoid_pairs.bias")),
+                                                 _p(part), _stream()),
+          "cxrk_sigmoid_pairs_fwd_bwd_inplace")
+    return C, part
+
+
+def sigmoid_pairs_loss(partials, scale: float, out=None, accumulate: bool = False):
+    """out[0] (+)= scale * sum(partials), one block, fixed order; `out` a one-element fp32 tensor (a fresh 0-d one when None)."""
+    lib = _lib.load()
+    _chk(partials, "sigmoid_pairs_loss.partials")
+    if not partials.is_contiguous() or partials.numel() < 1:
+        raise ValueError("sigmoid_pairs_loss.partials must be contiguous and non-empty")
+    if out is None:
+        if accumulate:
+            raise ValueError("sigmoid_pairs_loss: accumulate needs an `out` to add to")
+        out = torch.empty((), dtype=torch.float32, device=partials.device)
+    _chk(out, "sigmoid_pairs_loss.out")
+    if out.numel() != 1:
+        raise ValueError(f"sigmoid_pairs_loss.out must hold one element, got shape {tuple(out.shape)}")
+    check(lib.cxrk_sigmoid_pairs_loss(_p(partials), partials.numel(), float(scale), _p(out), int(accumulate), _stream()),
+          "cxrk_sigmoid_pairs_loss")
+    return out
+
+
 def clamp_inplace(x, lo: float, hi: float):
     """x <- min(max(x, lo), hi) in place on a dense tensor; a NaN stays a NaN."""
     lib = _lib.load()
