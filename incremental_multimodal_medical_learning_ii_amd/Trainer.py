@@ -31,6 +31,8 @@ Two extensions behind the same entry points (both off unless asked for):
     inside the training step; `val` / `test` never augment.  `"retrieval": True | (k, ...)` makes `val` / `test`
     also encode each batch's reports and add image<->text retrieval over the whole split (Recall@K, median / mean rank, both
     directions) to the returned dict and the writer as `Retrieval/i2t R@1`, ...; off by default.
+    `"micro_batch": n` runs the encoders on at most n of a rank's rows at a time (gradient cache): the same loss
+    and update as the unchunked step up to fp32 summation order, at the peak memory of one chunk.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -171,6 +173,7 @@ class Trainer:
                                                   **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
                                                   **({"loss": je["contrastive_loss"]} if "contrastive_loss" in je else {}),
                                                   **({"sigmoid_bias": je["sigmoid_bias"]} if je.get("sigmoid_bias") is not None else {}),
+                                                  **({"micro_batch": je["micro_batch"]} if je.get("micro_batch") is not None else {}),
                                                   **({"augment": je["augment"], "augment_seed": je.get("augment_seed")}
                                                      if je.get("augment") not in (None, False) else {}))
             print("*** JOINT ENCODER TRAINING (%s over the global batch): no adapters ***"

@@ -32,6 +32,12 @@ and hands the image model one call descriptor per `step` (spec, seed, counter, t
 NCHW -> NHWC boundary transform then samples each image through its own random affine map and jitters brightness / contrast.  The
 draws are keyed by the global image index, so a sharded step augments exactly as the single-process step on the global batch does.
 `augment=None` (the default) issues exactly the calls it always did.
+
+`micro_batch=n`: the step runs the encoders on at most n of this rank's rows at a time (the gradient-cache scheme):
+every chunk but the last is embedded without keeping activations, the loss runs once on all embeddings, and each chunk is then
+run again with its graph to take its slice of dL/d(embedding) through the encoders into the flat gradient buffer.  The loss, its
+collectives and the update are those of the unchunked step up to fp32 summation order; the peak memory is that of one chunk.
+`micro_batch=None` (the default) or n >= this rank's rows issues exactly the calls it always did.
 """
 from __future__ import annotations
 
@@ -207,12 +213,34 @@ SIGMOID_BIAS = -10.0                          # SigLIP's initial bias: the Bg^2 
 LOG_SCALE_BOUNDS = (0.0, math.log(100.0))     # CLIP / open_clip: tau in [0.01, 1]
 
 
+def check_micro_batch(micro_batch) -> Optional[int]:
+    """None, or an integer >= 1 (bools, floats and values <= 0 are refused)"""
+    if micro_batch is None:
+        return None
+    if isinstance(micro_batch, bool) or not isinstance(micro_batch, int) or micro_batch < 1:
+        raise ValueError(f"micro_batch must be None or an integer >= 1, got {micro_batch!r}")
+    return micro_batch
+
+
+def micro_slices(n: int, micro_batch: int) -> Tuple[Tuple[int, int], ...]:
+    """The (lo, hi) row ranges of the encoder calls of a step on n rows with at most `micro_batch` rows per call: contiguous, in
+    order, the last one ragged.  (8, 3) -> ((0, 3), (3, 6), (6, 8)); any micro_batch >= n -> ((0, n),)."""
+    m = check_micro_batch(micro_batch)
+    if m is None:
+        raise ValueError("micro_slices: micro_batch must be an integer >= 1, got None")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"micro_slices: the number of rows must be an integer >= 1, got {n!r}")
+    return tuple((lo, min(lo + m, n)) for lo in range(0, n, m))
+
+
 class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
                  optim: str = "adam", positives: Optional[str] = None, learn_temperature: bool = False,
                  log_scale_bounds: Tuple[float, float] = LOG_SCALE_BOUNDS, augment: Optional[AugmentSpec] = None,
-                 augment_seed: Optional[int] = None, loss: str = "infonce", sigmoid_bias: Optional[float] = None):
+                 augment_seed: Optional[int] = None, loss: str = "infonce", sigmoid_bias: Optional[float] = None,
+                 micro_batch: Optional[int] = None):
+        self.micro_batch = check_micro_batch(micro_batch)
         if positives not in POSITIVES:
             raise ValueError(f"positives must be None, 'labels' or 'text', got {positives!r}")
         if loss not in LOSSES:
@@ -419,10 +447,15 @@ class JointContrastiveTrainer:
         if keys is not None:
             keys = keys.to(images.device, non_blocking=True)
         self.text_model.dropout_row_offset = self.rank * int(input_ids.shape[0])
+        img, txt = self._encode_pair(images, input_ids, attention_mask)
+        return self._loss(img, txt, keys)
+
+    def _encode_pair(self, images, input_ids, attention_mask) -> Tuple[torch.Tensor, torch.Tensor]:
+        """both encoders on the same rows -> (image embeddings, text embeddings), the text encoder on the second stream"""
         if not (self.two_streams and images.is_cuda):
             img = self.image_model(images)
             txt = self.text_model.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
-            return self._loss(img, txt, keys)
+            return img, txt
         if self._text_stream is None:
             self._text_stream = torch.cuda.Stream(device=images.device)
         cur = torch.cuda.current_stream(images.device)
@@ -432,7 +465,7 @@ class JointContrastiveTrainer:
         img = self.image_model(images)
         cur.wait_stream(self._text_stream)
         txt.record_stream(cur)
-        return self._loss(img, txt, keys)
+        return img, txt
 
     def _loss(self, img, txt, keys):
         if self.loss == "sigmoid":
@@ -455,7 +488,14 @@ class JointContrastiveTrainer:
         tag fired) is reduced after `backward()` returns.  Precondition, asserted: each encoder runs ONCE per step inside
         `forward_loss` — a second call of an encoder in the same graph would have its range reduced before the second
         contribution was accumulated.  A rank that raises inside `backward()` after a range was started leaves its peers inside that
-        collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog)."""
+        collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog).
+
+        With `micro_batch` < this rank's rows the forward and backward run chunk by chunk (`_chunked_forward_backward`); the hook
+        is then handed only to the encoder calls of the step's LAST backward, after which every range is complete."""
+        slices = ((0, int(images.shape[0])),) if self.micro_batch is None else micro_slices(int(images.shape[0]), self.micro_batch)
+        chunked = len(slices) > 1
+        if chunked:
+            self._require_eval_batchnorm()
         self.optimizer.zero_grad()
         self.sync_dropout_state()
         self.sync_augment_state()
@@ -472,23 +512,102 @@ class JointContrastiveTrainer:
                 fired.append(tag)
                 works.extend(self.optimizer.all_reduce_span(span[0], span[1], self.group))
 
-            self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = on_ready
-            try:
-                loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
-            finally:
-                self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
-            loss.backward()
+            if chunked:
+                loss = self._chunked_forward_backward(images, input_ids, attention_mask, labels, keys, slices, on_ready)
+            else:
+                self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = on_ready
+                try:
+                    loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
+                finally:
+                    self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
+                loss.backward()
             self.last_overlapped = tuple(fired)
             self.optimizer.all_reduce_grads(self.group, skip=[self._spans[t] for t in fired], pending=works)
         else:
-            loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)
-            loss.backward()
+            if chunked:
+                loss = self._chunked_forward_backward(images, input_ids, attention_mask, labels, keys, slices, None)
+            else:
+                loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)
+                loss.backward()
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)
         self.optimizer.step()
         if self.logit_scale is not None:
             K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)
         return loss.detach()
+
+    def _require_eval_batchnorm(self) -> None:
+        """a micro-batched step is the unchunked step only while the rows of a batch are independent up to the loss"""
+        if any(m.training for m in self.image_model.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)):
+            raise ValueError("JointContrastiveTrainer(micro_batch=...): the image model's BatchNorm layers are in training mode; batch "
+                             "statistics depend on the chunk, so a micro-batched step would not be the step on the whole batch. "
+                             "Call image_model.eval() / .train(my_freeze=True), or construct the trainer with micro_batch=None")
+
+    def _chunked_forward_backward(self, images, input_ids, attention_mask, labels, keys, slices, on_ready) -> torch.Tensor:
+        """Forward and backward of one step in the chunks `slices` -> the loss, detached.
+
+          1. chunks 0..n-2 run through both encoders save-free (`ImageModel.save_free`, `CXRBertModel.save_free`): the same kernels
+             and the same bits as a normal forward, nothing kept; their embeddings become one leaf that requires grad;
+          2. the last chunk is forwarded normally; the loss head runs once on the [rows, D] pair (cache + last chunk), with its usual
+             collectives; `loss.backward()` runs the last chunk's encoder backward, writes theta's and b's gradient and leaves
+             dL/d(embedding) of the cached rows in the leaves' `.grad`;
+          3. chunks 0..n-2 are forwarded again with their graph, and each takes its slice of the cached gradient through both
+             encoders: the kernels accumulate into the flat gradient buffer (`gradsink`).
+
+        At most one chunk's activations are alive at any time.  Every encoder call of the step uses the same dropout and augment
+        (seed, counter), pinned here without going through the public setters (whose version bump would cost a broadcast), and the
+        row offset rank * rows + chunk.lo; both counters advance once.  `on_ready` (data parallel) is handed only to the calls of
+        the last backward, chunk n-2's: each range is reduced once, after its last contribution."""
+        rows = int(images.shape[0])
+        im, tm = self.image_model, self.text_model
+        keys = self.pair_keys(input_ids, attention_mask, labels, keys)
+        if keys is not None:
+            keys = keys.to(images.device, non_blocking=True)
+        aug = None
+        if self._augment is not None:
+            aug = (self._augment[0], self._augment[1])
+            self._augment[1] = aug[1] + 1
+        drop = getattr(tm, "_dropout", None)          # [seed, counter] of an opted-in text model
+        drop_before = drop[1] if drop is not None else None
+        base = self.rank * rows
+
+        def encode(lo, hi, save_free=False, hook=None):
+            if aug is not None:
+                im.augment_call = AugmentCall(self.augment, aug[0], aug[1], base + lo)
+            tm.dropout_row_offset = base + lo
+            im.save_free = tm.save_free = save_free
+            im.grad_ready_hook = tm.grad_ready_hook = hook
+            try:
+                return self._encode_pair(images[lo:hi], input_ids[lo:hi], attention_mask[lo:hi])
+            finally:
+                im.augment_call = None
+                im.save_free = tm.save_free = False
+                im.grad_ready_hook = tm.grad_ready_hook = None
+
+        cached = [encode(lo, hi, save_free=True) for lo, hi in slices[:-1]]            # pass 1: advances no counter
+        ci = torch.cat([i for i, _ in cached]).requires_grad_()
+        ct = torch.cat([t for _, t in cached]).requires_grad_()
+        del cached
+        img, txt = encode(*slices[-1])                                                   # advances the dropout counter, once
+        drop_after = drop[1] if drop is not None else None
+        loss = self._loss(torch.cat((ci, img)), torch.cat((ct, txt)), keys)
+        del img, txt
+        loss.backward()
+        loss = loss.detach()
+        gi, gt = ci.grad, ct.grad
+        try:
+            for k, (lo, hi) in enumerate(slices[:-1]):
+                if drop is not None:
+                    drop[1] = drop_before                                                # the masks of pass 1
+                out = encode(lo, hi, hook=on_ready if k == len(slices) - 2 else None)
+                pairs = [(o, g[lo:hi]) for o, g in zip(out, (gi, gt)) if o.requires_grad]   # a frozen encoder has no backward
+                del out
+                torch.autograd.backward([o for o, _ in pairs], [g for _, g in pairs])
+                del pairs
+        finally:
+            if drop is not None:
+                drop[1] = drop_after
+        return loss
 
     def _dist_group(self):
         """the group to hand to the collectives of an evaluation: None in a single process, else this trainer's (the default group

@@ -124,6 +124,7 @@ def _setup(args, kind):
                                              "learn_temperature": bool(getattr(args, "learn_temperature", False)),
                                              "contrastive_loss": getattr(args, "contrastive_loss", None) or "infonce",
                                              "sigmoid_bias": getattr(args, "sigmoid_bias", None),
+                                             "micro_batch": getattr(args, "micro_batch", None),
                                              "augment": augment_from_args(args),
                                              "retrieval": retrieval_from_args(args)})
     else:
@@ -287,6 +288,9 @@ def make_parser():
     ap.add_argument("--retrieval", type=int, nargs="*", default=None, metavar="K",
                     help="--joint: val / test also report image<->text retrieval over the whole split (Recall@K, median / mean rank, "
                          "both directions, DESIGN.md 5.5); without values K = 1 5 10")
+    ap.add_argument("--micro-batch", type=int, default=None, metavar="N",
+                    help="--joint: run the encoders on at most N of a rank's rows at a time (gradient cache, DESIGN.md 5.7): the loss "
+                         "and update of the whole batch at the peak memory of one chunk; default: the whole batch at once")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -317,6 +321,11 @@ def main(argv=None):
     if args.retrieval is not None and not args.joint:
         raise SystemExit("--retrieval ranks the reports of the evaluation batches against their images and needs --joint (the adapter "
                          "schedules evaluate on pre-computed image embeddings without reports)")
+    if args.micro_batch is not None and not args.joint:
+        raise SystemExit("--micro-batch chunks the encoder calls of the north-star step and needs --joint (the adapter schedules "
+                         "train on pre-computed embeddings)")
+    if args.micro_batch is not None and args.micro_batch < 1:
+        raise SystemExit(f"--micro-batch must be >= 1, got {args.micro_batch}")
     augment_from_args(args)      # --aug-* without --augment
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)

@@ -96,6 +96,9 @@ class ImageModel(nn.Module):
         # [B,1,H,W] images; no-grad forwards, `forward_stages`, `calibrate_batchnorm_` and the inference engines never augment.
         # Set and cleared by the joint trainer per step.
         self.augment_call = None
+        # True: the forward keeps nothing for a backward (its outputs carry no graph) yet still applies `augment_call`; no hook is
+        # attached.  Pass 1 of the joint trainer's micro-batched step sets and clears it around its calls.
+        self.save_free = False
         if pretrained_model_path is not None:
             if not isinstance(pretrained_model_path, (str, Path)):
                 raise TypeError(f"Expected a string or Path, got {type(pretrained_model_path)}")
@@ -157,7 +160,8 @@ class ImageModel(nn.Module):
                                "(there is no CPU fallback; the CPU oracle lives in oracle/ and is test-only)")
         if x.dtype != torch.float32:
             raise ValueError(f"expected fp32 images, got {x.dtype}")
-        augment = self.augment_call if torch.is_grad_enabled() else None
+        save_free = bool(self.save_free)
+        augment = self.augment_call if (torch.is_grad_enabled() or save_free) else None
         if x.dim() != 4 or not (x.shape[1] == 3 or (augment is not None and x.shape[1] == 1)):
             raise ValueError(f"ImageModel expects [B,3,H,W] input (ExpandChannels, transforms.py:12-38), got {tuple(x.shape)}")
         if augment is not None and x.requires_grad:
@@ -165,9 +169,9 @@ class ImageModel(nn.Module):
         momentum = self._bn_mode()
         self.prepare_()
         params, bufs = self._tensors()
-        hook = self.grad_ready_hook if torch.is_grad_enabled() else None
-        meta = IE.EncodeMeta(self._specs, self._blocks, len(params), want_patch, hook, momentum, augment)
-        with torch.set_grad_enabled(torch.is_grad_enabled() and not self.freeze_encoder):
+        hook = self.grad_ready_hook if (torch.is_grad_enabled() and not save_free) else None
+        meta = IE.EncodeMeta(self._specs, self._blocks, len(params), want_patch, hook, momentum, augment, save_free)
+        with torch.set_grad_enabled(torch.is_grad_enabled() and not self.freeze_encoder and not save_free):
             emb, patch = IE.ImageEncodeFn.apply(x, meta, *params, *bufs)
         if momentum is not None:       # the kernels updated running_mean / running_var in place; the counter is host bookkeeping
             with torch.no_grad():

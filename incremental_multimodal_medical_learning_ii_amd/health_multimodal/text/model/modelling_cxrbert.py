@@ -76,6 +76,9 @@ class CXRBertModel(BertForMaskedLM):
         self._dropout_version = 0
         # global sequence index of this process's first row (data parallel: rank * local rows; set by the joint trainer)
         self.dropout_row_offset = 0
+        # True: the encode call keeps nothing for a backward (no graph, no hook), still draws this call's dropout masks and leaves
+        # the call counter where it is.  Pass 1 of the joint trainer's micro-batched step sets and clears it.
+        self.save_free = False
 
     # ------------------------------------------------------------------ dropout
     def enable_dropout_(self, seed: Optional[int] = None) -> "CXRBertModel":
@@ -124,7 +127,8 @@ class CXRBertModel(BertForMaskedLM):
         if not self.training or self._dropout is None or (ph <= 0 and pa <= 0):
             return None
         seed, counter = self._dropout
-        self._dropout[1] = counter + 1
+        if not self.save_free:
+            self._dropout[1] = counter + 1
         return TE.Dropout(seed, counter, self.dropout_row_offset, ph, pa)
 
     # ------------------------------------------------------------------ parameter plumbing
@@ -164,7 +168,8 @@ class CXRBertModel(BertForMaskedLM):
             raise NotImplementedError(f"hidden_act={cfg.hidden_act!r}: only erf-GELU (CXR-BERT) is implemented")
         return TE.encode(self._hot_params(), input_ids, attention_mask, cfg.num_hidden_layers,
                          cfg.num_attention_heads, cfg.layer_norm_eps, cls_only, want_last,
-                         on_grads_ready=self.grad_ready_hook if torch.is_grad_enabled() else None, dropout=self._next_dropout())
+                         on_grads_ready=self.grad_ready_hook if torch.is_grad_enabled() else None, dropout=self._next_dropout(),
+                         save_free=bool(self.save_free))
 
     @torch.no_grad()
     def _mlm_logits(self, last_hidden: torch.Tensor) -> torch.Tensor:

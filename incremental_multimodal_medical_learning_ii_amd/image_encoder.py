@@ -113,6 +113,7 @@ class EncodeMeta(NamedTuple):
     on_grads_ready: Optional[Callable] = None     # per-call hook of the backward (ImageModel.grad_ready_hook at forward time)
     bn_momentum: Optional[float] = None           # None: eval-mode BatchNorm; float: train mode (ImageModel.train())
     augment: Optional[AugmentCall] = None         # on-device augmentation of this call (ImageModel.augment_call at forward time)
+    save_free: bool = False                       # keep nothing for a backward (ImageModel.save_free: pass 1 of a micro-batched step)
 
 
 def _filter_rsc(w: torch.Tensor) -> torch.Tensor:
@@ -655,7 +656,7 @@ class ImageEncodeFn(torch.autograd.Function):
     def forward(ctx, x, meta, *tensors):
         ctx.set_materialize_grads(False)
         params, bufs = tensors[:meta.n_params], tensors[meta.n_params:]
-        save = any(t.requires_grad for t in params)
+        save = any(t.requires_grad for t in params) and not meta.save_free
         p = [t.detach() for t in params]
         b = [t.detach() for t in bufs]
         emb, patch, state = _forward(meta.specs, meta.blocks, p, b, x.detach(), save, meta.want_patch, keep_stem=_capture is not None,

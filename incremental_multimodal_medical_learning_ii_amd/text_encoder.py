@@ -157,13 +157,17 @@ def _weights(p: Sequence[torch.Tensor], n_layers: int, pl: bool):
 
 
 def _forward(p: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.Tensor], n_layers: int, n_heads: int,
-             eps: float, save: bool, cls_only: bool = False, drop: Optional[Dropout] = None):
+             eps: float, save: bool, cls_only: bool = False, drop: Optional[Dropout] = None, recompute_twin: bool = False):
     """cls_only: the caller consumes only the projected CLS embedding (`get_projected_text_embeddings`,
     modelling_cxrbert.py:117-141 -> `hidden_states[-1][:, 0, :]`).  Everything in the LAST layer after the attention is
     row-wise, so it runs on the N CLS rows instead of N*L tokens (output projection, both LayerNorms, the FFN: 75 % of that
     layer's GEMM work); the returned `last` is then [N, H] (the CLS rows).
     drop: train-mode dropout (None: eval semantics).  At the attention-output and FFN-output sites the GEMM then leaves the residual
-    to the LayerNorm kernel, LN(keep * s * dense + residual); the CLS rows draw the same masks as in the full path."""
+    to the LayerNorm kernel, LN(keep * s * dense + residual); the CLS rows draw the same masks as in the full path.
+    recompute_twin (with save=False): the pass must give the bits of the saving pass that will recompute it (the save-free forward of
+    a micro-batched step).  Every kernel but one only skips its stores when it is told to keep nothing; the FFN-up
+    GEMM without its pre-activation copy runs another instantiation of the epilogue, in which the compiler contracts the GELU's
+    arithmetic differently (last-bit differences in split-bf16 mode), so this pass hands it a scratch copy to write."""
     N, L = ids.shape
     word, pos, typ, eg, eb = p[0:5]
     H = word.shape[1]
@@ -189,7 +193,7 @@ def _forward(p: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.
         else:
             t1 = _lin(ctx_r, wo_w, bo, pl)
             a, xhat1, rstd1 = K.residual_ln_fwd(t1, x_r, g1, b1, eps, save=save, out_planes=pl, drop=d_ao, rows_per_seq=rps)
-        u_pre = torch.empty(t1.shape[0], wi.shape[0], dtype=torch.float32, device=t1.device) if save else None
+        u_pre = torch.empty(t1.shape[0], wi.shape[0], dtype=torch.float32, device=t1.device) if (save or recompute_twin) else None
         u = _lin(a, wi_w, bi, pl, act=K.ACT_GELU, preact_out=u_pre, out_planes=True)
         if d_fo is None:
             t2 = _lin(u, wo2_w, bo2, pl, residual=a)
@@ -354,12 +358,13 @@ class CXRBertEncodeFn(torch.autograd.Function):
     CLS rows when cls_only; an empty tensor when the caller does not want it)."""
 
     @staticmethod
-    def forward(ctx, ids, mask, n_layers, n_heads, eps, cls_only, want_last, on_grads_ready, drop, *params):
+    def forward(ctx, ids, mask, n_layers, n_heads, eps, cls_only, want_last, on_grads_ready, drop, save_free, *params):
         ctx.set_materialize_grads(False)
         ctx.on_grads_ready = on_grads_ready
-        save = any(t.requires_grad for t in params)
+        save = any(t.requires_grad for t in params) and not save_free
         p = [t.detach() for t in params]
-        proj, last, state = _forward(p, ids, mask, n_layers, n_heads, eps, save, cls_only, drop)   # state keeps (seed, counter)
+        proj, last, state = _forward(p, ids, mask, n_layers, n_heads, eps, save, cls_only, drop,   # state keeps (seed, counter)
+                                     recompute_twin=bool(save_free))
         if save:
             ctx.state = state
             ctx.cfg = (n_layers, n_heads, cls_only)
@@ -387,16 +392,18 @@ class CXRBertEncodeFn(torch.autograd.Function):
         hook = ctx.on_grads_ready
         if hook is not None and all(r is None for r in res):
             hook("text")   # every gradient of this encoder already sits in its `.grad` view: the data-parallel step starts reducing them now
-        return (None, None, None, None, None, None, None, None, None) + res
+        return (None, None, None, None, None, None, None, None, None, None) + res
 
 
 def encode(params: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[torch.Tensor], n_layers: int,
            n_heads: int, eps: float = 1e-12, cls_only: bool = False, want_last: bool = True,
-           on_grads_ready=None, dropout: Optional[Dropout] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+           on_grads_ready=None, dropout: Optional[Dropout] = None, save_free: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """`on_grads_ready(tag)`: optional callable bound to THIS call (it travels on the autograd node, not in a module global); the
     backward calls it with "text" on the stream it runs on once every parameter gradient of the call has been written in place
     (`gradsink`).  contrastive.JointContrastiveTrainer starts the encoder's gradient all-reduce from it.
-    `dropout`: train-mode dropout of this call (None, or both probabilities 0: eval semantics, the kernel sequence of eval mode)."""
+    `dropout`: train-mode dropout of this call (None, or both probabilities 0: eval semantics, the kernel sequence of eval mode).
+    `save_free`: keep nothing for a backward: the outputs carry no graph and no hook, the same kernels run with `save=False` and
+    still apply `dropout` (pass 1 of the joint trainer's micro-batched step)."""
     if ids.dtype != torch.int64:
         ids = ids.to(torch.int64)
     if mask is not None and mask.dtype != torch.int64:
@@ -405,4 +412,7 @@ def encode(params: Sequence[torch.Tensor], ids: torch.Tensor, mask: Optional[tor
     mask = mask.contiguous() if mask is not None else None
     if dropout is not None and dropout.p_hidden <= 0 and dropout.p_attn <= 0:
         dropout = None
-    return CXRBertEncodeFn.apply(ids, mask, n_layers, n_heads, eps, bool(cls_only), bool(want_last), on_grads_ready, dropout, *params)
+    if save_free:
+        with torch.no_grad():
+            return CXRBertEncodeFn.apply(ids, mask, n_layers, n_heads, eps, bool(cls_only), bool(want_last), None, dropout, True, *params)
+    return CXRBertEncodeFn.apply(ids, mask, n_layers, n_heads, eps, bool(cls_only), bool(want_last), on_grads_ready, dropout, False, *params)
