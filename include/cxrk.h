@@ -440,10 +440,33 @@ int cxrk_scale_mask(const float* x, const float* mask_src, const float* alpha_de
  * adam_fused:   torch.optim.Adam defaults (Trainer.py:172-175), one launch over a flat parameter buffer.
  * sgd:          optim.SGD (Trainer.py:176-178).
  * weight_reset: Trainer.myIncremental per tensor (Trainer.py:1562-1572); counters[0] += #restored.
+ * grad_sqnorm:  partials[b] = sum of g[i]^2 over block b's share of g, b < nparts(n) = min(1024, max(1, ceil(floor(n / 4) / 1024)));
+ *               cxrk_grad_sqnorm_partials_bytes(n) = 4 * nparts(n).  The partial sums are an output that adamw_clipped reads, sized
+ *               by the caller: ws_bytes below that size (or partials == NULL) gives CXRK_ERR_WS and nothing is written; no
+ *               256-byte alignment is asked of it.  float4 loads (g 16-byte aligned), four accumulators per thread, the n % 4 tail in
+ *               block 0, no atomics.  Partition and summation order depend on n alone, never on the device: the same buffer gives
+ *               the same bits in every run and on every data-parallel rank.  g is read only.
+ * adamw_clipped: torch.optim.AdamW (decoupled decay) behind torch.nn.utils.clip_grad_norm_, one launch over the flat buffers.
+ *               Every block re-derives total = sum partials[0..nparts(n)) in one fixed order;  norm = |grad_scale| * sqrt(total);
+ *               coef = min(max_norm / (norm + 1e-6), 1), a NaN norm giving a NaN coef; max_norm = +inf gives coef = 1 exactly
+ *               (monitoring).  partials == NULL with max_norm <= 0: no clipping, coef = 1, nothing is read; partials == NULL with
+ *               max_norm > 0: CXRK_ERR_ARG; partials given with max_norm <= 0: the norm is reported, coef = 1.  ws_bytes is the size
+ *               of partials (CXRK_ERR_WS below cxrk_grad_sqnorm_partials_bytes(n)).  Per element, in AdamW's order:
+ *               gg = g * (grad_scale * coef);  p *= 1 - lr * weight_decay where the mask says so;  then adam_fused's moment and
+ *               parameter lines without its L2 term: with coef = 1 and no decay applied the result is adam_fused(weight_decay = 0)
+ *               bit for bit.  decay_mask: ceil(n / 4) bytes, one per aligned group of four elements, non-zero = the group decays;
+ *               NULL = every element decays.  g, the mask and the partials are read only (the gradient stays unclipped).
+ *               stats (optional, 2 floats): stats[0] = norm before clipping, stats[1] = coef (0 and 1 without partials), written
+ *               by one thread with ordinary stores.  p, g, m, v 16-byte aligned, n > 0, step >= 1 as for adam_fused.
  */
 int cxrk_adam_fused(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, int step, float grad_scale, hipStream_t stream);
 int cxrk_sgd(float* p, const float* g, long n, float lr, float weight_decay, float grad_scale, hipStream_t stream);
+size_t cxrk_grad_sqnorm_partials_bytes(long n);
+int cxrk_grad_sqnorm(const float* g, long n, float* partials, size_t ws_bytes, hipStream_t stream);
+int cxrk_adamw_clipped(float* p, const float* g, float* m, float* v, const unsigned char* decay_mask, long n, float lr,
+                       float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float max_norm,
+                       const float* partials, size_t ws_bytes, float* stats, hipStream_t stream);
 size_t cxrk_weight_reset_ws_bytes(void);
 int cxrk_weight_reset(float* pnew, const float* pold, long n, float threshold, unsigned long long* counters, float* ws,
                       size_t ws_bytes, hipStream_t stream);

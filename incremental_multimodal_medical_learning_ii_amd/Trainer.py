@@ -33,6 +33,11 @@ Two extensions behind the same entry points (both off unless asked for):
     directions) to the returned dict and the writer as `Retrieval/i2t R@1`, ...; off by default.
     `"micro_batch": n` runs the encoders on at most n of a rank's rows at a time (gradient cache): the same loss
     and update as the unchunked step up to fp32 summation order, at the peak memory of one chunk.
+    `"optim": "adamw"` (overrides the module-level `OPTIM` for the joint trainer only) selects AdamW with decoupled
+    `"weight_decay"` (default 0.01; biases and norm parameters do not decay) and, with `"max_grad_norm"`, clipping of the global
+    gradient norm (`inf`: monitoring only); `"warmup_steps"`, `"total_steps"`, `"lr_decay"` ("constant" | "linear" | "cosine") and
+    `"min_lr_ratio"` put a warmup / decay schedule around `lr` for any optimiser.  `train` then logs `train/lr` and,
+    with "max_grad_norm", `train/grad_norm` once per epoch.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -168,7 +173,10 @@ class Trainer:
             if OPTIM not in ("adam", "sgd"):
                 raise Exception
             self._joint = JointContrastiveTrainer(self.image_model, self.bert_encoder.model, lr=lr,
-                                                  temperature=float(je.get("temperature", 0.07)), group=process_group, optim=OPTIM,
+                                                  temperature=float(je.get("temperature", 0.07)), group=process_group,
+                                                  optim=je["optim"] if je.get("optim") is not None else OPTIM,
+                                                  **{k: je[k] for k in ("weight_decay", "max_grad_norm", "warmup_steps", "total_steps",
+                                                                        "lr_decay", "min_lr_ratio") if je.get(k) is not None},
                                                   positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
                                                   **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
                                                   **({"loss": je["contrastive_loss"]} if "contrastive_loss" in je else {}),
@@ -714,6 +722,19 @@ class Trainer:
             self.writer.add_scalar('train/temperature', self._joint.current_temperature(), epoch)
             if self._joint.logit_bias is not None:
                 self.writer.add_scalar('train/bias', self._joint.current_bias(), epoch)
+        self._log_optimiser(epoch)
+
+    def _log_optimiser(self, epoch):
+        """with "optim": "adamw" or a learning-rate schedule: the learning rate of the epoch's last step, and with "max_grad_norm" that
+        step's gradient norm before clipping (the one read-back of the norm), once per epoch"""
+        if self._joint is None or self.writer is None:
+            return
+        opt = self._joint.optimizer
+        adamw = isinstance(opt, cxr_optim.AdamW)
+        if adamw or self._joint.schedule is not None:
+            self.writer.add_scalar('train/lr', opt.lr, epoch)
+        if adamw and opt.max_grad_norm is not None and opt.steps > 0:
+            self.writer.add_scalar('train/grad_norm', opt.current_grad_norm(), epoch)
 
     @staticmethod
     def _parse_retrieval(opt):

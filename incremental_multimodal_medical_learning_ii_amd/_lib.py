@@ -103,6 +103,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_scale_mask": (I, [P, P, P, F, L, P, P]),
     "cxrk_adam_fused": (I, [P, P, P, P, L, F, F, F, F, F, I, F, P]),
     "cxrk_sgd": (I, [P, P, L, F, F, F, P]),
+    "cxrk_grad_sqnorm_partials_bytes": (Z, [L]),
+    "cxrk_grad_sqnorm": (I, [P, L, P, Z, P]),
+    "cxrk_adamw_clipped": (I, [P, P, P, P, P, L, F, F, F, F, F, I, F, F, P, Z, P, P]),
     "cxrk_weight_reset_ws_bytes": (Z, []),
     "cxrk_weight_reset": (I, [P, P, L, F, P, P, Z, P]),
     "cxrk_gemm_wgrad_splitk": (I, [I, I, I, I]),

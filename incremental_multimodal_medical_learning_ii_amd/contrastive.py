@@ -209,6 +209,7 @@ def retrieval_metrics(img_emb: torch.Tensor, txt_emb: torch.Tensor, keys: Option
 
 POSITIVES = (None, "labels", "text")
 LOSSES = ("infonce", "sigmoid")
+OPTIMS = ("adam", "sgd", "adamw")
 SIGMOID_BIAS = -10.0                          # SigLIP's initial bias: the Bg^2 - Bg negatives start out nearly free
 LOG_SCALE_BOUNDS = (0.0, math.log(100.0))     # CLIP / open_clip: tau in [0.01, 1]
 
@@ -239,8 +240,23 @@ class JointContrastiveTrainer:
                  optim: str = "adam", positives: Optional[str] = None, learn_temperature: bool = False,
                  log_scale_bounds: Tuple[float, float] = LOG_SCALE_BOUNDS, augment: Optional[AugmentSpec] = None,
                  augment_seed: Optional[int] = None, loss: str = "infonce", sigmoid_bias: Optional[float] = None,
-                 micro_batch: Optional[int] = None):
+                 micro_batch: Optional[int] = None, weight_decay: Optional[float] = None, max_grad_norm: Optional[float] = None,
+                 warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, lr_decay: Optional[str] = None,
+                 min_lr_ratio: Optional[float] = None):
+        """`optim="adamw"`: `optim.AdamW` with decoupled `weight_decay` (default 0.01; parameters with ndim <= 1 do
+        not decay) and, with `max_grad_norm`, clipping of the global gradient norm (`inf`: the norm is taken and reported, nothing
+        is clipped).  `warmup_steps` / `total_steps` / `lr_decay` ("constant" | "linear" | "cosine") / `min_lr_ratio`: an
+        `optim.LRSchedule` around `lr`, for every optimiser; with none of them given the learning rate is never touched."""
         self.micro_batch = check_micro_batch(micro_batch)
+        if optim not in OPTIMS:
+            raise ValueError(f"optim must be 'adam', 'sgd' or 'adamw', got {optim!r}")
+        if optim != "adamw" and (weight_decay is not None or max_grad_norm is not None):
+            raise ValueError(f"weight_decay / max_grad_norm are options of optim='adamw'; they were given with optim={optim!r}")
+        self.schedule = None
+        if any(v is not None for v in (warmup_steps, total_steps, lr_decay, min_lr_ratio)):
+            self.schedule = cxr_optim.LRSchedule(lr, warmup_steps=0 if warmup_steps is None else warmup_steps, total_steps=total_steps,
+                                                 decay="constant" if lr_decay is None else lr_decay,
+                                                 min_lr_ratio=0.0 if min_lr_ratio is None else min_lr_ratio)
         if positives not in POSITIVES:
             raise ValueError(f"positives must be None, 'labels' or 'text', got {positives!r}")
         if loss not in LOSSES:
@@ -307,8 +323,9 @@ class JointContrastiveTrainer:
             self.optimizer = cxr_optim.Adam(params + tparams, lr=lr)
         elif optim == "sgd":
             self.optimizer = cxr_optim.SGD(params + tparams, lr=lr)
-        else:
-            raise ValueError(f"optim must be 'adam' or 'sgd', got {optim!r}")
+        else:                        # "adamw": biases, norm parameters, theta and b (everything with ndim <= 1) do not decay
+            self.optimizer = cxr_optim.AdamW(params + tparams, lr=lr, max_grad_norm=max_grad_norm,
+                                             **({"weight_decay": weight_decay} if weight_decay is not None else {}))
         text_model.prepare_()
         self.world, self.rank = 1, 0
         import torch.distributed as dist
@@ -531,6 +548,8 @@ class JointContrastiveTrainer:
                 loss.backward()
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)
+        if self.schedule is not None:    # a host float that the update kernel takes as an argument: no launch, no sync
+            self.optimizer.param_groups[0]["lr"] = self.schedule(self.optimizer.steps + 1)
         self.optimizer.step()
         if self.logit_scale is not None:
             K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)

@@ -125,6 +125,7 @@ def _setup(args, kind):
                                              "contrastive_loss": getattr(args, "contrastive_loss", None) or "infonce",
                                              "sigmoid_bias": getattr(args, "sigmoid_bias", None),
                                              "micro_batch": getattr(args, "micro_batch", None),
+                                             **optimiser_from_args(args, kind, train_loader),
                                              "augment": augment_from_args(args),
                                              "retrieval": retrieval_from_args(args)})
     else:
@@ -140,6 +141,28 @@ def retrieval_from_args(args):
     if ks is None:
         return None
     return True if len(ks) == 0 else tuple(ks)
+
+
+def run_steps(args, kind, train_loader) -> int:
+    """optimiser steps of the whole run: epochs x steps per epoch x tasks (class-inc / data-inc: one loader per task)"""
+    loaders = train_loader if isinstance(train_loader, (list, tuple)) else [train_loader]
+    return int(args.epochs) * sum(len(ld) for ld in loaders)
+
+
+def optimiser_from_args(args, kind=None, train_loader=None) -> dict:
+    """`--optim adamw` / `--weight-decay` / `--clip-grad-norm` / `--warmup-steps` / `--lr-decay` / `--min-lr-ratio` -> the
+    `joint_encoders` keys they set (none of them given: an empty dict).  The schedule spans the whole run, not each task:
+    total_steps is derived from the run's own length."""
+    out = {}
+    if getattr(args, "optim", None) is not None:
+        out["optim"] = args.optim
+    for flag, key in (("weight_decay", "weight_decay"), ("clip_grad_norm", "max_grad_norm"), ("warmup_steps", "warmup_steps"),
+                      ("lr_decay", "lr_decay"), ("min_lr_ratio", "min_lr_ratio")):
+        if getattr(args, flag, None) is not None:
+            out[key] = getattr(args, flag)
+    if any(k in out for k in ("warmup_steps", "lr_decay", "min_lr_ratio")) and train_loader is not None:
+        out["total_steps"] = run_steps(args, kind, train_loader)
+    return out
 
 
 AUG_FLAGS = {"aug_rotate": "rotate_deg", "aug_translate": "translate", "aug_zoom": "zoom", "aug_flip": "flip_p",
@@ -291,6 +314,17 @@ def make_parser():
     ap.add_argument("--micro-batch", type=int, default=None, metavar="N",
                     help="--joint: run the encoders on at most N of a rank's rows at a time (gradient cache, DESIGN.md 5.7): the loss "
                          "and update of the whole batch at the peak memory of one chunk; default: the whole batch at once")
+    ap.add_argument("--optim", default=None, choices=["adam", "sgd", "adamw"],
+                    help="--joint: the optimiser of the north-star step; adamw = decoupled weight decay (biases and norm parameters "
+                         "do not decay) with optional clipping (DESIGN.md 5.8); default: Adam, as the reference")
+    ap.add_argument("--weight-decay", type=float, default=None, metavar="W", help="--optim adamw: decoupled weight decay (default 0.01)")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="C",
+                    help="--optim adamw: clip the global gradient norm to C; inf = report the norm (train/grad_norm) without clipping")
+    ap.add_argument("--warmup-steps", type=int, default=None, metavar="N",
+                    help="--joint: linear learning-rate warmup over the first N optimiser steps of the run")
+    ap.add_argument("--lr-decay", default=None, choices=["constant", "linear", "cosine"],
+                    help="--joint: learning-rate decay after the warmup, to --min-lr-ratio x --lr at the run's last step")
+    ap.add_argument("--min-lr-ratio", type=float, default=None, metavar="R", help="--lr-decay: the final learning rate as a fraction of --lr")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -326,6 +360,12 @@ def main(argv=None):
                          "train on pre-computed embeddings)")
     if args.micro_batch is not None and args.micro_batch < 1:
         raise SystemExit(f"--micro-batch must be >= 1, got {args.micro_batch}")
+    given = [f for f in ("optim", "weight_decay", "clip_grad_norm", "warmup_steps", "lr_decay", "min_lr_ratio") if getattr(args, f) is not None]
+    if given and not args.joint:
+        raise SystemExit("--" + given[0].replace("_", "-") + " configures the optimiser of the north-star step and needs --joint (the "
+                         "adapter schedules keep the reference's Adam at a constant learning rate)")
+    if (args.weight_decay is not None or args.clip_grad_norm is not None) and args.optim != "adamw":
+        raise SystemExit("--weight-decay / --clip-grad-norm are options of AdamW and need --optim adamw")
     augment_from_args(args)      # --aug-* without --augment
     fn = {"zero-joint": zero_joint_bounds, "class-inc": class_incremental, "data-inc": data_incremental}[args.which]
     _, metrics = fn(args)

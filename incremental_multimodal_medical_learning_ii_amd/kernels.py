@@ -1451,6 +1451,61 @@ def adam_fused(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
                               float(weight_decay), int(step), float(grad_scale), _stream()), "cxrk_adam_fused")
 
 
+def grad_sqnorm_nparts(n: int) -> int:
+    """number of fp32 partial sums `grad_sqnorm` writes for n elements: a function of n alone (include/cxrk.h, "grad_sqnorm")"""
+    return _lib.load().cxrk_grad_sqnorm_partials_bytes(int(n)) // 4
+
+
+def grad_sqnorm(g: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-block partial sums of g[i]^2 over a flat fp32 buffer -> [nparts] (in `out`, else in the stream's workspace: valid until the
+    next wrapper call on this stream, which is `adamw_clipped`).  Bit-reproducible; g is not modified."""
+    lib = _lib.load()
+    _chk(g, "grad_sqnorm.g")
+    if g.dim() != 1 or not g.is_contiguous() or g.numel() == 0:
+        raise ValueError("grad_sqnorm.g: expected a non-empty contiguous 1-D buffer")
+    n = g.numel()
+    nbytes = lib.cxrk_grad_sqnorm_partials_bytes(n)
+    if out is None:
+        ws = workspace(nbytes, g.device)
+        ws_bytes = ws.numel() * 4
+    else:
+        ws = _chk(out, "grad_sqnorm.out")
+        if not out.is_contiguous():
+            raise ValueError("grad_sqnorm.out: must be contiguous")
+        ws_bytes = out.numel() * 4
+    check(lib.cxrk_grad_sqnorm(_p(g), n, _p(ws), ws_bytes, _stream()), "cxrk_grad_sqnorm")
+    return ws[:nbytes // 4]
+
+
+def adamw_clipped(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale: float = 1.0, max_norm: float = 0.0,
+                  decay_mask: Optional[torch.Tensor] = None, partials: Optional[torch.Tensor] = None,
+                  stats: Optional[torch.Tensor] = None):
+    """AdamW with decoupled, masked weight decay and global-norm clipping in one launch (include/cxrk.h, "adamw_clipped").
+    `partials` = what `grad_sqnorm(g)` returned (None with max_norm <= 0: no clipping); `decay_mask`: uint8 [ceil(n / 4)], one byte
+    per aligned group of four elements (None: everything decays); `stats`: 2 floats <- (norm before clipping, coefficient)."""
+    lib = _lib.load()
+    n = p.numel()
+    for nme, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _chk(t, "adamw." + nme)
+        if not t.is_contiguous() or t.numel() != n:
+            raise ValueError(f"adamw.{nme}: must be contiguous with {n} elements")
+    if decay_mask is not None:
+        _chk(decay_mask, "adamw.decay_mask", torch.uint8)
+        if not decay_mask.is_contiguous() or decay_mask.numel() != (n + 3) // 4:
+            raise ValueError(f"adamw.decay_mask: must be contiguous with ceil({n} / 4) = {(n + 3) // 4} bytes")
+    if partials is not None:
+        _chk(partials, "adamw.partials")
+        if not partials.is_contiguous():
+            raise ValueError("adamw.partials: must be contiguous")
+    if stats is not None:
+        _chk(stats, "adamw.stats")
+        if not stats.is_contiguous() or stats.numel() != 2:
+            raise ValueError("adamw.stats: must be 2 contiguous floats")
+    check(lib.cxrk_adamw_clipped(_p(p), _p(g), _p(m), _p(v), _p(decay_mask), n, float(lr), float(beta1), float(beta2), float(eps),
+                                 float(weight_decay), int(step), float(grad_scale), float(max_norm), _p(partials),
+                                 0 if partials is None else partials.numel() * 4, _p(stats), _stream()), "cxrk_adamw_clipped")
+
+
 def sgd(p, g, lr, weight_decay: float = 0.0, grad_scale: float = 1.0):
     lib = _lib.load()
     check(lib.cxrk_sgd(_p(_chk(p, "sgd.p")), _p(_chk(g, "sgd.g")), p.numel(), float(lr), float(weight_decay),

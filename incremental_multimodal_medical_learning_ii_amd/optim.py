@@ -6,9 +6,13 @@ buffer), so an optimiser step is a single HBM-bound kernel launch (28 B/paramete
 all-reduce is a handful of large contiguous RCCL calls instead of one per tensor.  Parameters that were adjacent in
 memory before (the fused q/k/v projections) stay adjacent; the physical layout of each tensor (e.g. channels_last
 conv filters) is preserved.
+
+`AdamW` (decoupled weight decay with a no-decay set, global-norm clipping) and `LRSchedule` (warmup / decay) are opt-in additions
+that the reference does not have.
 """
 from __future__ import annotations
 
+import math
 from typing import Iterable, List, Optional
 
 import torch
@@ -162,6 +166,113 @@ class Adam(_FlatOptimizer):
 
     def state_dict(self):
         return {"step": self.steps, "exp_avg": self.flat_m, "exp_avg_sq": self.flat_v, "lr": self.lr}
+
+
+class AdamW(_FlatOptimizer):
+    """`torch.optim.AdamW` (decoupled weight decay) behind `torch.nn.utils.clip_grad_norm_`, on the flat buffers.
+
+    `no_decay`: the parameters that do not decay; default every parameter with `ndim <= 1` (biases, BatchNorm / LayerNorm gamma and
+    beta, the logit scale and bias) -- embedding tables and filters decay.  `max_grad_norm`: None = no norm is taken; a positive
+    number clips the global gradient norm to it; `inf` takes and reports the norm without clipping.  A step is one launch, or two
+    with `max_grad_norm`: `grad_sqnorm` over the flat gradient buffer, then `adamw_clipped`, which derives the coefficient on the
+    device -- no host sync.  The gradient buffer itself is left unclipped.  `last_grad_norm` / `last_clip_coef` are device views of
+    the last step's norm (before clipping, `grad_scale` included) and coefficient; `current_grad_norm()` reads the norm back."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.01,
+                 max_grad_norm: Optional[float] = None, no_decay=None):
+        weight_decay = float(weight_decay)
+        if not (weight_decay >= 0.0 and weight_decay != float("inf")):
+            raise ValueError(f"AdamW: weight_decay must be finite and >= 0, got {weight_decay!r}")
+        if max_grad_norm is not None:
+            max_grad_norm = float(max_grad_norm)
+            if not max_grad_norm > 0.0:
+                raise ValueError(f"AdamW: max_grad_norm must be None, positive or inf, got {max_grad_norm!r}")
+        super().__init__(params, lr)
+        self.betas, self.eps, self.weight_decay, self.max_grad_norm = betas, eps, weight_decay, max_grad_norm
+        self.flat_m = torch.zeros_like(self.flat_p)
+        self.flat_v = torch.zeros_like(self.flat_p)
+        if no_decay is None:
+            skip = {id(p) for p in self.params if p.ndim <= 1}
+        else:
+            skip = {id(p) for p in no_decay}
+            unknown = skip - {id(p) for p in self.params}
+            if unknown:
+                raise ValueError(f"AdamW: {len(unknown)} of the no_decay parameters are not among the optimised parameters")
+        self.no_decay_ids = skip
+        self.decay_mask = self._build_decay_mask(skip)
+        self._stats = torch.tensor([0.0, 1.0], dtype=torch.float32, device=self.flat_p.device)
+        self.last_grad_norm, self.last_clip_coef = self._stats[0:1], self._stats[1:2]
+        self._partials = None
+
+    def _build_decay_mask(self, skip) -> torch.Tensor:
+        """uint8 [numel / 4]: one byte per aligned group of four elements of the flat buffers, 1 = the group decays.  Every tensor is
+        padded to a multiple of four, so no group holds two tensors; a tensor's padding follows the tensor."""
+        mask = torch.zeros(self.numel // 4, dtype=torch.uint8)
+        base = self.flat_g.data_ptr()
+        for p, gv in zip(self.params, self._views):
+            if id(p) not in skip:
+                o = (gv.data_ptr() - base) // 4
+                mask[o // 4:(o + (p.numel() + 3) // 4 * 4) // 4] = 1
+        return mask.to(self.flat_p.device)
+
+    @torch.no_grad()
+    def step(self, grad_scale: float = 1.0) -> None:
+        self._sync_grads()
+        self.steps += 1
+        partials = None
+        if self.max_grad_norm is not None:
+            if self._partials is None:
+                self._partials = torch.empty(K.grad_sqnorm_nparts(self.numel), dtype=torch.float32, device=self.flat_p.device)
+            partials = K.grad_sqnorm(self.flat_g, out=self._partials)
+        K.adamw_clipped(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.lr, self.betas[0], self.betas[1], self.eps,
+                        self.weight_decay, self.steps, grad_scale, 0.0 if self.max_grad_norm is None else self.max_grad_norm,
+                        decay_mask=self.decay_mask, partials=partials, stats=self._stats)
+
+    def current_grad_norm(self) -> Optional[float]:
+        """the last step's gradient norm before clipping as a host float (None without `max_grad_norm`): the one read-back"""
+        if self.max_grad_norm is None:
+            return None
+        return float(self.last_grad_norm.cpu())
+
+    def state_dict(self):
+        return {"step": self.steps, "exp_avg": self.flat_m, "exp_avg_sq": self.flat_v, "lr": self.lr}
+
+
+DECAYS = ("constant", "linear", "cosine")
+
+
+class LRSchedule:
+    """Learning rate of optimiser step `step` (counted from 1), a pure host function: linear warmup from base_lr / warmup_steps to
+    base_lr over the first `warmup_steps` steps, then constant, or a linear / cosine decay to `min_lr_ratio * base_lr` at
+    `total_steps` (and constant from there on).  The learning rate is a host float argument of the update kernel already, so a
+    schedule adds no launch and no sync."""
+
+    def __init__(self, base_lr: float, warmup_steps: int = 0, total_steps: Optional[int] = None, decay: str = "constant",
+                 min_lr_ratio: float = 0.0):
+        if decay not in DECAYS:
+            raise ValueError(f"LRSchedule: decay must be one of {DECAYS}, got {decay!r}")
+        for name, val in (("warmup_steps", warmup_steps), ("total_steps", total_steps)):
+            if val is not None and (isinstance(val, bool) or not isinstance(val, int) or val < 0):
+                raise ValueError(f"LRSchedule: {name} must be an integer >= 0, got {val!r}")
+        if decay != "constant" and total_steps is None:
+            raise ValueError(f"LRSchedule: decay={decay!r} needs total_steps")
+        if total_steps is not None and warmup_steps > total_steps:
+            raise ValueError(f"LRSchedule: warmup_steps {warmup_steps} > total_steps {total_steps}")
+        if not 0.0 <= float(min_lr_ratio) <= 1.0:
+            raise ValueError(f"LRSchedule: min_lr_ratio must be in [0, 1], got {min_lr_ratio!r}")
+        self.base_lr, self.warmup_steps, self.total_steps = float(base_lr), warmup_steps, total_steps
+        self.decay, self.min_lr_ratio = decay, float(min_lr_ratio)
+
+    def __call__(self, step: int) -> float:
+        if step < 1:
+            raise ValueError(f"LRSchedule: steps count from 1, got {step!r}")
+        if step <= self.warmup_steps:
+            return self.base_lr * step / self.warmup_steps
+        if self.decay == "constant":
+            return self.base_lr
+        t = min(1.0, max(0.0, (step - self.warmup_steps) / max(1, self.total_steps - self.warmup_steps)))
+        f = 1.0 - t if self.decay == "linear" else 0.5 * (1.0 + math.cos(math.pi * t))
+        return self.base_lr * (self.min_lr_ratio + (1.0 - self.min_lr_ratio) * f)
 
 
 class SGD(_FlatOptimizer):
