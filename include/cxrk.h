@@ -56,7 +56,7 @@ int cxrk_gemm_wgrad_splitk(int M, int N, int K, int planes);
 /* 1 when a launch of this GEMM shape takes the 256x256 tile (reporting only).  kind: 0 or 3 dense layer / weight gradient,
  * 1 convolution forward, 2 convolution data gradient. */
 int cxrk_gemm_wide_tile(int M, int N, long K, int splitk, int kind);
-/* What the last call of a GEMM-family entry point (cxrk_gemm_f32 / _pl, cxrk_conv_bn_act_fwd* / _bwd_data* / _bwd_params*) on the
+/* What the last call of a GEMM-family entry point (cxrk_gemm_f32 / _pl, cxrk_conv_bn_act_fwd* / _bwd_data* / _bwd_params*, cxrk_stem_pool_*) on the
  * calling thread launched: the kernel instantiation as scripts/pmc_summary_key.py abbreviates its rocprofv3 name ("" if the call
  * launched nothing; valid until the thread's next query), the number of MFMA kernel launches (reductions not counted), and whether
  * the mainloop is the split-bf16 one.  Of several launches the label is that of the largest M*N*K (the first on ties). */
@@ -202,6 +202,20 @@ int cxrk_maxpool_fwd_pl(const void* x, long xplane, void* y, long yplane, unsign
                         hipStream_t stream);
 int cxrk_maxpool_bwd_pl(const void* dy, long dyplane, const unsigned char* idx, const void* pooled, float* dx, int N, int H,
                         int W, int C, hipStream_t stream);
+
+/* The stem with its max-pool fused — self.conv1, self.bn1, self.relu, self.maxpool (resnet.py:34-38) in one kernel: the stem output
+ * [N,Hs,Ws,64] never reaches memory.  x: fp32 [N,H,W,4]; w_scaled: fp32 [64][7][7][4] and shift as for cxrk_conv_bn_act_fwd_pl with
+ * in_planes = 0; y: planes [N,Hp,Wp,64]; idx: uint8 [N,Hp,Wp,64], or null when no backward follows.  Bit-identical to
+ * cxrk_conv_bn_act_fwd_pl(relu = 1) followed by cxrk_maxpool_fwd_pl.  Any other geometry than 7x7 / stride 2 / pad 3, 4 -> 64
+ * channels: CXRK_ERR_UNSUPPORTED (the caller takes the two calls). */
+int cxrk_stem_pool_fwd(const float* x, const float* w_scaled, const float* shift, void* y, long yplane, unsigned char* idx, int N,
+                       int H, int W, int C, int Ko, int R, int S, int stride, int pad, hipStream_t stream);
+/* sums[c] = sum over the stem pixels of the dx cxrk_maxpool_bwd_pl writes for (g, idx, pooled) — the stem's BatchNorm sums — without
+ * that tensor: every window has one winner, so it is the sum over the pooled pixels of g * [pooled > 0].  g, pooled: planes
+ * [N,Hp,Wp,64].  Deterministic: per-block partials in `part` (scratch memory of cxrk_colsum_ws_bytes(N*Hp*Wp, 64)
+ * bytes, sized and aligned like every workspace), then a fixed-order final pass. */
+int cxrk_stem_pool_bwd_sums(const void* g, long gplane, const void* pooled, float* sums, int N, int Hp, int Wp, int C, float* part,
+                            size_t part_bytes, hipStream_t stream);
 
 /* spatial_mean — torch.mean(projected_patch_embeddings, dim=(2,3)) (model.py:145). x[N][P][C] -> y[N][C]. */
 int cxrk_spatial_mean_fwd(const float* x, float* y, int N, int P, int C, hipStream_t stream);

@@ -54,6 +54,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_maxpool_bwd": (I, [P, P, P, P, I, I, I, I, I, P]),
     "cxrk_maxpool_fwd_pl": (I, [P, L, P, L, P, I, I, I, I, P]),
     "cxrk_maxpool_bwd_pl": (I, [P, L, P, P, P, I, I, I, I, P]),
+    "cxrk_stem_pool_fwd": (I, [P, P, P, P, L, P, I, I, I, I, I, I, I, I, I, P]),
+    "cxrk_stem_pool_bwd_sums": (I, [P, L, P, P, I, I, I, I, P, Z, P]),
     "cxrk_spatial_mean_fwd": (I, [P, P, I, I, I, P]),
     "cxrk_spatial_mean_bwd": (I, [P, P, I, I, I, P]),
     "cxrk_spatial_mean_bwd_pl": (I, [P, P, P, L, I, I, I, P]),

@@ -251,14 +251,29 @@ def _conv_bn_train(i, s, fold, p, bufs, x, residual, relu, N, H, W, want_mask, m
     return y, mask
 
 
-def _trunk(specs, blocks, unit, x0, H, W, pl, st: Optional[_Saved] = None, keep_stem=False, stages: Optional[list] = None):
+def _stem_pool_on() -> bool:
+    """CXRK_STEM_POOL=0 restores the unfused stem (convolution, max-pool, column sums of the max-pool gradient as separate kernels)"""
+    return os.environ.get("CXRK_STEM_POOL", "1") != "0"
+
+
+def _trunk(specs, blocks, unit, x0, H, W, pl, st: Optional[_Saved] = None, keep_stem=False, stages: Optional[list] = None,
+           stem_pool: Optional[Callable] = None):
     """The walk the forward and the BatchNorm calibration share: stem, max-pool, the bottlenecks, the projector's conv + BN + ReLU,
     every unit through `unit(i, x, residual, relu, H, W, want_mask=True) -> (y, mask)`.  Fills `st` when the pass is saved.
+    stem_pool (planes mode, eval-mode BatchNorm, stem output not kept): `stem_pool(x0, H, W, want_idx) -> (pooled, idx) or None`, the
+    stem and its max-pool in one kernel (kernels.stem_pool_fwd_pl); None = this geometry is not fused, take the two kernels.
     -> (projector hidden activation pj1, h, w)"""
-    stem, _ = unit(0, x0, None, True, H, W, want_mask=False)   # its ReLU mask = sign of the pooled value
-    cur, idx = K.maxpool_fwd_pl(stem) if pl else K.maxpool_fwd(stem)
+    s0 = specs[0]
+    fused = stem_pool(x0, H, W, st is not None) if stem_pool is not None else None
+    if fused is not None:
+        (cur, idx), stem = fused, None
+        Hs, Ws = _out_hw(s0, H, W)
+    else:
+        stem, _ = unit(0, x0, None, True, H, W, want_mask=False)   # its ReLU mask = sign of the pooled value
+        cur, idx = K.maxpool_fwd_pl(stem) if pl else K.maxpool_fwd(stem)
+        Hs, Ws = stem.shape[1], stem.shape[2]
     if st is not None:
-        st.x0, st.idx, st.pooled, st.Hs, st.Ws = x0, idx, cur, stem.shape[1], stem.shape[2]
+        st.x0, st.idx, st.pooled, st.Hs, st.Ws = x0, idx, cur, Hs, Ws
         st.stem = stem if (keep_stem or not pl) else None     # planes mode: the max-pool backward needs only `pooled`
     del stem, x0, idx
     h, w = cur.shape[1], cur.shape[2]
@@ -324,7 +339,14 @@ def _forward(specs, blocks, p: Sequence[torch.Tensor], bufs: Sequence[torch.Tens
             return _conv_bn_train(i, specs[i], fold, p, bufs, x, residual, relu, N, H, W, want_mask, bn_momentum, st.bn if save else None)
         return _conv(i, specs[i], fold, x, residual, relu, N, H, W, want_mask)
 
-    pj1, h, w = _trunk(specs, blocks, unit, _stem_input(x, augment), H, W, pl, st, keep_stem, stages)
+    stem_pool = None
+    s0 = specs[0]
+    if (pl and not train and not keep_stem and stages is None and _stem_pool_on()
+            and (s0.k, s0.stride, s0.pad, s0.cout, s0.cpad) == (7, 2, 3, 64, 4)):
+        def stem_pool(x0, H, W, want_idx):
+            return K.stem_pool_fwd_pl(x0, fold.ws(0, s0), fold.shift(0, s0), N, H, W, s0.cpad, s0.cout, s0.k, s0.k, s0.stride, s0.pad, want_idx)
+
+    pj1, h, w = _trunk(specs, blocks, unit, _stem_input(x, augment), H, W, pl, st, keep_stem, stages, stem_pool)
     pj2, w3p = _proj_linear(pj1.view(N * h * w, pj1.shape[-1]), p[3 * len(specs)], p[3 * len(specs) + 1], pl)
     if save:
         st.w3p = w3p
@@ -497,7 +519,10 @@ def _backward(specs, blocks, p, bufs, st: _Saved, demb: Optional[torch.Tensor], 
         dstem = K.maxpool_bwd(g, st.idx, st.stem, True)
     if _debug is not None:
         _debug["ds"], _debug["x0"] = dstem, st.x0
-    sum_s = K.colsum(dstem.view(-1, dstem.shape[-1]), torch.empty(dstem.shape[-1], dtype=torch.float32, device=dev))
+    if st.pl and st.bn is None and _stem_pool_on() and dstem.shape[-1] == 64:
+        sum_s = K.stem_pool_bwd_sums(g, st.pooled)     # the same sums in pooled space: no pass over the [N, Hs, Ws, 64] gradient
+    else:
+        sum_s = K.colsum(dstem.view(-1, dstem.shape[-1]), torch.empty(dstem.shape[-1], dtype=torch.float32, device=dev))
     dstem, sum_s = through_bn(0, dstem, sum_s)
     params_bwd(0, st.x0, dstem, sum_s, st.H, st.W)
     if on_grads_ready is not None and all(r is None for r in sink.ret):

@@ -723,6 +723,45 @@ def maxpool_bwd_pl(dy: Planes, idx, pooled: Planes, H: int, W: int) -> torch.Ten
     return dx
 
 
+def stem_pool_fwd_pl(x, w_scaled, shift, N, H, W, C, Ko, R, S, stride, pad, want_idx: bool = True):
+    """Stem convolution + folded BatchNorm + ReLU + 3x3/2/1 max-pool in one kernel (csrc/stem_pool.hip): x fp32 [N,H,W,C], w_scaled
+    fp32 -> (pooled Planes [N,Hp,Wp,Ko], winners uint8 [N,Hp,Wp,Ko] or None), bit-identical to `conv_fwd_pl(relu=True)` followed by
+    `maxpool_fwd_pl`.  -> None when the library does not fuse this geometry (the caller takes the two calls)."""
+    lib = _lib.load()
+    Hs, Ws = _conv_out(H, W, R, S, stride, pad)
+    Hp, Wp = (Hs - 1) // 2 + 1, (Ws - 1) // 2 + 1
+    y = Planes.empty(N, Hp, Wp, Ko, device=x.device)
+    idx = torch.empty(N, Hp, Wp, Ko, dtype=torch.uint8, device=x.device) if want_idx else None
+    ev = None
+    if profiler.on:
+        ev = profiler.bracket(2.0 * N * Hs * Ws * Ko * R * S * C, 4.0 * (N * H * W * C + Ko * R * S * C + N * Hp * Wp * Ko) + (N * Hp * Wp * Ko if want_idx else 0))
+    rc = lib.cxrk_stem_pool_fwd(_p(_chk(x, "stem_pool.x")), _p(_chk(w_scaled, "stem_pool.w")), _p(_chk(shift, "stem_pool.shift")), y.ptr(), y.plane,
+                                _p(idx), N, H, W, C, Ko, R, S, stride, pad, _stream())
+    profiler.end(ev)
+    if rc == -4:    # CXRK_ERR_UNSUPPORTED
+        return None
+    check(rc, f"cxrk_stem_pool_fwd(N={N},H={H},W={W})")
+    return y, idx
+
+
+def stem_pool_bwd_sums(g: Planes, pooled: Planes) -> torch.Tensor:
+    """sums[c] of the tensor `maxpool_bwd_pl(g, idx, pooled, ...)` would write, over its pixels, without that tensor: the sum over the
+    pooled pixels of g * [pooled > 0] (every window has one winner).  Deterministic."""
+    lib = _lib.load()
+    N, Hp, Wp, C = pooled.shape
+    if tuple(g.shape) != (N, Hp, Wp, C) or not g.is_contiguous() or not pooled.is_contiguous():
+        raise ValueError(f"stem_pool_bwd_sums: g {tuple(g.shape)} and pooled {tuple(pooled.shape)} must be contiguous and of one shape")
+    sums = torch.empty(C, dtype=torch.float32, device=g.device)
+    part = workspace(lib.cxrk_colsum_ws_bytes(N * Hp * Wp, C), g.device)
+    ev = None
+    if profiler.on:
+        ev = profiler.bracket(2.0 * N * Hp * Wp * C, 6.0 * N * Hp * Wp * C)
+    rc = lib.cxrk_stem_pool_bwd_sums(g.ptr(), g.plane, pooled.ptr(), _p(sums), N, Hp, Wp, C, _p(part), part.numel() * 4, _stream())
+    profiler.end(ev)
+    check(rc, f"cxrk_stem_pool_bwd_sums(N={N},Hp={Hp},Wp={Wp},C={C})")
+    return sums
+
+
 def spatial_mean_bwd_pl(dy: torch.Tensor, Pn: int, add: Optional[torch.Tensor] = None) -> Planes:
     lib = _lib.load()
     N, C = dy.shape
