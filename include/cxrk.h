@@ -108,6 +108,26 @@ int cxrk_colvar(const void* X, long ldx, long plane, long rows, int cols, const 
  * bf16 planes hi = bf16(x), lo = bf16(x - hi) of the same shape, the lo plane `*plane` ELEMENTS behind the hi plane (4 bytes
  * per element like fp32; pointers are `void*`).  They are what the encoders use in split-bf16 mode: the MFMA mainloops then
  * load operands without any conversion work.  ReLU decisions travel as bit masks: byte [pixel][channel / 8], bit channel % 8.
+ *
+ * Geometry contract (tests/test_conv_geometry_gpu.py).  x [N][H][W][C], w [Ko][R][S][C], y / dy [N][Ho][Wo][Ko] with
+ * Ho = floor((H + 2 pad - R) / stride) + 1, Wo likewise; one stride and one pad for both axes; H != W and R != S are computed like
+ * squares, and pad is free of R (0 .. any, not only R / 2).  A call either computes exactly that or returns an error with no
+ * output byte written.
+ *   all three, both storage forms — CXRK_ERR_ARG: N, H, W, R or S <= 0; pad < 0; stride other than 1 or 2; Ho <= 0 or Wo <= 0 (the
+ *     filter does not fit the padded image once); 2^31 or more GEMM rows (N Ho Wo; data gradient: N H W); operands not 16-byte aligned.
+ *     CXRK_ERR_UNSUPPORTED: the images under one 256-row tile span 2 GiB or more.
+ *   fwd       fp32: C % 4 == 0, else CXRK_ERR_ARG; any R, S (C % 32 == 0 with R S <= 32 and R <= 8 gathers tap-wise, anything else per
+ *             lane: the stem).  _pl: Ko % 8 == 0, and Ko % 64 == 0 with maskout (the bits are written 64 channels at a time), else
+ *             CXRK_ERR_ARG; with in_planes = 1, C % 32 == 0, R S <= 32 and R <= 8, else CXRK_ERR_UNSUPPORTED; with in_planes = 0 the
+ *             fp32 rules.
+ *   bwd_data  C and Ko % 4 == 0 (_pl: % 8), else CXRK_ERR_ARG.  Ko % 32 != 0, R S > 32 or R > 8: CXRK_ERR_UNSUPPORTED.  Stride 2 runs
+ *             per output-parity class and takes R, S <= 3 only (CXRK_ERR_ARG above); pad < R - 1 is fine (taps then reach row / column
+ *             -1 of dy and are masked like those past the end).  A class no tap reaches (a 1-wide filter extent at stride 2 along an axis
+ *             of >= 2 pixels) is exactly zero and exists in the plain form only: residual, relu_src / maskin -> CXRK_ERR_ARG; sums
+ *             -> CXRK_ERR_ARG whenever R == 1 at stride 2.  _pl_s2res: stride 1 only (CXRK_ERR_ARG).
+ *   bwd_params Cpad and Ko % 4 == 0 (_pl: C and Ko % 8), 1 <= C <= Cpad, else CXRK_ERR_ARG; any R, S; dw has the REAL channel count C
+ *             and nothing is written for the padded channels.  One image of 2^31 / 12 bytes or more: CXRK_ERR_UNSUPPORTED.
+ *             cxrk_conv_wgrad_ws_bytes returns 0 for a geometry the call refuses.
  */
 int cxrk_bn_fold(const float* w, const float* gamma, const float* beta, const float* rmean, const float* rvar,
                  float eps, int Ko, int taps, int C, int Cpad, float* w_scaled, float* scale, float* shift,

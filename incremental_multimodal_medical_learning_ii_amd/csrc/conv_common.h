@@ -14,6 +14,14 @@ static inline ConvGeom make_geom(int N, int H, int W, int C, int Ko, int R, int 
   return g;
 }
 
+// What every convolution entry point refuses with CXRK_ERR_ARG before any size arithmetic: a non-positive image or filter
+// extent, a negative pad, a stride other than 1 or 2, or a filter that does not fit the padded image once (Ho <= 0 or Wo <= 0;
+// tested on the numerator, as make_geom's division truncates towards zero and would turn an extent of -1 at stride 2 into Ho = 1).
+static inline bool conv_geom_ok(int H, int W, int R, int S, int stride, int pad) {
+  if (H <= 0 || W <= 0 || R <= 0 || S <= 0 || pad < 0 || (stride != 1 && stride != 2)) return false;
+  return (long)H + 2L * pad - R >= 0 && (long)W + 2L * pad - S >= 0;
+}
+
 // The convolution gathers address a block's rows with 32-bit byte offsets from the first image the tile touches
 // (gemm_loaders.h): a 256-row tile spans at most 256 / (Ho*Wo) + 2 images of the gathered tensor, which must stay < 2 GiB.
 static bool tile_span_ok(long rows_per_image, long image_elems) {

@@ -79,7 +79,7 @@ static int conv_bwd_data_impl(const typename FMT::T* dy, long dyplane, const typ
                               bool has_side, int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad,
                               hipStream_t stream) {
   CXRK_CHECK_ARG(dy && w && N > 0 && C % FMT::EPL == 0 && Ko % FMT::EPL == 0 && aligned16(dy) && aligned16(w));
-  CXRK_CHECK_ARG(stride == 1 || stride == 2);
+  CXRK_CHECK_ARG(conv_geom_ok(H, W, R, S, stride, pad));
   if (Ko % BK != 0 || R * S > 32 || R > 8) return CXRK_ERR_UNSUPPORTED;  // the gather keeps a K-tile inside one filter tap
   const ConvGeom g = make_geom(N, H, W, C, Ko, R, S, stride, pad);
   const long Ml = (long)N * H * W;
@@ -157,7 +157,7 @@ extern "C" int cxrk_conv_bn_act_bwd_data(const float* dy, const float* w_scaled,
                                          const float* relu_src, float* dx, int N, int H, int W, int C, int Ko, int R, int S,
                                          int stride, int pad, float* sums, float* ws, size_t ws_bytes, hipStream_t stream) {
   last_launch = {};
-  CXRK_CHECK_ARG(dx);
+  CXRK_CHECK_ARG(dx && N > 0 && conv_geom_ok(H, W, R, S, stride, pad));
   EpiParams ep{};
   ep.C = dx; ep.ldc = C; ep.R = residual; ep.ldr = C; ep.alpha = 1.f;
   if (relu_src) { ep.aux = relu_src; ep.ldaux = C; ep.auxmode = 1; }
@@ -194,7 +194,7 @@ extern "C" int cxrk_conv_bn_act_bwd_data_pl_s2res(const void* dy, long dyplane, 
                                                   int C, int Ko, int R, int S, int stride, int pad, float* sums, float* ws,
                                                   size_t ws_bytes, hipStream_t stream) {
   last_launch = {};
-  CXRK_CHECK_ARG(residual_s2 && stride == 1);
+  CXRK_CHECK_ARG(residual_s2 && stride == 1 && N > 0 && conv_geom_ok(H, W, R, S, stride, pad));
   // 32-bit byte offsets into the compact tensor (gemm_epilogue.h)
   if ((long)N * ((H + 1) / 2) * ((W + 1) / 2) * C * 2 >= (1L << 31)) return CXRK_ERR_UNSUPPORTED;
   return conv_bwd_data_pl_impl(dy, dyplane, w_scaled, wplane, residual_s2, rplane, 1, maskin, dx, dxplane, N, H, W, C, Ko, R, S, stride, pad, sums,
@@ -203,7 +203,7 @@ extern "C" int cxrk_conv_bn_act_bwd_data_pl_s2res(const void* dy, long dyplane, 
 static int conv_bwd_data_pl_impl(const void* dy, long dyplane, const void* w_scaled, long wplane, const void* residual, long rplane, int res_s2,
                                  const unsigned char* maskin, void* dx, long dxplane, int N, int H, int W, int C, int Ko, int R, int S,
                                  int stride, int pad, float* sums, float* ws, size_t ws_bytes, hipStream_t stream) {
-  CXRK_CHECK_ARG(dx && (C % 8) == 0);
+  CXRK_CHECK_ARG(dx && (C % 8) == 0 && N > 0 && conv_geom_ok(H, W, R, S, stride, pad));
   EpiParams ep{};
   if (res_s2) { ep.rs2_on = 1; ep.rs2_H = H; ep.rs2_W = W; ep.rs2_Ho = (H + 1) / 2; ep.rs2_Wo = (W + 1) / 2; }
   ep.Cp = static_cast<unsigned short*>(dx); ep.cplane = dxplane; ep.ldc = C;

@@ -14,9 +14,8 @@ template <class FMT>
 static int conv_fwd_impl(const typename FMT::T* x, long xplane, const typename FMT::T* w, long wplane, EpiParams ep, int N, int H,
                          int W, int C, int Ko, int R, int S, int stride, int pad, hipStream_t stream) {
   CXRK_CHECK_ARG(x && w && N > 0 && C % FMT::EPL == 0 && aligned16(x) && aligned16(w));
-  CXRK_CHECK_ARG(stride == 1 || stride == 2);
+  CXRK_CHECK_ARG(conv_geom_ok(H, W, R, S, stride, pad));
   const ConvGeom g = make_geom(N, H, W, C, Ko, R, S, stride, pad);
-  CXRK_CHECK_ARG(g.Ho > 0 && g.Wo > 0);
   const long Ml = (long)N * g.Ho * g.Wo;
   CXRK_CHECK_ARG(Ml < (1L << 31));
   const int M = (int)Ml, K = R * S * C;

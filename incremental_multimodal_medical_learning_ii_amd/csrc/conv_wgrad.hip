@@ -89,6 +89,7 @@ static int wgrad_splitk(int Ko, int Ncols, long Kred, bool planes) { return wgra
 static int wgrad_dot_parts(int Nc) { return ceil_div(Nc, 64); }   // upper bound of the reduction grid's y extent
 
 extern "C" size_t cxrk_conv_wgrad_ws_bytes(int N, int H, int W, int C, int Ko, int R, int S, int stride, int pad) {
+  if (N <= 0 || C <= 0 || Ko <= 0 || !conv_geom_ok(H, W, R, S, stride, pad)) return 0;   // the entry points refuse these
   const ConvGeom g = make_geom(N, H, W, C, Ko, R, S, stride, pad);
   int sk = wgrad_splitk(Ko, R * S * C, (long)N * g.Ho * g.Wo, false);   // upper bound over both storage formats
   const int sk2 = wgrad_splitk(Ko, R * S * C, (long)N * g.Ho * g.Wo, true);
@@ -106,6 +107,7 @@ static int conv_bwd_params_impl(const typename FMT::T* x, long xplane, const typ
                                 int S, int stride, int pad, float* ws, size_t ws_bytes, hipStream_t stream) {
   CXRK_CHECK_ARG(x && dy && dw && N > 0 && Cpad % FMT::EPL == 0 && Ko % FMT::EPL == 0 && aligned16(x) && aligned16(dy));
   CXRK_CHECK_ARG(!(dgamma && !(w && rstd && rmean && sumdy && dbeta)));
+  CXRK_CHECK_ARG(conv_geom_ok(H, W, R, S, stride, pad) && C > 0 && C <= Cpad);
   const ConvGeom g = make_geom(N, H, W, Cpad, Ko, R, S, stride, pad);
   const long Kl = (long)N * g.Ho * g.Wo;
   CXRK_CHECK_ARG(Kl < (1L << 31));

@@ -388,7 +388,8 @@ struct ConvFilterMC : MCGeom<TILE, FMT, NT> {
 // Stride-2 dgrad, one output-parity class (ph,pw) per launch: only the taps r = (ph+pad) mod 2 (+2) reach pixels
 // (2a+ph, 2b+pw), so the K loop runs over those taps only (no multiply-by-zero work: 9 taps -> 1+2+2+4 over the
 // four classes).  idx = (n,a,b) on the half-resolution grid; k = (ti,ko) with ti indexing the class's tap list.
-struct S2Taps { int nr, ns; int r[2], s[2]; int dr[2], ds[2]; };  // ho = a + dr[tr], wo = b + ds[ts]   (dr, ds >= 0)
+// dr, ds = (parity + pad - tap) / 2 is -1 for tap 2 at pad 0: the loaders mask a tap on either side of [0, Ho) x [0, Wo)
+struct S2Taps { int nr, ns; int r[2], s[2]; int dr[2], ds[2]; };  // ho = a + dr[tr], wo = b + ds[ts]
 
 template <int TILE, class FMT = F32, int NT = NTHREADS>
 struct ConvDgradS2KC : KCGeom<TILE, FMT, NT> {
@@ -417,7 +418,7 @@ struct ConvDgradS2KC : KCGeom<TILE, FMT, NT> {
         for (int ir = 0; ir < 2; ++ir)
 #pragma unroll
           for (int is = 0; is < 2; ++is)
-            if (ir < t.nr && is < t.ns && (a + t.dr[ir] >= Ho || b + t.ds[is] >= Wo)) m |= 1u << (ir * t.ns + is);
+            if (ir < t.nr && is < t.ns && ((unsigned)(a + t.dr[ir]) >= (unsigned)Ho || (unsigned)(b + t.ds[is]) >= (unsigned)Wo)) m |= 1u << (ir * t.ns + is);
         inv[j] = m;
       } else { off[j] = 0; inv[j] = 0xffffffffu; }
     }

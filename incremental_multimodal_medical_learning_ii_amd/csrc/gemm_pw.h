@@ -259,7 +259,7 @@ struct DmaConvDgradS2KC {
         for (int ir = 0; ir < 2; ++ir)
 #pragma unroll
           for (int is = 0; is < 2; ++is)
-            if (ir < t.nr && is < t.ns && (a + t.dr[ir] >= Ho || b + t.ds[is] >= Wo)) m |= 1u << (ir * t.ns + is);
+            if (ir < t.nr && is < t.ns && ((unsigned)(a + t.dr[ir]) >= (unsigned)Ho || (unsigned)(b + t.ds[is]) >= (unsigned)Wo)) m |= 1u << (ir * t.ns + is);
         inv[j] = m;
       } else { off[j] = 0; inv[j] = 0xffffffffu; }
     }

@@ -169,6 +169,36 @@ def test_image_model_forward_backward(golden_dir):
     assert not model(x.to(DEV)).requires_grad
 
 
+@pytest.mark.parametrize("H,W,grid", [(70, 106, (3, 4)), (96, 160, (3, 5))])
+def test_image_model_forward_backward_on_a_rectangle(H, W, grid):
+    """The same parity on images that are not square: 70 x 106 gives the trunk 18 x 27 -> 9 x 14 -> 5 x 7 -> 3 x 4, so every
+    stride-2 stage meets an odd and an even extent (a left-over row in one direction, none in the other); 96 x 160 stays even down
+    to 3 x 5.  Forward and every gradient against the CPU oracle under the captured ReLU decisions, bounds of the square test."""
+    from incremental_multimodal_medical_learning_ii_amd import image_encoder as IE
+    model = get_biovil_resnet(None)
+    syn.fill_module_(model)
+    sd_cpu = {k: v.clone() for k, v in model.state_dict().items()}
+    model.to(DEV).eval()
+    gen = torch.Generator().manual_seed(31)
+    x = torch.rand(2, 1, H, W, generator=gen).repeat_interleave(3, dim=1).contiguous()     # as syn.synthetic_images, H x W
+    probe = torch.randn(2, 128, generator=gen)
+    with IE.capture_relu_decisions() as cap:
+        emb = model(x.to(DEV))
+    assert emb.shape == (2, 128)
+    (emb * probe.to(DEV)).sum().backward()
+    named = dict(model.named_parameters())
+    emb_ref, gref, pol = _image_oracle_with_decisions(sd_cpu, x, probe, cap[0])
+    assert rel(emb, emb_ref) < TOL, rel(emb, emb_ref)
+    assert pol.flips <= _flip_budget()[0] and pol.max_flip_rel < _flip_budget()[1], (pol.flips, pol.max_flip_rel)
+    assert pol.pool_flips <= _flip_budget()[0] // 100 + 2 and pol.pool_max_gap < _flip_budget()[1], (pol.pool_flips, pol.pool_max_gap)
+    worst = max(((rel(named[k].grad, v), k) for k, v in gref.items()), key=lambda t: t[0])
+    assert worst[0] < TOL, worst
+    with torch.no_grad():
+        patches = model.get_patchwise_projected_embeddings(x.to(DEV), normalize=True)
+    assert patches.shape == (2,) + grid + (128,)
+    assert rel(patches.norm(dim=-1), torch.ones(2, *grid)) < 1e-5
+
+
 PATCH_PX = 64      # 2 images of 64 x 64: the head sees 2 x 2 patches, the smallest size at which the spatial mean and its `add=` form
 #                    are not trivial
 
