@@ -492,6 +492,23 @@ int cxrk_scale_mask(const float* x, const float* mask_src, const float* alpha_de
  *               NULL = every element decays.  g, the mask and the partials are read only (the gradient stays unclipped).
  *               stats (optional, 2 floats): stats[0] = norm before clipping, stats[1] = coef (0 and 1 without partials), written
  *               by one thread with ordinary stores.  p, g, m, v 16-byte aligned, n > 0, step >= 1 as for adam_fused.
+ *
+ * Elastic weight consolidation over the same flat buffers (penalty strength / 2 * sum_i F[i] * (p[i] - anchor[i])^2).  All three
+ * follow grad_sqnorm's conventions: float4 accesses (every buffer 16-byte aligned, else CXRK_ERR_ARG), a scalar n % 4 tail,
+ * grid-stride loops, no atomics, n > 0, and nothing is written when a call is refused.
+ * fisher_accumulate: acc[i] = fma(w, g[i] * g[i], acc[i]), i.e. acc += w * g^2 (two roundings).  g is read only.
+ * ewc_consolidate: one pass: F[i] = fma(gamma, F[i], scale * acc[i]) and anchor[i] = p[i].  acc == NULL: only the anchor is written
+ *               (identity Fisher) and F must be NULL too; F == NULL with acc given is CXRK_ERR_ARG.  acc and p are read only.
+ * ewc_penalty:  d = p[i] - anchor[i];  t = F[i] * d;  g[i] = fma(strength, t, g[i]);  partials[b] = sum of t * d over block b's share.
+ *               The partition is grad_sqnorm's, a function of n alone: nparts(n) blocks, the n % 4 tail in block 0, each block's sum
+ *               in a fixed order, so the same buffers give the same bits in every run and on every data-parallel rank.
+ *               cxrk_ewc_penalty_partials_bytes(n) = cxrk_grad_sqnorm_partials_bytes(n); partials == NULL or ws_bytes below it gives
+ *               CXRK_ERR_WS with nothing written; no 256-byte alignment is asked of it.  F == NULL: F = 1 everywhere (L2-SP), bit for
+ *               bit the result of an all-ones F.  The penalty's value is strength / 2 * sum of the partials (the caller's sum).
+ *               p, anchor and F are read only; g is updated in place.
+ *               Non-finite: as the torch expression g + strength * F * (p - anchor).  A NaN or Inf in element i of g, p, anchor or F
+ *               reaches g[i] (0 * Inf = NaN included) and the partial sum of the block that holds i; it reaches no other element
+ *               of g and no other partial.
  */
 int cxrk_adam_fused(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, int step, float grad_scale, hipStream_t stream);
@@ -501,6 +518,12 @@ int cxrk_grad_sqnorm(const float* g, long n, float* partials, size_t ws_bytes, h
 int cxrk_adamw_clipped(float* p, const float* g, float* m, float* v, const unsigned char* decay_mask, long n, float lr,
                        float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float max_norm,
                        const float* partials, size_t ws_bytes, float* stats, hipStream_t stream);
+int cxrk_fisher_accumulate(float* acc, const float* g, long n, float w, hipStream_t stream);
+int cxrk_ewc_consolidate(float* F, const float* acc, float* anchor, const float* p, long n, float gamma, float scale,
+                         hipStream_t stream);
+size_t cxrk_ewc_penalty_partials_bytes(long n);
+int cxrk_ewc_penalty(float* g, const float* p, const float* anchor, const float* F, long n, float strength, float* partials,
+                     size_t ws_bytes, hipStream_t stream);
 size_t cxrk_weight_reset_ws_bytes(void);
 int cxrk_weight_reset(float* pnew, const float* pold, long n, float threshold, unsigned long long* counters, float* ws,
                       size_t ws_bytes, hipStream_t stream);

@@ -38,6 +38,10 @@ Two extensions behind the same entry points (both off unless asked for):
     gradient norm (`inf`: monitoring only); `"warmup_steps"`, `"total_steps"`, `"lr_decay"` ("constant" | "linear" | "cosine") and
     `"min_lr_ratio"` put a warmup / decay schedule around `lr` for any optimiser.  `train` then logs `train/lr` and,
     with "max_grad_norm", `train/grad_norm` once per epoch.
+    `"ewc_lambda": s` adds elastic weight consolidation (optionally `"ewc_fisher"` "empirical" | "identity",
+    `"ewc_gamma"` in [0, 1], `"ewc_batches"`: the most batches one estimate reads): `consolidate(loader)` after a task anchors the
+    parameters and estimates their importance, later steps carry the quadratic penalty; `train` logs `train/ewc_penalty` once per
+    epoch while it is active, `save` / `load` carry the state as `ewc.pt`.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -130,6 +134,7 @@ class Trainer:
         "image_model" (an `ImageModel` on `device`) and optionally "temperature" (default 0.07) — no adapters are created, the
         trainable parameters are the two encoders.  `process_group`: the data-parallel group (default: the default group when
         `torch.distributed` is initialised)."""
+        self._ewc_batches = self._check_ewc_keys(joint_encoders)
         self.pos_mean_counter = 0
         self.neg_mean_counter = 0
         self.n_reset = 0
@@ -176,7 +181,8 @@ class Trainer:
                                                   temperature=float(je.get("temperature", 0.07)), group=process_group,
                                                   optim=je["optim"] if je.get("optim") is not None else OPTIM,
                                                   **{k: je[k] for k in ("weight_decay", "max_grad_norm", "warmup_steps", "total_steps",
-                                                                        "lr_decay", "min_lr_ratio") if je.get(k) is not None},
+                                                                        "lr_decay", "min_lr_ratio", "ewc_lambda", "ewc_gamma", "ewc_fisher")
+                                                     if je.get(k) is not None},
                                                   positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
                                                   **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
                                                   **({"loss": je["contrastive_loss"]} if "contrastive_loss" in je else {}),
@@ -239,6 +245,25 @@ class Trainer:
         self._flat_copy = None
         self._reset_counters = torch.zeros(2, dtype=torch.int64, device=device)
         self._reset_total = 0
+
+    EWC_KEYS = ("ewc_lambda", "ewc_gamma", "ewc_fisher", "ewc_batches")
+
+    @staticmethod
+    def _check_ewc_keys(joint_encoders):
+        """the "ewc_*" entries of `joint_encoders`, checked before anything is built -> "ewc_batches" (None: every batch of the
+        loader).  They configure the joint trainer: without an "image_model" there is none, and they are refused."""
+        if not isinstance(joint_encoders, dict):
+            return None
+        given = [k for k in Trainer.EWC_KEYS if joint_encoders.get(k) is not None]
+        if given and joint_encoders.get("image_model") is None:
+            raise ValueError(f"joint_encoders: {given} configure elastic weight consolidation of the joint-encoder step and need joint "
+                             f"mode (an 'image_model'); the adapter schedules have no such penalty")
+        if given and joint_encoders.get("ewc_lambda") is None:
+            raise ValueError(f"joint_encoders: {given} are options of 'ewc_lambda' and were given without it")
+        nb = joint_encoders.get("ewc_batches")
+        if nb is not None and (isinstance(nb, bool) or not isinstance(nb, int) or nb < 1):
+            raise ValueError(f"joint_encoders['ewc_batches'] must be an integer >= 1, got {nb!r}")
+        return nb
 
     # ------------------------------------------------------------------------------------------------ data
     @staticmethod
@@ -735,6 +760,9 @@ class Trainer:
             self.writer.add_scalar('train/lr', opt.lr, epoch)
         if adamw and opt.max_grad_norm is not None and opt.steps > 0:
             self.writer.add_scalar('train/grad_norm', opt.current_grad_norm(), epoch)
+        penalty = self._joint.current_penalty()     # None without "ewc_lambda" and before the first penalised step
+        if penalty is not None:
+            self.writer.add_scalar('train/ewc_penalty', penalty, epoch)
 
     @staticmethod
     def _parse_retrieval(opt):
@@ -844,6 +872,32 @@ class Trainer:
         return m
 
     # ------------------------------------------------------------------------------------------------ continual learning
+    def consolidate(self, loader) -> int:
+        """End of a task with `joint_encoders={..., "ewc_lambda": s}`: the encoders in evaluation mode, each batch of
+        `loader` sharded as in `_joint_step`, at most "ewc_batches" of them -> `JointContrastiveTrainer.consolidate`; returns the
+        number of batches read.  Every rank calls it, as it calls the training loop."""
+        if self._joint is None or self._joint.ewc is None:
+            raise ValueError("Trainer.consolidate needs joint_encoders={..., 'ewc_lambda': strength}")
+        self._set_mode(False)
+        positives, dev = self._joint.positives, self.device
+
+        def shards():
+            for batch in loader:
+                if len(batch) < 3 or (positives == "labels" and len(batch) < 4):
+                    raise ValueError("Trainer.consolidate expects the batches of joint-encoder training: (images, input_ids, "
+                                     f"attention_mask[, labels]); got a batch of {len(batch)} tensors")
+                images, ids, mask = batch[0], batch[1], batch[2]
+                n = images.shape[0]
+                if self.world > 1 and n % self.world:
+                    raise ValueError(f"joint-encoder training shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
+                lo, hi = self._shard(n) if self.world > 1 else (0, n)
+                out = (images[lo:hi].to(dev, non_blocking=True), ids[lo:hi].to(dev, non_blocking=True), mask[lo:hi].to(dev, non_blocking=True))
+                if positives is not None:   # the keys, hashed where the loader left the tensors
+                    out += (self._joint.pair_keys(ids[lo:hi], mask[lo:hi], batch[3][lo:hi] if positives == "labels" else None),)
+                yield out
+
+        return self._joint.consolidate(shards(), max_batches=self._ewc_batches)
+
     @torch.no_grad()
     def model_copy(self):
         """Snapshot the adapters before a step (`Trainer.py:1634-1641`)."""
@@ -928,6 +982,8 @@ class Trainer:
                 if self._joint.logit_bias is not None:
                     sd["logit_bias"] = self._joint.logit_bias.detach().cpu()
                 torch.save(sd, os.path.join(self.writer.log_dir, 'logit_scale.pt'))
+            if self._joint.ewc is not None:
+                torch.save(self._joint.ewc.state_dict(), os.path.join(self.writer.log_dir, 'ewc.pt'))
         if hasattr(self.writer, "flush"):
             self.writer.flush()
 
@@ -963,4 +1019,6 @@ class Trainer:
                 self._joint.logit_scale.data.copy_(sd["logit_scale"].reshape(1))
                 if self._joint.logit_bias is not None:
                     self._joint.logit_bias.data.copy_(sd["logit_bias"].reshape(1))
+            if self._joint.ewc is not None:   # keys, fisher kind and the size of F / anchor are checked by `EWC.load_state_dict`
+                self._joint.ewc.load_state_dict(torch.load(os.path.join(self.writer.log_dir, 'ewc.pt'), map_location="cpu", weights_only=True))
             self._bert_cache.clear()

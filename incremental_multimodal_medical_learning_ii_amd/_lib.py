@@ -108,6 +108,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_grad_sqnorm_partials_bytes": (Z, [L]),
     "cxrk_grad_sqnorm": (I, [P, L, P, Z, P]),
     "cxrk_adamw_clipped": (I, [P, P, P, P, P, L, F, F, F, F, F, I, F, F, P, Z, P, P]),
+    "cxrk_fisher_accumulate": (I, [P, P, L, F, P]),
+    "cxrk_ewc_consolidate": (I, [P, P, P, P, L, F, F, P]),
+    "cxrk_ewc_penalty_partials_bytes": (Z, [L]),
+    "cxrk_ewc_penalty": (I, [P, P, P, P, L, F, P, Z, P]),
     "cxrk_weight_reset_ws_bytes": (Z, []),
     "cxrk_weight_reset": (I, [P, P, L, F, P, P, Z, P]),
     "cxrk_gemm_wgrad_splitk": (I, [I, I, I, I]),

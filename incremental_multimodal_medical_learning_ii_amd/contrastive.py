@@ -242,12 +242,19 @@ class JointContrastiveTrainer:
                  augment_seed: Optional[int] = None, loss: str = "infonce", sigmoid_bias: Optional[float] = None,
                  micro_batch: Optional[int] = None, weight_decay: Optional[float] = None, max_grad_norm: Optional[float] = None,
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, lr_decay: Optional[str] = None,
-                 min_lr_ratio: Optional[float] = None):
+                 min_lr_ratio: Optional[float] = None, ewc_lambda: Optional[float] = None, ewc_gamma: Optional[float] = None,
+                 ewc_fisher: Optional[str] = None):
         """`optim="adamw"`: `optim.AdamW` with decoupled `weight_decay` (default 0.01; parameters with ndim <= 1 do
         not decay) and, with `max_grad_norm`, clipping of the global gradient norm (`inf`: the norm is taken and reported, nothing
         is clipped).  `warmup_steps` / `total_steps` / `lr_decay` ("constant" | "linear" | "cosine") / `min_lr_ratio`: an
-        `optim.LRSchedule` around `lr`, for every optimiser; with none of them given the learning rate is never touched."""
+        `optim.LRSchedule` around `lr`, for every optimiser; with none of them given the learning rate is never touched.
+        `ewc_lambda`: elastic weight consolidation, an `optim.EWC` of that strength over the optimiser's flat
+        buffers (`ewc_fisher` "empirical" | "identity", `ewc_gamma` in [0, 1]).  Until the first `consolidate(batches)` a step is
+        bit for bit the step without it; afterwards `step` adds the penalty's gradient between the gradient all-reduce and the
+        optimiser's step, so clipping and the update see it exactly as if the penalty were part of the loss."""
         self.micro_batch = check_micro_batch(micro_batch)
+        if ewc_lambda is None and (ewc_gamma is not None or ewc_fisher is not None):
+            raise ValueError("ewc_gamma / ewc_fisher are options of elastic weight consolidation; they were given without ewc_lambda")
         if optim not in OPTIMS:
             raise ValueError(f"optim must be 'adam', 'sgd' or 'adamw', got {optim!r}")
         if optim != "adamw" and (weight_decay is not None or max_grad_norm is not None):
@@ -327,6 +334,10 @@ class JointContrastiveTrainer:
             self.optimizer = cxr_optim.AdamW(params + tparams, lr=lr, max_grad_norm=max_grad_norm,
                                              **({"weight_decay": weight_decay} if weight_decay is not None else {}))
         text_model.prepare_()
+        self.ewc = None
+        if ewc_lambda is not None:
+            self.ewc = cxr_optim.EWC(self.optimizer, ewc_lambda, fisher="empirical" if ewc_fisher is None else ewc_fisher,
+                                     gamma=1.0 if ewc_gamma is None else ewc_gamma)
         self.world, self.rank = 1, 0
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
@@ -494,21 +505,9 @@ class JointContrastiveTrainer:
             return Fh.infonce_loss(img, txt, self.temperature, self.group)
         return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys)
 
-    def step(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
-             labels: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """One optimisation step on this rank's shard; returns the global-batch loss (device scalar, no host sync).
-
-        Data-parallel overlap (N > 1): the gradient all-reduce of a range of the flat buffer (`reduce_spans`) is started by the
-        backward itself the moment that range is complete — a callable handed to THIS step's two encoder calls and carried by
-        their autograd nodes (no module-level state): the text encoder's 0.44 GB under the image backward, then the image
-        encoder's stages from the back (60 / 28 / 5 / 1 MB) under the layers in front of them; what is left (nothing, when every
-        tag fired) is reduced after `backward()` returns.  Precondition, asserted: each encoder runs ONCE per step inside
-        `forward_loss` — a second call of an encoder in the same graph would have its range reduced before the second
-        contribution was accumulated.  A rank that raises inside `backward()` after a range was started leaves its peers inside that
-        collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog).
-
-        With `micro_batch` < this rank's rows the forward and backward run chunk by chunk (`_chunked_forward_backward`); the hook
-        is then handed only to the encoder calls of the step's LAST backward, after which every range is complete."""
+    def _gradient(self, images, input_ids, attention_mask, labels, keys) -> torch.Tensor:
+        """Everything of a step up to and including the gradient all-reduce -> the loss; afterwards the flat gradient buffer holds the
+        global-batch gradient, identical on every rank.  Shared by `step` and `consolidate`."""
         slices = ((0, int(images.shape[0])),) if self.micro_batch is None else micro_slices(int(images.shape[0]), self.micro_batch)
         chunked = len(slices) > 1
         if chunked:
@@ -548,12 +547,70 @@ class JointContrastiveTrainer:
                 loss.backward()
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)
+        return loss
+
+    def step(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+             labels: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One optimisation step on this rank's shard; returns the global-batch loss (device scalar, no host sync).
+
+        Data-parallel overlap (N > 1): the gradient all-reduce of a range of the flat buffer (`reduce_spans`) is started by the
+        backward itself the moment that range is complete — a callable handed to THIS step's two encoder calls and carried by
+        their autograd nodes (no module-level state): the text encoder's 0.44 GB under the image backward, then the image
+        encoder's stages from the back (60 / 28 / 5 / 1 MB) under the layers in front of them; what is left (nothing, when every
+        tag fired) is reduced after `backward()` returns.  Precondition, asserted: each encoder runs ONCE per step inside
+        `forward_loss` — a second call of an encoder in the same graph would have its range reduced before the second
+        contribution was accumulated.  A rank that raises inside `backward()` after a range was started leaves its peers inside that
+        collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog).
+
+        With `micro_batch` < this rank's rows the forward and backward run chunk by chunk (`_chunked_forward_backward`); the hook
+        is then handed only to the encoder calls of the step's LAST backward, after which every range is complete."""
+        loss = self._gradient(images, input_ids, attention_mask, labels, keys)
+        if self.ewc is not None:         # no launch before the first consolidation
+            self.ewc.apply()
         if self.schedule is not None:    # a host float that the update kernel takes as an argument: no launch, no sync
             self.optimizer.param_groups[0]["lr"] = self.schedule(self.optimizer.steps + 1)
         self.optimizer.step()
         if self.logit_scale is not None:
             K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)
         return loss.detach()
+
+    def consolidate(self, batches, max_batches: Optional[int] = None) -> int:
+        """End of a task (needs `ewc_lambda`): estimate the Fisher diagonal and anchor the parameters -> the number of batches used.
+        For each batch `(images, input_ids, attention_mask[, labels | keys])` -- this rank's shard, as for `step`; a fourth tensor
+        of more than one dimension is taken as labels, a 1-D one as keys -- the gradient is computed as in `step` (the same
+        `micro_batch` chunks, the same overlapped all-reduce) and its square accumulated; then `optim.EWC.consolidate()`.  No
+        optimiser update, no schedule advance, no clamp: `optimizer.steps`, the moments and the parameters stay as they are.  It
+        never augments and leaves the augmentation counter alone.  With `ewc_fisher="identity"` no batch is read.  Under data
+        parallelism every rank calls it with its shards; F comes from the all-reduced gradient, so it needs no collective of its
+        own and is bit-identical on every rank."""
+        if self.ewc is None:
+            raise ValueError("JointContrastiveTrainer.consolidate: this trainer was constructed without ewc_lambda")
+        used = 0
+        if self.ewc.fisher == "empirical":
+            self.ewc.begin_estimate()
+            augment, self._augment = self._augment, None      # the images as they are; the counter does not move
+            try:
+                for batch in batches:
+                    if max_batches is not None and used >= max_batches:
+                        break
+                    if len(batch) < 3:
+                        raise ValueError("consolidate: a batch is (images, input_ids, attention_mask[, labels | keys]); got "
+                                         f"{len(batch)} tensors")
+                    extra = batch[3] if len(batch) > 3 else None
+                    labels = extra if extra is not None and extra.dim() > 1 else None
+                    keys = extra if extra is not None and extra.dim() == 1 else None
+                    self._gradient(batch[0], batch[1], batch[2], labels, keys)
+                    self.ewc.accumulate()
+                    used += 1
+            finally:
+                self._augment = augment
+        self.ewc.consolidate()
+        return used
+
+    def current_penalty(self) -> Optional[float]:
+        """the consolidation penalty of the last step as a host float (None without `ewc_lambda` or before the first penalised
+        step): a host sync, and only when called"""
+        return None if self.ewc is None else self.ewc.current_penalty()
 
     def _require_eval_batchnorm(self) -> None:
         """a micro-batched step is the unchunked step only while the rows of a batch are independent up to the loss"""

@@ -6,6 +6,7 @@ and `DATA_INCREMENTAL.py:74-97` (hyper-parameters as arguments instead of litera
     python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --parts 5
 
     python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --parts 5 --joint --batch-size 1024 --epochs 1
+    python -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --joint --cl ewc --ewc-lambda 1e4 --ewc-batches 8
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29511 \
         -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --mode class-pos-neg --batch-size 2048
 
@@ -126,6 +127,7 @@ def _setup(args, kind):
                                              "sigmoid_bias": getattr(args, "sigmoid_bias", None),
                                              "micro_batch": getattr(args, "micro_batch", None),
                                              **optimiser_from_args(args, kind, train_loader),
+                                             **ewc_from_args(args),
                                              "augment": augment_from_args(args),
                                              "retrieval": retrieval_from_args(args)})
     else:
@@ -162,6 +164,21 @@ def optimiser_from_args(args, kind=None, train_loader=None) -> dict:
             out[key] = getattr(args, flag)
     if any(k in out for k in ("warmup_steps", "lr_decay", "min_lr_ratio")) and train_loader is not None:
         out["total_steps"] = run_steps(args, kind, train_loader)
+    return out
+
+
+EWC_LAMBDA = 1e4     # F is a squared mean gradient, so useful strengths are large
+
+
+def ewc_from_args(args) -> dict:
+    """`--cl ewc` / `--ewc-lambda` / `--ewc-batches` / `--ewc-gamma` / `--ewc-fisher` -> the `joint_encoders` keys they set (without
+    `--cl ewc`: an empty dict)"""
+    if getattr(args, "cl", None) != "ewc":
+        return {}
+    out = {"ewc_lambda": EWC_LAMBDA if args.ewc_lambda is None else args.ewc_lambda}
+    for flag in ("ewc_batches", "ewc_gamma", "ewc_fisher"):
+        if getattr(args, flag, None) is not None:
+            out[flag] = getattr(args, flag)
     return out
 
 
@@ -228,6 +245,8 @@ def class_incremental(args):
                                 last_batch, actual_task)
                 if args.cl == "profCL" and actual_task > 1:
                     trainer.profIncremental(epoch, args.epochs, actual_task, threshold)
+            if args.cl == "ewc" and actual_task < len(tasks_order):      # anchor this task before the next one starts
+                trainer.consolidate(train_loader[actual_task - 1])
             trainer.val(val_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
             metrics = trainer.test(test_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
     finally:
@@ -253,6 +272,8 @@ def data_incremental(args):
                               actual_task=part)
                 if args.cl == "profCL":
                     trainer.profIncremental(epoch, args.epochs, part, threshold)
+            if args.cl == "ewc" and part < args.parts:
+                trainer.consolidate(train_loader[part - 1])
             train_loader[part - 1] = None
             trainer.val(val_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
             metrics = trainer.test(test_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
@@ -272,7 +293,9 @@ def make_parser():
     ap.add_argument("--more-labels", action="store_true")
     ap.add_argument("--single-prompt", action="store_true")
     ap.add_argument("--xrays-position", default="all")
-    ap.add_argument("--cl", default=None, choices=[None, "myCL", "profCL"])
+    ap.add_argument("--cl", default=None, choices=[None, "myCL", "profCL", "ewc"],
+                    help="continual learning: the reference's weight-reset heuristics (myCL, profCL) or, with --joint, elastic weight "
+                         "consolidation (ewc, DESIGN.md 5.10)")
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--adder", type=float, default=0.001)
     ap.add_argument("--threshold-scheduling", action="store_true")
@@ -325,12 +348,42 @@ def make_parser():
     ap.add_argument("--lr-decay", default=None, choices=["constant", "linear", "cosine"],
                     help="--joint: learning-rate decay after the warmup, to --min-lr-ratio x --lr at the run's last step")
     ap.add_argument("--min-lr-ratio", type=float, default=None, metavar="R", help="--lr-decay: the final learning rate as a fraction of --lr")
+    ap.add_argument("--ewc-lambda", type=float, default=None, metavar="S",
+                    help="--cl ewc: strength of the penalty S / 2 * sum F (p - anchor)^2 (default 1e4: F is a squared mean gradient)")
+    ap.add_argument("--ewc-batches", type=int, default=None, metavar="N",
+                    help="--cl ewc: estimate the Fisher diagonal from at most N batches of the finished task (default: all of them)")
+    ap.add_argument("--ewc-gamma", type=float, default=None, metavar="G",
+                    help="--cl ewc: F = G * F_old + F_new when a further task is consolidated, G in [0, 1] (default 1)")
+    ap.add_argument("--ewc-fisher", default=None, choices=["empirical", "identity"],
+                    help="--cl ewc: empirical Fisher diagonal (default) or identity (L2-SP: no estimate, half the memory)")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
 
+def parse_args(argv=None):
+    """`make_parser().parse_args` plus the refusals that concern `--cl ewc` (parser errors: exit status 2)"""
+    ap = make_parser()
+    args = ap.parse_args(argv)
+    given = [f for f in ("ewc_lambda", "ewc_batches", "ewc_gamma", "ewc_fisher") if getattr(args, f) is not None]
+    if given and args.cl != "ewc":
+        ap.error("--" + given[0].replace("_", "-") + " configures elastic weight consolidation and needs --cl ewc")
+    if args.cl == "ewc":
+        if args.which == "zero-joint":
+            ap.error("--cl ewc consolidates between tasks; zero-joint trains a single task (use class-inc or data-inc)")
+        if not args.joint:
+            ap.error("--cl ewc penalises the encoders of the north-star step and needs --joint (the adapter schedules keep the "
+                     "reference's weight-reset heuristics myCL / profCL)")
+        if args.ewc_lambda is not None and not (args.ewc_lambda >= 0 and args.ewc_lambda != float("inf")):
+            ap.error(f"--ewc-lambda must be finite and >= 0, got {args.ewc_lambda}")
+        if args.ewc_gamma is not None and not 0.0 <= args.ewc_gamma <= 1.0:
+            ap.error(f"--ewc-gamma must be in [0, 1], got {args.ewc_gamma}")
+        if args.ewc_batches is not None and args.ewc_batches < 1:
+            ap.error(f"--ewc-batches must be >= 1, got {args.ewc_batches}")
+    return args
+
+
 def main(argv=None):
-    args = make_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.text_dropout and not args.joint:
         raise SystemExit("--text-dropout trains the text encoder in-loop and needs --joint (the adapter schedules use frozen "
                          "pre-computed text embeddings)")

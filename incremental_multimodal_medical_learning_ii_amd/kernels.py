@@ -1545,6 +1545,64 @@ def adamw_clipped(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_sc
                                  0 if partials is None else partials.numel() * 4, _p(stats), _stream()), "cxrk_adamw_clipped")
 
 
+def _flat(t: torch.Tensor, name: str, n: Optional[int] = None) -> torch.Tensor:
+    """a non-empty contiguous 1-D fp32 GPU buffer (of n elements)"""
+    _chk(t, name)
+    if t.dim() != 1 or not t.is_contiguous() or t.numel() == 0 or (n is not None and t.numel() != n):
+        raise ValueError(f"{name}: expected a non-empty contiguous 1-D buffer" + (f" of {n} elements" if n is not None else ""))
+    return t
+
+
+def fisher_accumulate(acc: torch.Tensor, g: torch.Tensor, w: float = 1.0) -> None:
+    """acc += w * g^2 over flat fp32 buffers, in place (include/cxrk.h, "fisher_accumulate"); g is not modified."""
+    lib = _lib.load()
+    _flat(acc, "fisher_accumulate.acc")
+    _flat(g, "fisher_accumulate.g", acc.numel())
+    check(lib.cxrk_fisher_accumulate(_p(acc), _p(g), acc.numel(), float(w), _stream()), "cxrk_fisher_accumulate")
+
+
+def ewc_consolidate(F: Optional[torch.Tensor], acc: Optional[torch.Tensor], anchor: torch.Tensor, p: torch.Tensor,
+                    gamma: float = 1.0, scale: float = 1.0) -> None:
+    """One pass: F = gamma * F + scale * acc and anchor = p (include/cxrk.h, "ewc_consolidate").  acc = None (identity Fisher): only the
+    anchor is written, and F must be None too."""
+    lib = _lib.load()
+    n = _flat(anchor, "ewc_consolidate.anchor").numel()
+    _flat(p, "ewc_consolidate.p", n)
+    for nme, t in (("F", F), ("acc", acc)):
+        if t is not None:
+            _flat(t, "ewc_consolidate." + nme, n)
+    check(lib.cxrk_ewc_consolidate(_p(F), _p(acc), _p(anchor), _p(p), n, float(gamma), float(scale), _stream()), "cxrk_ewc_consolidate")
+
+
+def ewc_penalty_nparts(n: int) -> int:
+    """number of fp32 partial sums `ewc_penalty` writes for n elements: `grad_sqnorm_nparts(n)` (include/cxrk.h, "ewc_penalty")"""
+    return _lib.load().cxrk_ewc_penalty_partials_bytes(int(n)) // 4
+
+
+def ewc_penalty(g: torch.Tensor, p: torch.Tensor, anchor: torch.Tensor, F: Optional[torch.Tensor], strength: float,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """g += strength * F * (p - anchor) in place, and the per-block partial sums of F * (p - anchor)^2 -> [nparts] (in `out`, else in
+    the stream's workspace: valid until the next wrapper call on this stream).  F = None: F = 1 everywhere (L2-SP).  The penalty is
+    strength / 2 * the sum of the partials.  Bit-reproducible; p, anchor and F are not modified."""
+    lib = _lib.load()
+    n = _flat(g, "ewc_penalty.g").numel()
+    _flat(p, "ewc_penalty.p", n)
+    _flat(anchor, "ewc_penalty.anchor", n)
+    if F is not None:
+        _flat(F, "ewc_penalty.F", n)
+    nbytes = lib.cxrk_ewc_penalty_partials_bytes(n)
+    if out is None:
+        ws = workspace(nbytes, g.device)
+        ws_bytes = ws.numel() * 4
+    else:
+        ws = _chk(out, "ewc_penalty.out")
+        if not out.is_contiguous():
+            raise ValueError("ewc_penalty.out: must be contiguous")
+        ws_bytes = out.numel() * 4
+    check(lib.cxrk_ewc_penalty(_p(g), _p(p), _p(anchor), _p(F), n, float(strength), _p(ws), ws_bytes, _stream()), "cxrk_ewc_penalty")
+    return ws[:nbytes // 4]
+
+
 def sgd(p, g, lr, weight_decay: float = 0.0, grad_scale: float = 1.0):
     lib = _lib.load()
     check(lib.cxrk_sgd(_p(_chk(p, "sgd.p")), _p(_chk(g, "sgd.g")), p.numel(), float(lr), float(weight_decay),

@@ -8,7 +8,7 @@ memory before (the fused q/k/v projections) stay adjacent; the physical layout o
 conv filters) is preserved.
 
 `AdamW` (decoupled weight decay with a no-decay set, global-norm clipping) and `LRSchedule` (warmup / decay) are opt-in additions
-that the reference does not have.
+that the reference does not have; so is `EWC`, elastic weight consolidation over the same flat buffers (§5.10).
 """
 from __future__ import annotations
 
@@ -285,3 +285,128 @@ class SGD(_FlatOptimizer):
         self._sync_grads()
         self.steps += 1
         K.sgd(self.flat_p, self.flat_g, self.lr, self.weight_decay, grad_scale)
+
+
+FISHERS = ("empirical", "identity")
+
+
+class EWC:
+    """Elastic weight consolidation over the flat buffers of any `_FlatOptimizer`: after a task, `consolidate()`
+    keeps the parameters as the anchor a and an importance F per parameter; from then on `apply()` adds the gradient of
+    strength / 2 * sum F (p - a)^2 to the flat gradient buffer, before the optimiser's step (and its clipping norm) reads it.
+
+    `fisher="empirical"`: F is the mean, over the batches between `begin_estimate()` and `consolidate()`, of the squared gradient
+    that `accumulate()` finds in `optimizer.flat_g` -- the global-batch MEAN gradient (call it after `all_reduce_grads`), not the
+    per-example Fisher.  Such an F is of the size of a squared mean gradient, so useful `strength` values are large (1e3 and far
+    above, depending on the loss).  `fisher="identity"`: F = 1 (L2-SP); no F is stored and no estimate is needed.  `gamma` in [0, 1]
+    merges tasks: F = gamma * F_old + F_new; the anchor is always the latest parameters.  Memory: +8 B per parameter (F and the
+    anchor; +4 B with "identity"), and another +4 B while an estimate runs.  `apply()` is one launch, none before the first
+    consolidation; `current_penalty()` is the one read-back and happens only when asked."""
+
+    def __init__(self, optimizer: _FlatOptimizer, strength: float, fisher: str = "empirical", gamma: float = 1.0):
+        strength, gamma = float(strength), float(gamma)
+        if not (math.isfinite(strength) and strength >= 0.0):
+            raise ValueError(f"EWC: strength must be finite and >= 0, got {strength!r}")
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"EWC: gamma must be in [0, 1], got {gamma!r}")
+        if fisher not in FISHERS:
+            raise ValueError(f"EWC: fisher must be one of {FISHERS}, got {fisher!r}")
+        self.optimizer, self.strength, self.fisher, self.gamma = optimizer, strength, fisher, gamma
+        self.F: Optional[torch.Tensor] = None
+        self.anchor: Optional[torch.Tensor] = None
+        self._acc: Optional[torch.Tensor] = None
+        self._partials: Optional[torch.Tensor] = None
+        self.samples, self.tasks, self.active, self._applied = 0, 0, False, False
+
+    def begin_estimate(self) -> None:
+        """allocate and zero the accumulator of an empirical estimate (a running one starts over)"""
+        self._acc = torch.zeros_like(self.optimizer.flat_p)
+        self.samples = 0
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """acc += g^2 from `optimizer.flat_g` (after `all_reduce_grads` under data parallelism); counts one sample"""
+        if self._acc is None:
+            raise ValueError("EWC.accumulate: no estimate is running (call begin_estimate() first)")
+        self.optimizer._sync_grads()
+        K.fisher_accumulate(self._acc, self.optimizer.flat_g, 1.0)
+        self.samples += 1
+
+    @torch.no_grad()
+    def consolidate(self) -> None:
+        """F = gamma * F + acc / samples, anchor = flat_p, in one launch; frees the accumulator"""
+        opt = self.optimizer
+        if self.fisher == "empirical":
+            if self._acc is None or self.samples == 0:
+                raise ValueError("EWC.consolidate: fisher='empirical' needs at least one accumulate() since begin_estimate()")
+            if self.F is None:
+                self.F = torch.zeros_like(opt.flat_p)
+        if self.anchor is None:
+            self.anchor = torch.empty_like(opt.flat_p)
+        if self.fisher == "empirical":
+            K.ewc_consolidate(self.F, self._acc, self.anchor, opt.flat_p, self.gamma, 1.0 / self.samples)
+        else:
+            K.ewc_consolidate(None, None, self.anchor, opt.flat_p)
+        self._acc, self.samples = None, 0
+        self.tasks += 1
+        self.active = True
+
+    @torch.no_grad()
+    def apply(self) -> None:
+        """flat_g += strength * F * (flat_p - anchor); the partial sums of the penalty are kept for `current_penalty()`.  Not active
+        (nothing consolidated yet): returns without a launch."""
+        if not self.active:
+            return
+        opt = self.optimizer
+        opt._sync_grads()
+        if self._partials is None:
+            self._partials = torch.empty(K.ewc_penalty_nparts(opt.numel), dtype=torch.float32, device=opt.flat_p.device)
+        K.ewc_penalty(opt.flat_g, opt.flat_p, self.anchor, self.F, self.strength, out=self._partials)
+        self._applied = True
+
+    def current_penalty(self) -> Optional[float]:
+        """strength / 2 * sum F (p - a)^2 of the last `apply()` as a host float (float64 sum of the partials; None before the first
+        penalised step): the one read-back, only when asked"""
+        if not (self.active and self._applied):
+            return None
+        return 0.5 * self.strength * float(self._partials.detach().cpu().double().sum())
+
+    def state_dict(self) -> dict:
+        """tensors and plain numbers only (loadable with weights_only=True)"""
+        sd = {"tasks": int(self.tasks), "gamma": float(self.gamma), "fisher": self.fisher, "numel": int(self.optimizer.numel)}
+        if self.anchor is not None:
+            sd["anchor"] = self.anchor.detach().cpu()
+        if self.F is not None:
+            sd["F"] = self.F.detach().cpu()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """strict: the keys of `state_dict()`, the same fisher kind, and F / anchor of exactly `optimizer.numel` elements"""
+        if not isinstance(sd, dict):
+            raise ValueError(f"EWC.load_state_dict: expected a dict, got {type(sd).__name__}")
+        want = {"tasks", "gamma", "fisher", "numel"}
+        unknown = set(sd) - want - {"anchor", "F"}
+        if unknown or not want <= set(sd):
+            raise ValueError(f"EWC.load_state_dict: keys {sorted(sd)} (expected {sorted(want)} and, once consolidated, 'anchor' / 'F')")
+        if sd["fisher"] != self.fisher:
+            raise ValueError(f"EWC.load_state_dict: the state was written with fisher={sd['fisher']!r}, this object has {self.fisher!r}")
+        tasks, n = int(sd["tasks"]), self.optimizer.numel
+        need = set() if tasks == 0 else ({"anchor", "F"} if self.fisher == "empirical" else {"anchor"})
+        if {k for k in ("anchor", "F") if k in sd} != need:
+            raise ValueError(f"EWC.load_state_dict: {tasks} task(s) with fisher={self.fisher!r} need exactly the tensors {sorted(need)}")
+        for k in need:
+            t = sd[k]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (n,):
+                raise ValueError(f"EWC.load_state_dict: '{k}' must be a float32 tensor of {n} elements (this optimiser's flat buffer), "
+                                 f"got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        if int(sd["numel"]) != n:
+            raise ValueError(f"EWC.load_state_dict: the state belongs to a flat buffer of {int(sd['numel'])} elements, this one has {n}")
+        gamma = float(sd["gamma"])
+        if not 0.0 <= gamma <= 1.0:
+            raise ValueError(f"EWC.load_state_dict: gamma must be in [0, 1], got {gamma!r}")
+        dev = self.optimizer.flat_p.device
+        self.anchor = sd["anchor"].to(dev).clone() if "anchor" in need else None
+        self.F = sd["F"].to(dev).clone() if "F" in need else None
+        self.gamma, self.tasks, self.active = gamma, tasks, tasks > 0
+        self._acc, self.samples, self._applied = None, 0, False
