@@ -386,6 +386,21 @@ int cxrk_gelu_bwd(const float* dy, const float* pre, long n, float* dx, hipStrea
  *              touches nothing else; at +-Inf, g * (t c) may be 0 * Inf (the "0 or NaN" clause above).
  * sigmoid_pairs_loss: loss_out[0] = (accumulate ? loss_out[0] : 0) + scale * sum partials[0..n); one block, fixed order (plane 0 with
  *              scale 1/Bg gives the loss; logit_scale_grad on plane 1 gives d theta and on plane 2 d b, with partials2 = NULL).
+ * distill:     similarity distillation from a frozen teacher: S is the student's logits block and St the teacher's,
+ *              both [rows][cols] (rows ld / ldt >= cols floats apart), St read-only and distinct from S.  With p = softmax of a row
+ *              of S and pt = that of St, row_stats writes per row lse[i], lse_t[i] and
+ *                  kl[i] = sum_j pt_ij (St_ij - S_ij) + (lse[i] - lse_t[i])      (= KL(pt_i || p_i)),
+ *              in one pass over the two rows, and, with loss_out, loss_out[0] = (accumulate ? loss_out[0] : 0) + loss_scale * sum_i
+ *              kl[i] from one block in a fixed order (no atomics).  grad_inplace turns S into
+ *                  (exp(S-lse_row[i]) - exp(St-lse_t_row[i])) + (exp(S-lse_col[j]) - exp(St-lse_t_col[j])).
+ *              Exact fp32 in both precision modes.  One 256-thread block per row; 16-byte accesses where ld % 4 == 0, ldt % 4 == 0 and
+ *              both bases are 16-byte aligned, scalar otherwise; columns cols..ld of a row are never read or written.  No scratch
+ *              memory: every output is the caller's.  Two runs are bit-identical.  IDENTICAL INPUTS GIVE EXACT ZEROS: if St equals S
+ *              bit for bit (and lse_t_row / lse_t_col equal lse_row / lse_col), every kl[i] and every element of the gradient block is
+ *              exactly 0.0 -- each summand of kl carries the factor (St_ij - S_ij), the two log-sum-exps come from the same code, and
+ *              the gradient groups student - teacher per direction.  Non-finite values: a NaN in row i of S makes lse[i], kl[i] and
+ *              the loss NaN, a NaN in row i of St makes lse_t[i], kl[i] and the loss NaN; no other row's outputs are touched and
+ *              nothing is clamped or replaced.
  * clamp_inplace: x[i] = min(max(x[i], lo), hi) for lo <= hi; a NaN stays a NaN.
  * pairwise_cosine: torchmetrics pairwise_cosine_similarity as called by Trainer.myCosineSimilarity (Trainer.py:1682-1704).
  * pairwise_cosine_max: the MAX_EMB branch of the same function (Trainer.py:1691-1693): y holds G groups of Pg prompt
@@ -428,6 +443,10 @@ int cxrk_sigmoid_pairs_fwd_bwd_inplace(float* C, long ld, int rows, int cols, in
                                        const long long* keys_col, const float* log_scale, const float* bias, float* partials,
                                        hipStream_t stream);
 int cxrk_sigmoid_pairs_loss(const float* partials, long n, float scale, float* loss_out, int accumulate, hipStream_t stream);
+int cxrk_distill_row_stats(const float* S, long ld, const float* St, long ldt, int rows, int cols, float* lse, float* lse_t,
+                           float* kl, float* loss_out, float loss_scale, int loss_accumulate, hipStream_t stream);
+int cxrk_distill_grad_inplace(float* S, long ld, const float* St, long ldt, int rows, int cols, const float* lse_row,
+                              const float* lse_col, const float* lse_t_row, const float* lse_t_col, hipStream_t stream);
 int cxrk_clamp_inplace(float* x, long n, float lo, float hi, hipStream_t stream);
 int cxrk_pairwise_cosine_fwd(const float* x, const float* y, long B, int P, int D, float* cosv, float* xnorm,
                              float* ynorm, hipStream_t stream);

@@ -42,6 +42,10 @@ Two extensions behind the same entry points (both off unless asked for):
     `"ewc_gamma"` in [0, 1], `"ewc_batches"`: the most batches one estimate reads): `consolidate(loader)` after a task anchors the
     parameters and estimates their importance, later steps carry the quadratic penalty; `train` logs `train/ewc_penalty` once per
     epoch while it is active, `save` / `load` carry the state as `ewc.pt`.
+    `"distill_weight": beta` (optionally `"distill_temperature": tau_d`, default "temperature") adds similarity distillation from a
+    frozen teacher: `snapshot_teacher()` after a task freezes the current encoders, later steps add beta * L_d, the
+    KL divergence of the teacher's image-text similarity distributions over the batch from the student's; `train` logs
+    `train/distill` once per epoch while a teacher exists, `save` / `load` carry the teacher as `teacher.pt`.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -135,6 +139,7 @@ class Trainer:
         trainable parameters are the two encoders.  `process_group`: the data-parallel group (default: the default group when
         `torch.distributed` is initialised)."""
         self._ewc_batches = self._check_ewc_keys(joint_encoders)
+        self._check_distill_keys(joint_encoders)
         self.pos_mean_counter = 0
         self.neg_mean_counter = 0
         self.n_reset = 0
@@ -181,7 +186,8 @@ class Trainer:
                                                   temperature=float(je.get("temperature", 0.07)), group=process_group,
                                                   optim=je["optim"] if je.get("optim") is not None else OPTIM,
                                                   **{k: je[k] for k in ("weight_decay", "max_grad_norm", "warmup_steps", "total_steps",
-                                                                        "lr_decay", "min_lr_ratio", "ewc_lambda", "ewc_gamma", "ewc_fisher")
+                                                                        "lr_decay", "min_lr_ratio", "ewc_lambda", "ewc_gamma", "ewc_fisher",
+                                                                        "distill_weight", "distill_temperature")
                                                      if je.get(k) is not None},
                                                   positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
                                                   **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
@@ -264,6 +270,23 @@ class Trainer:
         if nb is not None and (isinstance(nb, bool) or not isinstance(nb, int) or nb < 1):
             raise ValueError(f"joint_encoders['ewc_batches'] must be an integer >= 1, got {nb!r}")
         return nb
+
+    DISTILL_KEYS = ("distill_weight", "distill_temperature")
+
+    @staticmethod
+    def _check_distill_keys(joint_encoders) -> None:
+        """the "distill_*" entries of `joint_encoders`, checked before anything is built.  They configure the joint trainer: without an
+        "image_model" there is none, and they are refused."""
+        if not isinstance(joint_encoders, dict):
+            return
+        given = [k for k in Trainer.DISTILL_KEYS if joint_encoders.get(k) is not None]
+        if given and joint_encoders.get("image_model") is None:
+            raise ValueError(f"joint_encoders: {given} configure similarity distillation of the joint-encoder step and need joint mode "
+                             f"(an 'image_model'); the adapter schedules have no teacher")
+        if given and joint_encoders.get("distill_weight") is None:
+            raise ValueError(f"joint_encoders: {given} are options of 'distill_weight' and were given without it")
+        from .contrastive import check_distill_options
+        check_distill_options(joint_encoders.get("distill_weight"), joint_encoders.get("distill_temperature"))
 
     # ------------------------------------------------------------------------------------------------ data
     @staticmethod
@@ -763,6 +786,9 @@ class Trainer:
         penalty = self._joint.current_penalty()     # None without "ewc_lambda" and before the first penalised step
         if penalty is not None:
             self.writer.add_scalar('train/ewc_penalty', penalty, epoch)
+        distill = self._joint.current_distill()     # None without a teacher and before the first distilled step
+        if distill is not None:
+            self.writer.add_scalar('train/distill', distill, epoch)
 
     @staticmethod
     def _parse_retrieval(opt):
@@ -898,6 +924,14 @@ class Trainer:
 
         return self._joint.consolidate(shards(), max_batches=self._ewc_batches)
 
+    def snapshot_teacher(self) -> None:
+        """End of a task with `joint_encoders={..., "distill_weight": beta}`: freeze the current encoders as the
+        teacher of the tasks that follow (`JointContrastiveTrainer.snapshot_teacher`).  Every rank calls it, as it calls the training
+        loop."""
+        if self._joint is None or self._joint.distill_weight is None:
+            raise ValueError("Trainer.snapshot_teacher needs joint_encoders={..., 'distill_weight': beta}")
+        self._joint.snapshot_teacher()
+
     @torch.no_grad()
     def model_copy(self):
         """Snapshot the adapters before a step (`Trainer.py:1634-1641`)."""
@@ -984,6 +1018,8 @@ class Trainer:
                 torch.save(sd, os.path.join(self.writer.log_dir, 'logit_scale.pt'))
             if self._joint.ewc is not None:
                 torch.save(self._joint.ewc.state_dict(), os.path.join(self.writer.log_dir, 'ewc.pt'))
+            if self._joint.teacher is not None:
+                torch.save(self._joint.teacher.state_dict(), os.path.join(self.writer.log_dir, 'teacher.pt'))
         if hasattr(self.writer, "flush"):
             self.writer.flush()
 
@@ -1021,4 +1057,10 @@ class Trainer:
                     self._joint.logit_bias.data.copy_(sd["logit_bias"].reshape(1))
             if self._joint.ewc is not None:   # keys, fisher kind and the size of F / anchor are checked by `EWC.load_state_dict`
                 self._joint.ewc.load_state_dict(torch.load(os.path.join(self.writer.log_dir, 'ewc.pt'), map_location="cpu", weights_only=True))
+            tpath = os.path.join(self.writer.log_dir, 'teacher.pt')
+            if self._joint.distill_weight is not None and os.path.exists(tpath):
+                # (a run saved before its first snapshot wrote no file and has no teacher.)  The copies are built from the encoders
+                # just loaded, then take the saved tensors; size and keys are checked by `FrozenTeacher.load_state_dict`
+                self._joint.snapshot_teacher()
+                self._joint.teacher.load_state_dict(torch.load(tpath, map_location="cpu", weights_only=True))
             self._bert_cache.clear()

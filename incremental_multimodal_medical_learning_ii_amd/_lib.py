@@ -89,6 +89,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_logit_scale_grad": (I, [P, L, P, L, P, F, P, I, P]),
     "cxrk_sigmoid_pairs_fwd_bwd_inplace": (I, [P, L, I, I, I, P, P, P, P, P, P]),
     "cxrk_sigmoid_pairs_loss": (I, [P, L, F, P, I, P]),
+    "cxrk_distill_row_stats": (I, [P, L, P, L, I, I, P, P, P, P, F, I, P]),
+    "cxrk_distill_grad_inplace": (I, [P, L, P, L, I, I, P, P, P, P, P]),
     "cxrk_clamp_inplace": (I, [P, L, F, F, P]),
     "cxrk_pairwise_cosine_fwd": (I, [P, P, L, I, I, P, P, P, P]),
     "cxrk_pairwise_cosine_bwd_ws_bytes": (Z, [L, I, I]),

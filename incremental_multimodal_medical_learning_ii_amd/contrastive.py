@@ -38,6 +38,13 @@ every chunk but the last is embedded without keeping activations, the loss runs 
 run again with its graph to take its slice of dL/d(embedding) through the encoders into the flat gradient buffer.  The loss, its
 collectives and the update are those of the unchunked step up to fp32 summation order; the peak memory is that of one chunk.
 `micro_batch=None` (the default) or n >= this rank's rows issues exactly the calls it always did.
+
+`distill_weight=beta`: similarity distillation from a frozen teacher (Learning without Forgetting in the
+similarity-distribution form of ZSCL / Mod-X).  `snapshot_teacher()` freezes the current encoders (`FrozenTeacher`: one flat copy of the
+parameters, +4 B per parameter); from then on every step also runs the teacher's two encoders save-free on the same rows and adds
+beta * L_d (`functional.distill_loss`) to the objective: two more collectives than the plain step's (the [B, 4D] embedding gather and
+the [B, 4] log-sum-exp gather) and one scalar all-reduce.  Before the first snapshot, and with `distill_weight=None` (the default),
+a step issues exactly the calls it always did.
 """
 from __future__ import annotations
 
@@ -234,6 +241,92 @@ def micro_slices(n: int, micro_batch: int) -> Tuple[Tuple[int, int], ...]:
     return tuple((lo, min(lo + m, n)) for lo in range(0, n, m))
 
 
+def check_distill_options(distill_weight, distill_temperature) -> Tuple[Optional[float], Optional[float]]:
+    """(beta, tau_d) of `JointContrastiveTrainer(distill_weight=, distill_temperature=)` as floats or None: beta finite and >= 0
+    (bools refused), tau_d positive and finite and only together with beta"""
+    if distill_weight is None:
+        if distill_temperature is not None:
+            raise ValueError("distill_temperature is an option of similarity distillation; it was given without distill_weight")
+        return None, None
+    if isinstance(distill_weight, bool) or not isinstance(distill_weight, (int, float)) or not (math.isfinite(distill_weight) and distill_weight >= 0):
+        raise ValueError(f"distill_weight must be finite and >= 0, got {distill_weight!r}")
+    if distill_temperature is not None:
+        if (isinstance(distill_temperature, bool) or not isinstance(distill_temperature, (int, float))
+                or not (math.isfinite(distill_temperature) and distill_temperature > 0)):
+            raise ValueError(f"distill_temperature must be positive and finite, got {distill_temperature!r}")
+        distill_temperature = float(distill_temperature)
+    return float(distill_weight), distill_temperature
+
+
+class FrozenTeacher:
+    """The frozen teacher of similarity distillation: structural copies of the two encoders whose optimised
+    parameters are views of ONE flat copy of `optimizer.flat_p` (+4 B per parameter), laid out exactly as the student's are in its
+    flat buffer (so fused q/k/v stay adjacent and filters keep their memory format); module buffers (BatchNorm running statistics)
+    and parameters outside the optimiser are cloned.  Both copies are in eval mode for good, require no gradient, belong to no
+    optimiser and no reduce span, and never take a hook, dropout or a gradient.  `refresh()` overwrites the flat copy and the cloned
+    tensors IN PLACE: every tensor the copies hold keeps its identity, and the encoders derive nothing from their parameters that
+    outlives a forward (q/k/v are fused by adjacency, BatchNorm is folded and planes are split per call), so nothing is stale."""
+
+    def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, optimizer):
+        import copy
+        self.flat = optimizer.flat_p.detach().clone()
+        self.numel = int(optimizer.numel)
+        base = optimizer.flat_p.data_ptr()
+        memo = {}
+        for p in optimizer.params:
+            o = (p.data_ptr() - base) // 4
+            view = self.flat[o:o + p.numel()].as_strided(p.shape, p.stride())
+            memo[id(p)] = torch.nn.Parameter(view, requires_grad=False)
+        self.image_model = copy.deepcopy(image_model, memo)
+        self.text_model = copy.deepcopy(text_model, memo)
+        self._pairs = []                      # (teacher tensor, student tensor) of everything that does not live in the flat copy
+        shared = {id(v) for v in memo.values()}
+        for tm, sm in ((self.image_model, image_model), (self.text_model, text_model)):
+            tm.eval()
+            tm.grad_ready_hook = None
+            tm.save_free = False
+            for tp, sp in zip(tm.parameters(), sm.parameters()):
+                tp.requires_grad_(False)
+                tp.grad = None
+                if id(tp) not in shared:
+                    self._pairs.append((tp, sp))
+            self._pairs += list(zip(tm.buffers(), sm.buffers()))
+        if hasattr(self.text_model, "_dropout"):
+            self.text_model._dropout = None   # eval mode already draws none; the copy does not carry the student's stream either
+
+    @torch.no_grad()
+    def refresh(self, optimizer) -> None:
+        """take the student's current parameters and buffers, in place"""
+        self.flat.copy_(optimizer.flat_p)
+        for t, s in self._pairs:
+            t.copy_(s)
+
+    def state_dict(self) -> dict:
+        """tensors and plain numbers only (loadable with weights_only=True): the flat copy and the cloned tensors, in module order"""
+        return {"numel": self.numel, "flat": self.flat.detach().cpu(), "tensors": [t.detach().cpu() for t, _ in self._pairs]}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """strict: the keys of `state_dict()`, a flat copy of exactly this optimiser's size, the cloned tensors' number and shapes"""
+        if not isinstance(sd, dict) or set(sd) != {"numel", "flat", "tensors"}:
+            raise ValueError(f"FrozenTeacher.load_state_dict: expected the keys ['flat', 'numel', 'tensors'], got "
+                             f"{sorted(sd) if isinstance(sd, dict) else type(sd).__name__}")
+        flat, tensors = sd["flat"], sd["tensors"]
+        if int(sd["numel"]) != self.numel or not isinstance(flat, torch.Tensor) or flat.dtype != torch.float32 or tuple(flat.shape) != (self.numel,):
+            raise ValueError(f"FrozenTeacher.load_state_dict: 'flat' must be a float32 tensor of {self.numel} elements (this optimiser's "
+                             f"flat buffer), got numel {sd['numel']!r} and {tuple(flat.shape) if isinstance(flat, torch.Tensor) else type(flat).__name__}")
+        if not isinstance(tensors, (list, tuple)) or len(tensors) != len(self._pairs):
+            raise ValueError(f"FrozenTeacher.load_state_dict: expected {len(self._pairs)} cloned tensors, got "
+                             f"{len(tensors) if isinstance(tensors, (list, tuple)) else type(tensors).__name__}")
+        for k, ((t, _), v) in enumerate(zip(self._pairs, tensors)):
+            if not isinstance(v, torch.Tensor) or v.dtype != t.dtype or tuple(v.shape) != tuple(t.shape):
+                raise ValueError(f"FrozenTeacher.load_state_dict: cloned tensor {k} must be {t.dtype} {tuple(t.shape)}, got "
+                                 f"{getattr(v, 'dtype', type(v).__name__)} {tuple(getattr(v, 'shape', ()))}")
+        self.flat.copy_(flat)
+        for (t, _), v in zip(self._pairs, tensors):
+            t.copy_(v)
+
+
 class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
@@ -243,7 +336,8 @@ class JointContrastiveTrainer:
                  micro_batch: Optional[int] = None, weight_decay: Optional[float] = None, max_grad_norm: Optional[float] = None,
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, lr_decay: Optional[str] = None,
                  min_lr_ratio: Optional[float] = None, ewc_lambda: Optional[float] = None, ewc_gamma: Optional[float] = None,
-                 ewc_fisher: Optional[str] = None):
+                 ewc_fisher: Optional[str] = None, distill_weight: Optional[float] = None,
+                 distill_temperature: Optional[float] = None):
         """`optim="adamw"`: `optim.AdamW` with decoupled `weight_decay` (default 0.01; parameters with ndim <= 1 do
         not decay) and, with `max_grad_norm`, clipping of the global gradient norm (`inf`: the norm is taken and reported, nothing
         is clipped).  `warmup_steps` / `total_steps` / `lr_decay` ("constant" | "linear" | "cosine") / `min_lr_ratio`: an
@@ -251,8 +345,16 @@ class JointContrastiveTrainer:
         `ewc_lambda`: elastic weight consolidation, an `optim.EWC` of that strength over the optimiser's flat
         buffers (`ewc_fisher` "empirical" | "identity", `ewc_gamma` in [0, 1]).  Until the first `consolidate(batches)` a step is
         bit for bit the step without it; afterwards `step` adds the penalty's gradient between the gradient all-reduce and the
-        optimiser's step, so clipping and the update see it exactly as if the penalty were part of the loss."""
+        optimiser's step, so clipping and the update see it exactly as if the penalty were part of the loss.
+        `distill_weight` = beta: similarity distillation from a frozen teacher; `distill_temperature` = tau_d
+        (default: `temperature`).  Until the first `snapshot_teacher()` a step is bit for bit the step without it; afterwards the
+        step's objective is contrastive + beta * L_d, with L_d of `functional.distill_loss` against the snapshot's encoders."""
         self.micro_batch = check_micro_batch(micro_batch)
+        self.distill_weight, self.distill_temperature = check_distill_options(distill_weight, distill_temperature)
+        self.teacher: Optional[FrozenTeacher] = None
+        self._distill_off = False            # `consolidate` estimates the Fisher diagonal of the contrastive loss alone
+        self._pending_distill = None         # beta * L_d of the forward whose backward has not run yet
+        self._last_distill = None            # L_d of the last distilled step (device scalar)
         if ewc_lambda is None and (ewc_gamma is not None or ewc_fisher is not None):
             raise ValueError("ewc_gamma / ewc_fisher are options of elastic weight consolidation; they were given without ewc_lambda")
         if optim not in OPTIMS:
@@ -470,30 +572,91 @@ class JointContrastiveTrainer:
         each encoder's backward on the stream its forward ran on and joins them again before `backward()` returns.
         Text dropout masks are keyed by the global sequence index: this rank's shard starts at rank * local rows (the shards are
         equal and contiguous, gathered in rank order).
-        `labels` / `keys`: see `pair_keys`; computed once, before the encoders run."""
+        `labels` / `keys`: see `pair_keys`; computed once, before the encoders run.
+        With a teacher (`snapshot_teacher`) its two encoders run first, save-free, and beta * L_d on the same embeddings is left for
+        `_backward(loss)`, which `step` uses in place of `loss.backward()`; the returned scalar is the contrastive loss alone."""
         keys = self.pair_keys(input_ids, attention_mask, labels, keys)
         if keys is not None:
             keys = keys.to(images.device, non_blocking=True)
         self.text_model.dropout_row_offset = self.rank * int(input_ids.shape[0])
+        taught = self._teacher_pair(images, input_ids, attention_mask) if self._distilling() else None   # first: it keeps nothing
         img, txt = self._encode_pair(images, input_ids, attention_mask)
-        return self._loss(img, txt, keys)
+        loss = self._loss(img, txt, keys)
+        if taught is not None:
+            self._distill_head(img, txt, *taught)
+        return loss
 
-    def _encode_pair(self, images, input_ids, attention_mask) -> Tuple[torch.Tensor, torch.Tensor]:
-        """both encoders on the same rows -> (image embeddings, text embeddings), the text encoder on the second stream"""
+    def _encode_pair(self, images, input_ids, attention_mask, models=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """both encoders (`models`: another pair, the teacher's) on the same rows -> (image embeddings, text embeddings), the text
+        encoder on the second stream"""
+        im, tm = (self.image_model, self.text_model) if models is None else models
         if not (self.two_streams and images.is_cuda):
-            img = self.image_model(images)
-            txt = self.text_model.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
+            img = im(images)
+            txt = tm.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
             return img, txt
         if self._text_stream is None:
             self._text_stream = torch.cuda.Stream(device=images.device)
         cur = torch.cuda.current_stream(images.device)
         self._text_stream.wait_stream(cur)                     # inputs, weights and the zeroed gradients are ready
         with torch.cuda.stream(self._text_stream):
-            txt = self.text_model.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
-        img = self.image_model(images)
+            txt = tm.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
+        img = im(images)
         cur.wait_stream(self._text_stream)
         txt.record_stream(cur)
         return img, txt
+
+    # ------------------------------------------------------------------ similarity distillation (DESIGN.md §5.11)
+    def snapshot_teacher(self) -> None:
+        """End of a task (needs `distill_weight`): freeze the current encoders as the teacher of the steps that follow.  The first
+        call builds the copies (`FrozenTeacher`); a later one overwrites their flat parameter copy and buffers in place.  Under
+        data parallelism every rank calls it at the same step: the replicas are identical, so are the teachers, and nothing is
+        communicated."""
+        if self.distill_weight is None:
+            raise ValueError("JointContrastiveTrainer.snapshot_teacher: this trainer was constructed without distill_weight")
+        if self.teacher is None:
+            self.teacher = FrozenTeacher(self.image_model, self.text_model, self.optimizer)
+        else:
+            self.teacher.refresh(self.optimizer)
+
+    def current_distill(self) -> Optional[float]:
+        """the unweighted L_d of the last distilled step as a host float (None without a teacher or before the first distilled step):
+        a host sync, and only when called"""
+        return None if self._last_distill is None else float(self._last_distill.detach().cpu())
+
+    def _distilling(self) -> bool:
+        return self.teacher is not None and not self._distill_off
+
+    def _teacher_pair(self, images, input_ids, attention_mask) -> Tuple[torch.Tensor, torch.Tensor]:
+        """the teacher's two encoders on the same rows, under no_grad through the save-free path (the same kernels, nothing kept).
+        The teacher sees the images as the student does: it carries the student's augment call of this moment (`save_free` applies
+        it under no_grad).  Eval mode: running statistics, no dropout."""
+        t = self.teacher
+        t.image_model.augment_call = self.image_model.augment_call
+        t.image_model.save_free = t.text_model.save_free = True
+        try:
+            with torch.no_grad():
+                return self._encode_pair(images, input_ids, attention_mask, models=(t.image_model, t.text_model))
+        finally:
+            t.image_model.augment_call = None
+            t.image_model.save_free = t.text_model.save_free = False
+
+    def _distill_head(self, img, txt, img_t, txt_t) -> None:
+        """L_d on the step's embeddings: beta * L_d waits in `_pending_distill` for the step's one backward; beta = 0 keeps no graph"""
+        tau = self.temperature if self.distill_temperature is None else self.distill_temperature
+        if self.distill_weight > 0:
+            self._pending_distill, self._last_distill = Fh._distill_pair(img, txt, img_t, txt_t, tau, self.distill_weight, self.group)
+        else:
+            with torch.no_grad():
+                _, self._last_distill = Fh._distill_pair(img, txt, img_t, txt_t, tau, 0.0, self.group)
+
+    def _backward(self, loss: torch.Tensor) -> None:
+        """the step's one backward: the contrastive loss and, when a forward left one, beta * L_d, as two roots of one graph walk (each
+        encoder's backward runs once, on the sum of both gradients of its embeddings)"""
+        d, self._pending_distill = self._pending_distill, None
+        if d is None:
+            loss.backward()
+        else:
+            torch.autograd.backward([loss, d])
 
     def _loss(self, img, txt, keys):
         if self.loss == "sigmoid":
@@ -510,6 +673,7 @@ class JointContrastiveTrainer:
         global-batch gradient, identical on every rank.  Shared by `step` and `consolidate`."""
         slices = ((0, int(images.shape[0])),) if self.micro_batch is None else micro_slices(int(images.shape[0]), self.micro_batch)
         chunked = len(slices) > 1
+        self._pending_distill = None
         if chunked:
             self._require_eval_batchnorm()
         self.optimizer.zero_grad()
@@ -536,7 +700,7 @@ class JointContrastiveTrainer:
                     loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
                 finally:
                     self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
-                loss.backward()
+                self._backward(loss)
             self.last_overlapped = tuple(fired)
             self.optimizer.all_reduce_grads(self.group, skip=[self._spans[t] for t in fired], pending=works)
         else:
@@ -544,7 +708,7 @@ class JointContrastiveTrainer:
                 loss = self._chunked_forward_backward(images, input_ids, attention_mask, labels, keys, slices, None)
             else:
                 loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)
-                loss.backward()
+                self._backward(loss)
             if self.world > 1:
                 self.optimizer.all_reduce_grads(self.group)
         return loss
@@ -580,7 +744,8 @@ class JointContrastiveTrainer:
         of more than one dimension is taken as labels, a 1-D one as keys -- the gradient is computed as in `step` (the same
         `micro_batch` chunks, the same overlapped all-reduce) and its square accumulated; then `optim.EWC.consolidate()`.  No
         optimiser update, no schedule advance, no clamp: `optimizer.steps`, the moments and the parameters stay as they are.  It
-        never augments and leaves the augmentation counter alone.  With `ewc_fisher="identity"` no batch is read.  Under data
+        never augments and leaves the augmentation counter alone; nor does it distil (`distill_weight`): F is the Fisher diagonal of
+        the contrastive loss alone.  With `ewc_fisher="identity"` no batch is read.  Under data
         parallelism every rank calls it with its shards; F comes from the all-reduced gradient, so it needs no collective of its
         own and is bit-identical on every rank."""
         if self.ewc is None:
@@ -589,6 +754,7 @@ class JointContrastiveTrainer:
         if self.ewc.fisher == "empirical":
             self.ewc.begin_estimate()
             augment, self._augment = self._augment, None      # the images as they are; the counter does not move
+            self._distill_off = True                          # the Fisher diagonal of the contrastive loss alone: no teacher runs
             try:
                 for batch in batches:
                     if max_batches is not None and used >= max_batches:
@@ -604,6 +770,7 @@ class JointContrastiveTrainer:
                     used += 1
             finally:
                 self._augment = augment
+                self._distill_off = False
         self.ewc.consolidate()
         return used
 
@@ -660,15 +827,32 @@ class JointContrastiveTrainer:
                 im.save_free = tm.save_free = False
                 im.grad_ready_hook = tm.grad_ready_hook = None
 
+        def teach(lo, hi):
+            if aug is not None:       # `_teacher_pair` hands the teacher the student's call of this moment
+                im.augment_call = AugmentCall(self.augment, aug[0], aug[1], base + lo)
+            try:
+                return self._teacher_pair(images[lo:hi], input_ids[lo:hi], attention_mask[lo:hi])
+            finally:
+                im.augment_call = None
+
+        taught = None
+        if self._distilling():      # the teacher's embeddings of ALL rows, chunk by chunk, next to the student's cache
+            pairs = [teach(lo, hi) for lo, hi in slices]
+            taught = (torch.cat([i for i, _ in pairs]), torch.cat([t for _, t in pairs]))
+            del pairs
         cached = [encode(lo, hi, save_free=True) for lo, hi in slices[:-1]]            # pass 1: advances no counter
         ci = torch.cat([i for i, _ in cached]).requires_grad_()
         ct = torch.cat([t for _, t in cached]).requires_grad_()
         del cached
         img, txt = encode(*slices[-1])                                                   # advances the dropout counter, once
         drop_after = drop[1] if drop is not None else None
-        loss = self._loss(torch.cat((ci, img)), torch.cat((ct, txt)), keys)
+        img_all, txt_all = torch.cat((ci, img)), torch.cat((ct, txt))
         del img, txt
-        loss.backward()
+        loss = self._loss(img_all, txt_all, keys)
+        if taught is not None:
+            self._distill_head(img_all, txt_all, *taught)
+        del img_all, txt_all, taught
+        self._backward(loss)
         loss = loss.detach()
         gi, gt = ci.grad, ct.grad
         try:

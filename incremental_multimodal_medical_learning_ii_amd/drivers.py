@@ -7,6 +7,7 @@ and `DATA_INCREMENTAL.py:74-97` (hyper-parameters as arguments instead of litera
 
     python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --parts 5 --joint --batch-size 1024 --epochs 1
     python -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --joint --cl ewc --ewc-lambda 1e4 --ewc-batches 8
+    python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --joint --cl lwf --distill-weight 1.0
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29511 \
         -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --mode class-pos-neg --batch-size 2048
 
@@ -128,6 +129,7 @@ def _setup(args, kind):
                                              "micro_batch": getattr(args, "micro_batch", None),
                                              **optimiser_from_args(args, kind, train_loader),
                                              **ewc_from_args(args),
+                                             **distill_from_args(args),
                                              "augment": augment_from_args(args),
                                              "retrieval": retrieval_from_args(args)})
     else:
@@ -179,6 +181,20 @@ def ewc_from_args(args) -> dict:
     for flag in ("ewc_batches", "ewc_gamma", "ewc_fisher"):
         if getattr(args, flag, None) is not None:
             out[flag] = getattr(args, flag)
+    return out
+
+
+DISTILL_WEIGHT = 1.0     # beta of --cl lwf: the distillation term enters at the weight of the contrastive loss
+
+
+def distill_from_args(args) -> dict:
+    """`--cl lwf` / `--distill-weight` / `--distill-temperature` -> the `joint_encoders` keys they set (without `--cl lwf`: an empty
+    dict)"""
+    if getattr(args, "cl", None) != "lwf":
+        return {}
+    out = {"distill_weight": DISTILL_WEIGHT if args.distill_weight is None else args.distill_weight}
+    if getattr(args, "distill_temperature", None) is not None:
+        out["distill_temperature"] = args.distill_temperature
     return out
 
 
@@ -247,6 +263,8 @@ def class_incremental(args):
                     trainer.profIncremental(epoch, args.epochs, actual_task, threshold)
             if args.cl == "ewc" and actual_task < len(tasks_order):      # anchor this task before the next one starts
                 trainer.consolidate(train_loader[actual_task - 1])
+            if args.cl == "lwf" and actual_task < len(tasks_order):      # this task's encoders teach the next one
+                trainer.snapshot_teacher()
             trainer.val(val_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
             metrics = trainer.test(test_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
     finally:
@@ -274,6 +292,8 @@ def data_incremental(args):
                     trainer.profIncremental(epoch, args.epochs, part, threshold)
             if args.cl == "ewc" and part < args.parts:
                 trainer.consolidate(train_loader[part - 1])
+            if args.cl == "lwf" and part < args.parts:
+                trainer.snapshot_teacher()
             train_loader[part - 1] = None
             trainer.val(val_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
             metrics = trainer.test(test_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
@@ -293,9 +313,10 @@ def make_parser():
     ap.add_argument("--more-labels", action="store_true")
     ap.add_argument("--single-prompt", action="store_true")
     ap.add_argument("--xrays-position", default="all")
-    ap.add_argument("--cl", default=None, choices=[None, "myCL", "profCL", "ewc"],
+    ap.add_argument("--cl", default=None, choices=[None, "myCL", "profCL", "ewc", "lwf"],
                     help="continual learning: the reference's weight-reset heuristics (myCL, profCL) or, with --joint, elastic weight "
-                         "consolidation (ewc, DESIGN.md 5.10)")
+                         "consolidation (ewc, DESIGN.md 5.10) or similarity distillation from the previous task's encoders (lwf, "
+                         "DESIGN.md 5.11)")
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--adder", type=float, default=0.001)
     ap.add_argument("--threshold-scheduling", action="store_true")
@@ -356,6 +377,11 @@ def make_parser():
                     help="--cl ewc: F = G * F_old + F_new when a further task is consolidated, G in [0, 1] (default 1)")
     ap.add_argument("--ewc-fisher", default=None, choices=["empirical", "identity"],
                     help="--cl ewc: empirical Fisher diagonal (default) or identity (L2-SP: no estimate, half the memory)")
+    ap.add_argument("--distill-weight", type=float, default=None, metavar="BETA",
+                    help="--cl lwf: weight of the distillation term L_d in the step's objective contrastive + BETA * L_d (default 1.0; 0 "
+                         "only measures the drift)")
+    ap.add_argument("--distill-temperature", type=float, default=None, metavar="TAU",
+                    help="--cl lwf: the fixed temperature of the distilled similarity distributions (default: --temperature)")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -379,6 +405,19 @@ def parse_args(argv=None):
             ap.error(f"--ewc-gamma must be in [0, 1], got {args.ewc_gamma}")
         if args.ewc_batches is not None and args.ewc_batches < 1:
             ap.error(f"--ewc-batches must be >= 1, got {args.ewc_batches}")
+    given = [f for f in ("distill_weight", "distill_temperature") if getattr(args, f) is not None]
+    if given and args.cl != "lwf":
+        ap.error("--" + given[0].replace("_", "-") + " configures similarity distillation and needs --cl lwf")
+    if args.cl == "lwf":
+        if args.which == "zero-joint":
+            ap.error("--cl lwf takes its teacher between tasks; zero-joint trains a single task (use class-inc or data-inc)")
+        if not args.joint:
+            ap.error("--cl lwf distils the encoders of the north-star step and needs --joint (the adapter schedules keep the "
+                     "reference's weight-reset heuristics myCL / profCL)")
+        if args.distill_weight is not None and not (args.distill_weight >= 0 and args.distill_weight != float("inf")):
+            ap.error(f"--distill-weight must be finite and >= 0, got {args.distill_weight}")
+        if args.distill_temperature is not None and not (args.distill_temperature > 0 and args.distill_temperature != float("inf")):
+            ap.error(f"--distill-temperature must be positive and finite, got {args.distill_temperature}")
     return args
 
 

@@ -6,10 +6,12 @@
     group_mean                   prompt-embedding mean            Trainer.py:1665-1666
     posneg_bce_loss              pos-neg logits + BCEWithLogits   Trainer.py:575-583, ZERO_JOINT_BOUNDS.py:36
     infonce_loss                 north-star contrastive head (not in the reference), data-parallel aware
+    distill_loss                 similarity distillation from a frozen teacher's embeddings (not in the reference), data-parallel aware
     augment_images               on-device random affine + jitter (train-time transforms; no gradient)
 """
 from __future__ import annotations
 
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -499,6 +501,120 @@ def sigmoid_pairs_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, log_scale: 
     constant.  `keys`: as in `infonce_loss`: pairs with equal keys are positives of each other; None: only a pair's own two
     halves are.  A row may have no positive at all.  The scalars must not be updated in place between forward and backward."""
     return _SigmoidPairs.apply(img_emb, txt_emb, log_scale, logit_bias, group, keys)
+
+
+class _Distill(torch.autograd.Function):
+    """Similarity distillation from a frozen teacher over the GLOBAL batch: with S = I_hat T_hat^T / tau_d of the
+    student and St of the teacher's embeddings, p_i / q_j the softmax of row i / column j of S and pt / qt those of St,
+        L_d = 1/(2 Bg) [ sum_i KL(pt_i || p_i) + sum_j KL(qt_j || q_j) ],      dL_d/dS_ij = (p_ij - pt_ij + q_ij - qt_ij) / (2 Bg).
+    Returns (weight * L_d, L_d); only the first is differentiable, and only with respect to the student's embeddings.
+
+    Data-parallel form, `_InfoNCE`'s protocol with the teacher riding along: ONE all-gather of a [B, 4D] send buffer whose quarters
+    the four normalisations write in place, ONE all-gather of the [B, 4] log-sum-exps (student rows, student columns, teacher rows,
+    teacher columns) and the scalar all-reduce of the loss; every rank then forms the exact gradient for its own rows."""
+
+    @staticmethod
+    def forward(ctx, img, txt, img_t, txt_t, temperature, weight, group):
+        import torch.distributed as dist
+        dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
+        img, txt = img.detach().contiguous(), txt.detach().contiguous()
+        img_t, txt_t = img_t.detach().contiguous(), txt_t.detach().contiguous()
+        if img.dim() != 2 or tuple(txt.shape) != tuple(img.shape):
+            raise ValueError(f"distill_loss: image embeddings are {tuple(img.shape)} but text embeddings {tuple(txt.shape)}")
+        B, D = img.shape
+        if tuple(img_t.shape) != (B, D) or tuple(txt_t.shape) != (B, D):
+            raise ValueError(f"distill_loss: the student's embeddings are {(B, D)} but the teacher's {tuple(img_t.shape)} and "
+                             f"{tuple(txt_t.shape)}")
+        world_ = dist.get_world_size(group) if dist_on else 1
+        if (B * world_) % 4 != 0 or D % 4 != 0:
+            # as in _InfoNCE: fail HERE, before any collective is issued
+            raise ValueError(f"distill_loss: global batch {B * world_} (= {B} rows x {world_} ranks) and embedding size {D} must be "
+                             f"multiples of 4 (drop or pad the ragged last batch)")
+        dev = img.device
+        if dist_on:
+            rank, world = dist.get_rank(group), dist.get_world_size(group)
+            send = torch.empty(B, 4 * D, dtype=torch.float32, device=dev)
+            ih, inorm = K.l2norm_fwd(img, out=send[:, :D])
+            th, tnorm = K.l2norm_fwd(txt, out=send[:, D:2 * D])
+            iht, _ = K.l2norm_fwd(img_t, out=send[:, 2 * D:3 * D])
+            tht, _ = K.l2norm_fwd(txt_t, out=send[:, 3 * D:])
+            every = _all_gather_rows(send, group)                                                  # [Bg, 4D]
+            ih_all, th_all, iht_all, tht_all = (every[:, q * D:(q + 1) * D] for q in range(4))
+        else:
+            rank, world = 0, 1
+            ih, inorm = K.l2norm_fwd(img)
+            th, tnorm = K.l2norm_fwd(txt)
+            iht, _ = K.l2norm_fwd(img_t)
+            tht, _ = K.l2norm_fwd(txt_t)
+            ih_all, th_all, iht_all, tht_all = ih, th, iht, tht
+        Bg = B * world
+        inv_tau = 1.0 / float(temperature)
+        S1 = torch.empty(B, Bg, dtype=torch.float32, device=dev)      # local images x all texts
+        S2 = torch.empty(B, Bg, dtype=torch.float32, device=dev)      # local texts  x all images
+        T1 = torch.empty(B, Bg, dtype=torch.float32, device=dev)      # the teacher's two blocks
+        T2 = torch.empty(B, Bg, dtype=torch.float32, device=dev)
+        K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=inv_tau)
+        K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=inv_tau)
+        K.gemm(iht, tht_all, T1, B, Bg, D, False, True, alpha=inv_tau)
+        K.gemm(tht, iht_all, T2, B, Bg, D, False, True, alpha=inv_tau)
+        loss = torch.zeros((), dtype=torch.float32, device=dev)
+        lse1, lt1, _ = K.distill_row_stats(S1, T1, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+        lse2, lt2, _ = K.distill_row_stats(S2, T2, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
+        if dist_on:
+            dist.all_reduce(loss, group=group)
+            lse_all = _all_gather_rows(torch.stack((lse1, lse2, lt1, lt2), dim=1), group).t().contiguous()    # [4, Bg]
+            lse1_all, lse2_all, lt1_all, lt2_all = lse_all[0], lse_all[1], lse_all[2], lse_all[3]
+        else:
+            lse1_all, lse2_all, lt1_all, lt2_all = lse1, lse2, lt1, lt2
+        ctx.save_for_backward(S1, S2, T1, T2, lse1, lse2, lt1, lt2, lse1_all, lse2_all, lt1_all, lt2_all, ih, th, ih_all, th_all,
+                              inorm, tnorm)
+        ctx.meta = (float(weight) * inv_tau * 0.5 / Bg, Bg)
+        weighted = K.scale_mask(loss.reshape(1), alpha=float(weight)).reshape(())
+        ctx.mark_non_differentiable(loss)
+        return weighted, loss
+
+    @staticmethod
+    def backward(ctx, gloss, _gunweighted):
+        (S1, S2, T1, T2, lse1, lse2, lt1, lt2, lse1_all, lse2_all, lt1_all, lt2_all, ih, th, ih_all, th_all, inorm,
+         tnorm) = ctx.saved_tensors
+        c, Bg = ctx.meta
+        B, D = ih.shape
+        # column j of S1 is text j over all images: its log-sum-exp is row j's of the global S2, and the other way round
+        K.distill_grad_inplace(S1, T1, lse1, lse2_all, lt1, lt2_all)
+        K.distill_grad_inplace(S2, T2, lse2, lse1_all, lt2, lt1_all)
+        dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
+        dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
+        K.gemm(S1, th_all, dih, B, D, Bg, False, False, alpha=c)
+        K.gemm(S2, ih_all, dth, B, D, Bg, False, False, alpha=c)
+        di = K.l2norm_bwd(dih, ih, inorm)
+        dt = K.l2norm_bwd(dth, th, tnorm)
+        g = gloss.reshape(()).contiguous()
+        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None, None, None, None
+
+
+def _distill_pair(img_emb, txt_emb, img_teacher, txt_teacher, temperature, weight=1.0, group=None):
+    """(weight * L_d, L_d) of `distill_loss`; the second scalar carries no graph (the joint trainer reports it)"""
+    for t, name in ((img_teacher, "img_teacher"), (txt_teacher, "txt_teacher")):
+        if not isinstance(t, torch.Tensor) or t.requires_grad:
+            raise ValueError(f"distill_loss: {name} requires grad; the teacher is a constant (detach it, or run it under no_grad)")
+    weight = float(weight)
+    if not (math.isfinite(weight) and weight >= 0.0):
+        raise ValueError(f"distill_loss: weight must be finite and >= 0, got {weight!r}")
+    if not (float(temperature) > 0.0 and math.isfinite(float(temperature))):
+        raise ValueError(f"distill_loss: the temperature must be positive and finite, got {temperature!r}")
+    return _Distill.apply(img_emb, txt_emb, img_teacher, txt_teacher, temperature, weight, group)
+
+
+def distill_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, img_teacher: torch.Tensor, txt_teacher: torch.Tensor,
+                 temperature: float, weight: float = 1.0, group=None) -> torch.Tensor:
+    """weight * L_d, the similarity-distribution distillation loss against a frozen teacher (see `_Distill`), over
+    the global batch (all ranks of `group`, or the default group when initialised), as a device scalar.
+
+    `img_emb` / `txt_emb` [B, D] are the student's unnormalised embeddings of this rank's rows and receive the gradient;
+    `img_teacher` / `txt_teacher` [B, D] are the teacher's embeddings of the same rows, constants: one that requires grad is refused.
+    `temperature` is the fixed distillation temperature tau_d of both logits blocks.  When the teacher's embeddings equal the
+    student's bit for bit, the loss and the gradient are exactly zero."""
+    return _distill_pair(img_emb, txt_emb, img_teacher, txt_teacher, temperature, weight, group)[0]
 
 
 @torch.no_grad()

@@ -1305,6 +1305,54 @@ def sigmoid_pairs_loss(partials, scale: float, out=None, accumulate: bool = Fals
     return out
 
 
+def _block_pair(S, St, what):
+    """the student / teacher logits blocks of the distillation head: two distinct 2-d fp32 blocks of one shape, contiguous columns,
+    rows may be strided -> (rows, cols, ld, ldt)"""
+    for t, name in ((S, "S"), (St, "St")):
+        _chk(t, f"{what}.{name}")
+        if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise ValueError(f"{what}.{name} must be a 2-d block with contiguous columns, got shape {tuple(t.shape)} strides {t.stride()}")
+    if tuple(S.shape) != tuple(St.shape):
+        raise ValueError(f"{what}: the student block is {tuple(S.shape)} but the teacher block {tuple(St.shape)}")
+    rows, cols = S.shape
+    ld = S.stride(0) if rows > 1 else max(cols, S.stride(0))
+    ldt = St.stride(0) if rows > 1 else max(cols, St.stride(0))
+    return rows, cols, ld, ldt
+
+
+def _rowvec(t, n, what):
+    _chk(t, what)
+    if t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous fp32 [{n}] tensor, got shape {tuple(t.shape)} strides {t.stride()}")
+    return t
+
+
+def distill_row_stats(S, St, loss_out=None, loss_scale: float = 0.0, loss_accumulate: bool = False):
+    """(lse, lse_t, kl) per row of the student block S and the teacher block St (include/cxrk.h, "distill"): the two log-sum-exps and
+    KL(softmax(St_i) || softmax(S_i)); with `loss_out` (one fp32 element) also loss_out (+)= loss_scale * sum(kl), in a fixed order."""
+    lib = _lib.load()
+    rows, cols, ld, ldt = _block_pair(S, St, "distill_row_stats")
+    if loss_out is not None and (_chk(loss_out, "distill_row_stats.loss_out").numel() != 1):
+        raise ValueError(f"distill_row_stats.loss_out must hold one element, got shape {tuple(loss_out.shape)}")
+    lse = torch.empty(rows, dtype=torch.float32, device=S.device)
+    lse_t = torch.empty(rows, dtype=torch.float32, device=S.device)
+    kl = torch.empty(rows, dtype=torch.float32, device=S.device)
+    check(lib.cxrk_distill_row_stats(_p(S), ld, _p(St), ldt, rows, cols, _p(lse), _p(lse_t), _p(kl), _p(loss_out), float(loss_scale),
+                                     int(loss_accumulate), _stream()), "cxrk_distill_row_stats")
+    return lse, lse_t, kl
+
+
+def distill_grad_inplace(S, St, lse_row, lse_col, lse_t_row, lse_t_col):
+    """S <- (exp(S - lse_row[i]) - exp(St - lse_t_row[i])) + (exp(S - lse_col[j]) - exp(St - lse_t_col[j])) in place; St is only read."""
+    lib = _lib.load()
+    rows, cols, ld, ldt = _block_pair(S, St, "distill_grad")
+    check(lib.cxrk_distill_grad_inplace(_p(S), ld, _p(St), ldt, rows, cols, _p(_rowvec(lse_row, rows, "distill_grad.lse_row")),
+                                        _p(_rowvec(lse_col, cols, "distill_grad.lse_col")),
+                                        _p(_rowvec(lse_t_row, rows, "distill_grad.lse_t_row")),
+                                        _p(_rowvec(lse_t_col, cols, "distill_grad.lse_t_col")), _stream()), "cxrk_distill_grad_inplace")
+    return S
+
+
 def clamp_inplace(x, lo: float, hi: float):
     """x <- min(max(x, lo), hi) in place on a dense tensor; a NaN stays a NaN."""
     lib = _lib.load()
