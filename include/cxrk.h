@@ -528,6 +528,24 @@ int cxrk_scale_mask(const float* x, const float* mask_src, const float* alpha_de
  *               Non-finite: as the torch expression g + strength * F * (p - anchor).  A NaN or Inf in element i of g, p, anchor or F
  *               reaches g[i] (0 * Inf = NaN included) and the partial sum of the block that holds i; it reaches no other element
  *               of g and no other partial.
+ *
+ * A-GEM gradient projection (Chaudhry et al. 2019) over the same flat buffers: g is the step's gradient, gref the gradient of a batch
+ * drawn from an episodic memory.  Both calls follow grad_sqnorm's conventions as the three above do (float4 accesses, 16-byte alignment
+ * or CXRK_ERR_ARG, a scalar n % 4 tail in block 0, no atomics, n > 0, nothing written when a call is refused).
+ * agem_dots:    one pass over both buffers (8 B read per parameter): partials[b] = block b's share of sum g[i] * gref[i] and
+ *               partials[nparts + b] = its share of sum gref[i] * gref[i], nparts = cxrk_grad_sqnorm_partials_bytes(n) / 4.  The
+ *               partition is grad_sqnorm's, a function of n alone; each term enters its accumulator by one fma, each block's sums in
+ *               a fixed order: the same buffers give the same bits in every run and on every data-parallel rank.
+ *               cxrk_agem_dots_partials_bytes(n) = 2 * cxrk_grad_sqnorm_partials_bytes(n); partials == NULL or ws_bytes below it gives
+ *               CXRK_ERR_WS with nothing written; no 256-byte alignment is asked of it.  g and gref are read only.
+ * agem_project: every block re-derives dot and rr from the partials of agem_dots(g, gref, n) in adamw_clipped's fixed order (thread
+ *               t takes partials t, t + 256, ..., then the block sum).  Iff !(dot >= 0): coef = dot / rr and
+ *               g[i] = fma(-coef, gref[i], g[i]).  With dot >= 0 (dot == 0 with an all-zero gref included) every block returns
+ *               before it touches g or gref: g stays bit for bit.  stats (4 floats, written by one thread with ordinary stores):
+ *               stats[0] = dot, stats[1] = rr, stats[2] = coef (0 when not projected), stats[3] += 1 when projected (a running count
+ *               the caller zeroes once).  gref and the partials are read only.
+ *               Non-finite: a NaN anywhere in g or gref makes its block's partial NaN, hence dot NaN, the projection taken with
+ *               coef = NaN and every element of g NaN; a bad reference gradient never silently disables the projection.
  */
 int cxrk_adam_fused(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, int step, float grad_scale, hipStream_t stream);
@@ -543,6 +561,9 @@ int cxrk_ewc_consolidate(float* F, const float* acc, float* anchor, const float*
 size_t cxrk_ewc_penalty_partials_bytes(long n);
 int cxrk_ewc_penalty(float* g, const float* p, const float* anchor, const float* F, long n, float strength, float* partials,
                      size_t ws_bytes, hipStream_t stream);
+size_t cxrk_agem_dots_partials_bytes(long n);
+int cxrk_agem_dots(const float* g, const float* gref, long n, float* partials, size_t ws_bytes, hipStream_t stream);
+int cxrk_agem_project(float* g, const float* gref, long n, const float* partials, float* stats, hipStream_t stream);
 size_t cxrk_weight_reset_ws_bytes(void);
 int cxrk_weight_reset(float* pnew, const float* pold, long n, float threshold, unsigned long long* counters, float* ws,
                       size_t ws_bytes, hipStream_t stream);

@@ -46,6 +46,10 @@ Two extensions behind the same entry points (both off unless asked for):
     frozen teacher: `snapshot_teacher()` after a task freezes the current encoders, later steps add beta * L_d, the
     KL divergence of the teacher's image-text similarity distributions over the batch from the student's; `train` logs
     `train/distill` once per epoch while a teacher exists, `save` / `load` carry the teacher as `teacher.pt`.
+    `"agem_memory": M` (optionally `"agem_batch"`, `"agem_every"`, `"agem_seed"`) adds A-GEM: `remember(loader)` after
+    a task keeps M of its rows per rank in an episodic memory; later steps take a reference gradient on rows drawn from it and project
+    the step's gradient when the two conflict; `train` logs `train/agem_projected` (the fraction of the epoch's steps projected) and
+    `train/agem_dot` once per epoch while active, `save` / `load` carry the memory and the sampler's step counter as `agem.pt`.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -140,6 +144,8 @@ class Trainer:
         `torch.distributed` is initialised)."""
         self._ewc_batches = self._check_ewc_keys(joint_encoders)
         self._check_distill_keys(joint_encoders)
+        self._check_agem_keys(joint_encoders)
+        self._agem_logged = (0, 0)         # (projected, applied) of `optim.AGEM` at the last epoch log
         self.pos_mean_counter = 0
         self.neg_mean_counter = 0
         self.n_reset = 0
@@ -187,7 +193,8 @@ class Trainer:
                                                   optim=je["optim"] if je.get("optim") is not None else OPTIM,
                                                   **{k: je[k] for k in ("weight_decay", "max_grad_norm", "warmup_steps", "total_steps",
                                                                         "lr_decay", "min_lr_ratio", "ewc_lambda", "ewc_gamma", "ewc_fisher",
-                                                                        "distill_weight", "distill_temperature")
+                                                                        "distill_weight", "distill_temperature", "agem_memory", "agem_batch",
+                                                                        "agem_every", "agem_seed")
                                                      if je.get(k) is not None},
                                                   positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
                                                   **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
@@ -287,6 +294,23 @@ class Trainer:
             raise ValueError(f"joint_encoders: {given} are options of 'distill_weight' and were given without it")
         from .contrastive import check_distill_options
         check_distill_options(joint_encoders.get("distill_weight"), joint_encoders.get("distill_temperature"))
+
+    AGEM_KEYS = ("agem_memory", "agem_batch", "agem_every", "agem_seed")
+
+    @staticmethod
+    def _check_agem_keys(joint_encoders) -> None:
+        """the "agem_*" entries of `joint_encoders`, checked before anything is built.  They configure the joint trainer: without an
+        "image_model" there is none, and they are refused."""
+        if not isinstance(joint_encoders, dict):
+            return
+        given = [k for k in Trainer.AGEM_KEYS if joint_encoders.get(k) is not None]
+        if given and joint_encoders.get("image_model") is None:
+            raise ValueError(f"joint_encoders: {given} configure A-GEM's episodic memory of the joint-encoder step and need joint mode "
+                             f"(an 'image_model'); the adapter schedules have no such memory")
+        if given and joint_encoders.get("agem_memory") is None:
+            raise ValueError(f"joint_encoders: {given} are options of 'agem_memory' and were given without it")
+        from .contrastive import check_agem_options
+        check_agem_options(*(joint_encoders.get(k) for k in Trainer.AGEM_KEYS))
 
     # ------------------------------------------------------------------------------------------------ data
     @staticmethod
@@ -789,6 +813,13 @@ class Trainer:
         distill = self._joint.current_distill()     # None without a teacher and before the first distilled step
         if distill is not None:
             self.writer.add_scalar('train/distill', distill, epoch)
+        agem = self._joint.current_interference()   # None without "agem_memory" and before the first step with a reference
+        if agem is not None:
+            proj, applied = agem["projected"] - self._agem_logged[0], agem["applied"] - self._agem_logged[1]
+            self._agem_logged = (agem["projected"], agem["applied"])
+            if applied > 0:                         # the fraction of this epoch's steps whose gradient was projected
+                self.writer.add_scalar('train/agem_projected', proj / applied, epoch)
+                self.writer.add_scalar('train/agem_dot', agem["dot"], epoch)
 
     @staticmethod
     def _parse_retrieval(opt):
@@ -905,24 +936,33 @@ class Trainer:
         if self._joint is None or self._joint.ewc is None:
             raise ValueError("Trainer.consolidate needs joint_encoders={..., 'ewc_lambda': strength}")
         self._set_mode(False)
+        return self._joint.consolidate(self._joint_shards(loader, "consolidate"), max_batches=self._ewc_batches)
+
+    def _joint_shards(self, loader, what):
+        """this rank's shard of every batch of `loader`, on the device, cut as `_joint_step` cuts it (with its keys when the trainer
+        has positives)"""
         positives, dev = self._joint.positives, self.device
+        for batch in loader:
+            if len(batch) < 3 or (positives == "labels" and len(batch) < 4):
+                raise ValueError(f"Trainer.{what} expects the batches of joint-encoder training: (images, input_ids, "
+                                 f"attention_mask[, labels]); got a batch of {len(batch)} tensors")
+            images, ids, mask = batch[0], batch[1], batch[2]
+            n = images.shape[0]
+            if self.world > 1 and n % self.world:
+                raise ValueError(f"joint-encoder training shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
+            lo, hi = self._shard(n) if self.world > 1 else (0, n)
+            out = (images[lo:hi].to(dev, non_blocking=True), ids[lo:hi].to(dev, non_blocking=True), mask[lo:hi].to(dev, non_blocking=True))
+            if positives is not None:   # the keys, hashed where the loader left the tensors
+                out += (self._joint.pair_keys(ids[lo:hi], mask[lo:hi], batch[3][lo:hi] if positives == "labels" else None),)
+            yield out
 
-        def shards():
-            for batch in loader:
-                if len(batch) < 3 or (positives == "labels" and len(batch) < 4):
-                    raise ValueError("Trainer.consolidate expects the batches of joint-encoder training: (images, input_ids, "
-                                     f"attention_mask[, labels]); got a batch of {len(batch)} tensors")
-                images, ids, mask = batch[0], batch[1], batch[2]
-                n = images.shape[0]
-                if self.world > 1 and n % self.world:
-                    raise ValueError(f"joint-encoder training shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
-                lo, hi = self._shard(n) if self.world > 1 else (0, n)
-                out = (images[lo:hi].to(dev, non_blocking=True), ids[lo:hi].to(dev, non_blocking=True), mask[lo:hi].to(dev, non_blocking=True))
-                if positives is not None:   # the keys, hashed where the loader left the tensors
-                    out += (self._joint.pair_keys(ids[lo:hi], mask[lo:hi], batch[3][lo:hi] if positives == "labels" else None),)
-                yield out
-
-        return self._joint.consolidate(shards(), max_batches=self._ewc_batches)
+    def remember(self, loader) -> int:
+        """End of a task with `joint_encoders={..., "agem_memory": M}`: each batch of `loader` sharded as in
+        `_joint_step` -> `JointContrastiveTrainer.remember`, which keeps M of this rank's rows; returns the rows stored.  Every rank
+        calls it, as it calls the training loop."""
+        if self._joint is None or self._joint.memory is None:
+            raise ValueError("Trainer.remember needs joint_encoders={..., 'agem_memory': rows}")
+        return self._joint.remember(self._joint_shards(loader, "remember"))
 
     def snapshot_teacher(self) -> None:
         """End of a task with `joint_encoders={..., "distill_weight": beta}`: freeze the current encoders as the
@@ -1020,8 +1060,14 @@ class Trainer:
                 torch.save(self._joint.ewc.state_dict(), os.path.join(self.writer.log_dir, 'ewc.pt'))
             if self._joint.teacher is not None:
                 torch.save(self._joint.teacher.state_dict(), os.path.join(self.writer.log_dir, 'teacher.pt'))
+        if self._joint is not None and self._joint.memory is not None:   # every rank holds rows of its own shards
+            torch.save({"memory": self._joint.memory.state_dict(), "agem": self._joint.agem.state_dict(),
+                        "steps": int(self._joint.agem_steps)}, os.path.join(self.writer.log_dir, self._agem_file()))
         if hasattr(self.writer, "flush"):
             self.writer.flush()
+
+    def _agem_file(self) -> str:
+        return 'agem.pt' if self.rank == 0 else f'agem.rank{self.rank}.pt'
 
     @torch.no_grad()
     def load(self):
@@ -1063,4 +1109,13 @@ class Trainer:
                 # just loaded, then take the saved tensors; size and keys are checked by `FrozenTeacher.load_state_dict`
                 self._joint.snapshot_teacher()
                 self._joint.teacher.load_state_dict(torch.load(tpath, map_location="cpu", weights_only=True))
+            if self._joint.memory is not None:   # the memory, the projection's counters and the sampler's step counter
+                path = os.path.join(self.writer.log_dir, self._agem_file())
+                sd = torch.load(path, map_location="cpu", weights_only=True)
+                if not isinstance(sd, dict) or set(sd) != {"memory", "agem", "steps"} or int(sd["steps"]) < 0:
+                    raise ValueError(f"{path}: expected the keys ['agem', 'memory', 'steps'] with steps >= 0")
+                self._joint.memory.load_state_dict(sd["memory"], device=self.device)
+                self._joint.agem.load_state_dict(sd["agem"])
+                self._joint.agem_steps = int(sd["steps"])
+                self._agem_logged = (int(sd["agem"]["stats"][3]), int(sd["agem"]["applied"]))
             self._bert_cache.clear()

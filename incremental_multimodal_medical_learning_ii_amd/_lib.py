@@ -114,6 +114,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_ewc_consolidate": (I, [P, P, P, P, L, F, F, P]),
     "cxrk_ewc_penalty_partials_bytes": (Z, [L]),
     "cxrk_ewc_penalty": (I, [P, P, P, P, L, F, P, Z, P]),
+    "cxrk_agem_dots_partials_bytes": (Z, [L]),
+    "cxrk_agem_dots": (I, [P, P, L, P, Z, P]),
+    "cxrk_agem_project": (I, [P, P, L, P, P, P]),
     "cxrk_weight_reset_ws_bytes": (Z, []),
     "cxrk_weight_reset": (I, [P, P, L, F, P, P, Z, P]),
     "cxrk_gemm_wgrad_splitk": (I, [I, I, I, I]),

@@ -327,6 +327,19 @@ class FrozenTeacher:
             t.copy_(v)
 
 
+def check_agem_options(memory, batch, every, seed) -> tuple:
+    """(agem_memory, agem_batch, agem_every, agem_seed) checked, the defaults of `every` (1) and `seed` (0) filled in; options given
+    without `agem_memory` are refused"""
+    if memory is None:
+        if batch is not None or every is not None or seed is not None:
+            raise ValueError("agem_batch / agem_every / agem_seed are options of A-GEM; they were given without agem_memory")
+        return None, None, None, None
+    for name, v, lo in (("agem_memory", memory, 1), ("agem_batch", batch, 1), ("agem_every", every, 1), ("agem_seed", seed, 0)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < lo):
+            raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
+    return memory, batch, 1 if every is None else every, 0 if seed is None else seed
+
+
 class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
@@ -337,7 +350,8 @@ class JointContrastiveTrainer:
                  warmup_steps: Optional[int] = None, total_steps: Optional[int] = None, lr_decay: Optional[str] = None,
                  min_lr_ratio: Optional[float] = None, ewc_lambda: Optional[float] = None, ewc_gamma: Optional[float] = None,
                  ewc_fisher: Optional[str] = None, distill_weight: Optional[float] = None,
-                 distill_temperature: Optional[float] = None):
+                 distill_temperature: Optional[float] = None, agem_memory: Optional[int] = None,
+                 agem_batch: Optional[int] = None, agem_every: Optional[int] = None, agem_seed: Optional[int] = None):
         """`optim="adamw"`: `optim.AdamW` with decoupled `weight_decay` (default 0.01; parameters with ndim <= 1 do
         not decay) and, with `max_grad_norm`, clipping of the global gradient norm (`inf`: the norm is taken and reported, nothing
         is clipped).  `warmup_steps` / `total_steps` / `lr_decay` ("constant" | "linear" | "cosine") / `min_lr_ratio`: an
@@ -348,7 +362,14 @@ class JointContrastiveTrainer:
         optimiser's step, so clipping and the update see it exactly as if the penalty were part of the loss.
         `distill_weight` = beta: similarity distillation from a frozen teacher; `distill_temperature` = tau_d
         (default: `temperature`).  Until the first `snapshot_teacher()` a step is bit for bit the step without it; afterwards the
-        step's objective is contrastive + beta * L_d, with L_d of `functional.distill_loss` against the snapshot's encoders."""
+        step's objective is contrastive + beta * L_d, with L_d of `functional.distill_loss` against the snapshot's encoders.
+        `agem_memory` = M: A-GEM.  `remember(batches)` keeps M rows of a finished task per rank in an
+        `memory.EpisodicMemory` (seeded by `agem_seed`, default 0); once it holds rows, every `agem_every`-th step (default 1) first
+        takes the gradient of `agem_batch` memory rows (default: as many as the step's shard has, at most all stored) as the
+        reference, and every step projects its gradient against the stored reference (`optim.AGEM`).  Until the first `remember()`
+        a step is bit for bit the step without it."""
+        self.agem_memory, self.agem_batch, self.agem_every, self.agem_seed = check_agem_options(agem_memory, agem_batch, agem_every,
+                                                                                                agem_seed)
         self.micro_batch = check_micro_batch(micro_batch)
         self.distill_weight, self.distill_temperature = check_distill_options(distill_weight, distill_temperature)
         self.teacher: Optional[FrozenTeacher] = None
@@ -440,6 +461,11 @@ class JointContrastiveTrainer:
         if ewc_lambda is not None:
             self.ewc = cxr_optim.EWC(self.optimizer, ewc_lambda, fisher="empirical" if ewc_fisher is None else ewc_fisher,
                                      gamma=1.0 if ewc_gamma is None else ewc_gamma)
+        self.agem, self.memory, self.agem_steps = None, None, 0
+        if self.agem_memory is not None:
+            from .memory import EpisodicMemory
+            self.agem = cxr_optim.AGEM(self.optimizer)
+            self.memory = EpisodicMemory(self.agem_memory, seed=self.agem_seed)
         self.world, self.rank = 1, 0
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
@@ -728,7 +754,11 @@ class JointContrastiveTrainer:
 
         With `micro_batch` < this rank's rows the forward and backward run chunk by chunk (`_chunked_forward_backward`); the hook
         is then handed only to the encoder calls of the step's LAST backward, after which every range is complete."""
+        if self.agem is not None and len(self.memory) > 0:
+            self._agem_reference(int(images.shape[0]))
         loss = self._gradient(images, input_ids, attention_mask, labels, keys)
+        if self.agem is not None:        # no launch before the first reference; the penalty below is not projected: it already
+            self.agem.apply()            # speaks for the old tasks
         if self.ewc is not None:         # no launch before the first consolidation
             self.ewc.apply()
         if self.schedule is not None:    # a host float that the update kernel takes as an argument: no launch, no sync
@@ -737,6 +767,55 @@ class JointContrastiveTrainer:
         if self.logit_scale is not None:
             K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)
         return loss.detach()
+
+    # ------------------------------------------------------------------ episodic memory and A-GEM
+    def _agem_reference(self, rows: int) -> None:
+        """The reference pass of a step: the gradient of a batch drawn from the memory, by `_gradient` (the same `micro_batch`
+        chunks, the same overlapped all-reduce), kept by `optim.AGEM.store_reference()`.  Every `agem_every`-th step; in between
+        the stored reference is reused.  It never augments and does not distil, as `consolidate`; no optimiser state moves.  The
+        draw is keyed by (agem_seed, the count of such steps), identical on every rank."""
+        k = self.agem_steps
+        self.agem_steps = k + 1
+        if self.agem.valid and k % self.agem_every != 0:
+            return
+        n = min(rows if self.agem_batch is None else self.agem_batch, len(self.memory))
+        batch = self.memory.sample(n, step=k)
+        extra = batch[3] if len(batch) > 3 else None
+        augment, self._augment = self._augment, None
+        self._distill_off = True
+        try:
+            self._gradient(batch[0], batch[1], batch[2], extra if extra is not None and extra.dim() > 1 else None,
+                           extra if extra is not None and extra.dim() == 1 else None)
+        finally:
+            self._augment = augment
+            self._distill_off = False
+        self.agem.store_reference()
+
+    def remember(self, batches) -> int:
+        """End of a task (needs `agem_memory`): reservoir-sample `agem_memory` rows of the task's batches `(images, input_ids,
+        attention_mask[, labels | keys])` -- this rank's shards, as for `step` -- into the episodic memory -> the rows stored.
+        Under data parallelism every rank calls it with its own shards; one MAX all-reduce over (count, -count) then checks that
+        all ranks hold the same number of rows (the sampler's indices are then the same everywhere), and raises if they do not."""
+        if self.memory is None:
+            raise ValueError("JointContrastiveTrainer.remember: this trainer was constructed without agem_memory")
+        kept = self.memory.add_task(batches)
+        if self.world > 1:
+            import torch.distributed as dist
+            dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
+            total = len(self.memory)
+            t = torch.tensor([total, -total], dtype=torch.int64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+            hi, lo = int(t[0]), -int(t[1])
+            if hi != lo:
+                raise RuntimeError(f"JointContrastiveTrainer.remember: the ranks hold between {lo} and {hi} memory rows (this one "
+                                   f"{total}); every rank must be given the same number of rows per task")
+        self.agem.valid = False              # the stored reference predates these rows
+        return kept
+
+    def current_interference(self) -> Optional[dict]:
+        """`optim.AGEM.current_interference()` of the last projected-or-not step (None without `agem_memory` or before the first
+        such step): a host sync, and only when called"""
+        return None if self.agem is None else self.agem.current_interference()
 
     def consolidate(self, batches, max_batches: Optional[int] = None) -> int:
         """End of a task (needs `ewc_lambda`): estimate the Fisher diagonal and anchor the parameters -> the number of batches used.

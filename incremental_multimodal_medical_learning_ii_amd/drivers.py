@@ -8,6 +8,7 @@ and `DATA_INCREMENTAL.py:74-97` (hyper-parameters as arguments instead of litera
     python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --parts 5 --joint --batch-size 1024 --epochs 1
     python -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --joint --cl ewc --ewc-lambda 1e4 --ewc-batches 8
     python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --joint --cl lwf --distill-weight 1.0
+    python -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --joint --cl agem --agem-memory 256
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29511 \
         -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --mode class-pos-neg --batch-size 2048
 
@@ -130,6 +131,7 @@ def _setup(args, kind):
                                              **optimiser_from_args(args, kind, train_loader),
                                              **ewc_from_args(args),
                                              **distill_from_args(args),
+                                             **agem_from_args(args),
                                              "augment": augment_from_args(args),
                                              "retrieval": retrieval_from_args(args)})
     else:
@@ -195,6 +197,21 @@ def distill_from_args(args) -> dict:
     out = {"distill_weight": DISTILL_WEIGHT if args.distill_weight is None else args.distill_weight}
     if getattr(args, "distill_temperature", None) is not None:
         out["distill_temperature"] = args.distill_temperature
+    return out
+
+
+AGEM_MEMORY = 256     # rows kept per task and rank by --cl agem
+
+
+def agem_from_args(args) -> dict:
+    """`--cl agem` / `--agem-memory` / `--agem-batch` / `--agem-every` -> the `joint_encoders` keys they set (without `--cl agem`: an
+    empty dict)"""
+    if getattr(args, "cl", None) != "agem":
+        return {}
+    out = {"agem_memory": AGEM_MEMORY if args.agem_memory is None else args.agem_memory}
+    for flag in ("agem_batch", "agem_every"):
+        if getattr(args, flag, None) is not None:
+            out[flag] = getattr(args, flag)
     return out
 
 
@@ -265,6 +282,8 @@ def class_incremental(args):
                 trainer.consolidate(train_loader[actual_task - 1])
             if args.cl == "lwf" and actual_task < len(tasks_order):      # this task's encoders teach the next one
                 trainer.snapshot_teacher()
+            if args.cl == "agem" and actual_task < len(tasks_order):     # rows of this task constrain the next one's updates
+                trainer.remember(train_loader[actual_task - 1])
             trainer.val(val_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
             metrics = trainer.test(test_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
     finally:
@@ -294,6 +313,8 @@ def data_incremental(args):
                 trainer.consolidate(train_loader[part - 1])
             if args.cl == "lwf" and part < args.parts:
                 trainer.snapshot_teacher()
+            if args.cl == "agem" and part < args.parts:
+                trainer.remember(train_loader[part - 1])
             train_loader[part - 1] = None
             trainer.val(val_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
             metrics = trainer.test(test_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
@@ -313,10 +334,10 @@ def make_parser():
     ap.add_argument("--more-labels", action="store_true")
     ap.add_argument("--single-prompt", action="store_true")
     ap.add_argument("--xrays-position", default="all")
-    ap.add_argument("--cl", default=None, choices=[None, "myCL", "profCL", "ewc", "lwf"],
+    ap.add_argument("--cl", default=None, choices=[None, "myCL", "profCL", "ewc", "lwf", "agem"],
                     help="continual learning: the reference's weight-reset heuristics (myCL, profCL) or, with --joint, elastic weight "
-                         "consolidation (ewc, DESIGN.md 5.10) or similarity distillation from the previous task's encoders (lwf, "
-                         "DESIGN.md 5.11)")
+                         "consolidation (ewc, DESIGN.md 5.10), similarity distillation from the previous task's encoders (lwf, "
+                         "DESIGN.md 5.11) or A-GEM's gradient projection against an episodic memory (agem, DESIGN.md 5.12)")
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--adder", type=float, default=0.001)
     ap.add_argument("--threshold-scheduling", action="store_true")
@@ -382,12 +403,19 @@ def make_parser():
                          "only measures the drift)")
     ap.add_argument("--distill-temperature", type=float, default=None, metavar="TAU",
                     help="--cl lwf: the fixed temperature of the distilled similarity distributions (default: --temperature)")
+    ap.add_argument("--agem-memory", type=int, default=None, metavar="M",
+                    help="--cl agem: rows of every finished task kept in the episodic memory, per rank (default 256)")
+    ap.add_argument("--agem-batch", type=int, default=None, metavar="N",
+                    help="--cl agem: memory rows of the reference gradient, per rank (default: as many as the step's shard, at most "
+                         "all that are stored)")
+    ap.add_argument("--agem-every", type=int, default=None, metavar="K",
+                    help="--cl agem: recompute the reference gradient every K-th step and reuse it in between (default 1)")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
 
 def parse_args(argv=None):
-    """`make_parser().parse_args` plus the refusals that concern `--cl ewc` (parser errors: exit status 2)"""
+    """`make_parser().parse_args` plus the refusals that concern `--cl ewc`, `--cl lwf` and `--cl agem` (parser errors: exit status 2)"""
     ap = make_parser()
     args = ap.parse_args(argv)
     given = [f for f in ("ewc_lambda", "ewc_batches", "ewc_gamma", "ewc_fisher") if getattr(args, f) is not None]
@@ -418,6 +446,18 @@ def parse_args(argv=None):
             ap.error(f"--distill-weight must be finite and >= 0, got {args.distill_weight}")
         if args.distill_temperature is not None and not (args.distill_temperature > 0 and args.distill_temperature != float("inf")):
             ap.error(f"--distill-temperature must be positive and finite, got {args.distill_temperature}")
+    given = [f for f in ("agem_memory", "agem_batch", "agem_every") if getattr(args, f) is not None]
+    if given and args.cl != "agem":
+        ap.error("--" + given[0].replace("_", "-") + " configures A-GEM's episodic memory and needs --cl agem")
+    if args.cl == "agem":
+        if args.which == "zero-joint":
+            ap.error("--cl agem remembers rows between tasks; zero-joint trains a single task (use class-inc or data-inc)")
+        if not args.joint:
+            ap.error("--cl agem projects the gradient of the north-star step and needs --joint (the adapter schedules keep the "
+                     "reference's weight-reset heuristics myCL / profCL)")
+        for f in given:
+            if getattr(args, f) < 1:
+                ap.error(f"--{f.replace('_', '-')} must be >= 1, got {getattr(args, f)}")
     return args
 
 

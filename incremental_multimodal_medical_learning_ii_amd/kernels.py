@@ -1651,6 +1651,49 @@ def ewc_penalty(g: torch.Tensor, p: torch.Tensor, anchor: torch.Tensor, F: Optio
     return ws[:nbytes // 4]
 
 
+def agem_dots_nparts(n: int) -> int:
+    """number of blocks of `agem_dots` for n elements, `grad_sqnorm_nparts(n)`: it writes 2 * nparts floats (include/cxrk.h,
+    "agem_dots")"""
+    return _lib.load().cxrk_agem_dots_partials_bytes(int(n)) // 8
+
+
+def agem_dots(g: torch.Tensor, gref: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-block partial sums of g * gref -> [:nparts] and of gref * gref -> [nparts:] of a [2 * nparts] buffer (in `out`, else in the
+    stream's workspace: valid until the next wrapper call on this stream, which is `agem_project`).  Bit-reproducible; neither
+    buffer is modified."""
+    lib = _lib.load()
+    n = _flat(g, "agem_dots.g").numel()
+    _flat(gref, "agem_dots.gref", n)
+    nbytes = lib.cxrk_agem_dots_partials_bytes(n)
+    if out is None:
+        ws = workspace(nbytes, g.device)
+        ws_bytes = ws.numel() * 4
+    else:
+        ws = _chk(out, "agem_dots.out")
+        if not out.is_contiguous():
+            raise ValueError("agem_dots.out: must be contiguous")
+        ws_bytes = out.numel() * 4
+    check(lib.cxrk_agem_dots(_p(g), _p(gref), n, _p(ws), ws_bytes, _stream()), "cxrk_agem_dots")
+    return ws[:nbytes // 4]
+
+
+def agem_project(g: torch.Tensor, gref: torch.Tensor, partials: torch.Tensor, stats: torch.Tensor) -> None:
+    """A-GEM's projection in place (include/cxrk.h, "agem_project"): with dot and rr re-derived from `partials` = what
+    `agem_dots(g, gref)` returned, g -= (dot / rr) * gref iff !(dot >= 0); otherwise g is not touched.  `stats`: 4 floats <-
+    (dot, rr, coef, running count of projected calls, incremented on the device).  gref is not modified."""
+    lib = _lib.load()
+    n = _flat(g, "agem_project.g").numel()
+    _flat(gref, "agem_project.gref", n)
+    _chk(partials, "agem_project.partials")
+    if not partials.is_contiguous() or partials.numel() * 4 != lib.cxrk_agem_dots_partials_bytes(n):
+        raise ValueError(f"agem_project.partials: must be the {lib.cxrk_agem_dots_partials_bytes(n) // 4} contiguous floats of "
+                         f"agem_dots for {n} elements")
+    _chk(stats, "agem_project.stats")
+    if not stats.is_contiguous() or stats.numel() != 4:
+        raise ValueError("agem_project.stats: must be 4 contiguous floats")
+    check(lib.cxrk_agem_project(_p(g), _p(gref), n, _p(partials), _p(stats), _stream()), "cxrk_agem_project")
+
+
 def sgd(p, g, lr, weight_decay: float = 0.0, grad_scale: float = 1.0):
     lib = _lib.load()
     check(lib.cxrk_sgd(_p(_chk(p, "sgd.p")), _p(_chk(g, "sgd.g")), p.numel(), float(lr), float(weight_decay),

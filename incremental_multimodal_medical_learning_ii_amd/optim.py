@@ -8,7 +8,8 @@ memory before (the fused q/k/v projections) stay adjacent; the physical layout o
 conv filters) is preserved.
 
 `AdamW` (decoupled weight decay with a no-decay set, global-norm clipping) and `LRSchedule` (warmup / decay) are opt-in additions
-that the reference does not have; so is `EWC`, elastic weight consolidation over the same flat buffers (§5.10).
+that the reference does not have; so is `EWC`, elastic weight consolidation over the same flat buffers (§5.10).  So is
+`AGEM`, A-GEM's projection of the step's gradient against an episodic-memory gradient (§5.12).
 """
 from __future__ import annotations
 
@@ -410,3 +411,77 @@ class EWC:
         self.F = sd["F"].to(dev).clone() if "F" in need else None
         self.gamma, self.tasks, self.active = gamma, tasks, tasks > 0
         self._acc, self.samples, self._applied = None, 0, False
+
+
+class AGEM:
+    """A-GEM's gradient projection (Chaudhry et al. 2019) over the flat gradient buffer of any `_FlatOptimizer`.
+    `store_reference()` keeps a copy of `optimizer.flat_g` as the reference gradient g_ref (the gradient of a batch drawn from an
+    episodic memory; call it after `all_reduce_grads` under data parallelism); `apply()` then replaces the step's gradient g, when it
+    conflicts with the reference (g . g_ref < 0), by g - (g . g_ref / g_ref . g_ref) g_ref, before the optimiser's step (and its
+    clipping norm) reads it.
+
+    Memory: +4 B per parameter for g_ref, allocated at the first `store_reference()`.  `apply()` is two launches (`agem_dots`, then
+    `agem_project`, which decides on the device: no host sync), none before a reference exists.  `current_interference()` is the one
+    read-back and happens only when asked."""
+
+    def __init__(self, optimizer: _FlatOptimizer):
+        self.optimizer = optimizer
+        self.gref: Optional[torch.Tensor] = None
+        self._partials: Optional[torch.Tensor] = None
+        self._stats = torch.zeros(4, dtype=torch.float32, device=optimizer.flat_p.device)
+        self.valid, self.applied = False, 0
+
+    @torch.no_grad()
+    def store_reference(self) -> None:
+        """g_ref = `optimizer.flat_g` (one device copy); marks the reference valid"""
+        opt = self.optimizer
+        opt._sync_grads()
+        if self.gref is None:
+            self.gref = torch.empty_like(opt.flat_g)
+        self.gref.copy_(opt.flat_g)
+        self.valid = True
+
+    @torch.no_grad()
+    def apply(self) -> None:
+        """project `optimizer.flat_g` in place; no reference yet: returns without a launch"""
+        if not self.valid:
+            return
+        opt = self.optimizer
+        opt._sync_grads()
+        if self._partials is None:
+            self._partials = torch.empty(2 * K.agem_dots_nparts(opt.numel), dtype=torch.float32, device=opt.flat_p.device)
+        K.agem_dots(opt.flat_g, self.gref, out=self._partials)
+        K.agem_project(opt.flat_g, self.gref, self._partials, self._stats)
+        self.applied += 1
+
+    def current_interference(self) -> Optional[dict]:
+        """the last `apply()` as host numbers: "dot" (g . g_ref), "ref_sqnorm", "coef" (0 when not projected), and the running counts
+        "projected" / "applied" of calls (None before the first `apply()`): the one read-back, only when asked"""
+        if self.applied == 0:
+            return None
+        s = self._stats.detach().cpu().tolist()
+        return {"dot": s[0], "ref_sqnorm": s[1], "coef": s[2], "projected": int(s[3]), "applied": int(self.applied)}
+
+    def state_dict(self) -> dict:
+        """tensors and plain numbers only (loadable with weights_only=True).  The reference gradient is not saved: it is recomputed
+        from the memory."""
+        return {"numel": int(self.optimizer.numel), "applied": int(self.applied), "stats": self._stats.detach().cpu()}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """strict: exactly the keys of `state_dict()`, written for a flat buffer of `optimizer.numel` elements"""
+        if not isinstance(sd, dict):
+            raise ValueError(f"AGEM.load_state_dict: expected a dict, got {type(sd).__name__}")
+        want = {"numel", "applied", "stats"}
+        if set(sd) != want:
+            raise ValueError(f"AGEM.load_state_dict: keys {sorted(sd)} (expected {sorted(want)})")
+        if int(sd["numel"]) != self.optimizer.numel:
+            raise ValueError(f"AGEM.load_state_dict: the state belongs to a flat buffer of {int(sd['numel'])} elements, this one has "
+                             f"{self.optimizer.numel}")
+        st = sd["stats"]
+        if not isinstance(st, torch.Tensor) or st.dtype != torch.float32 or tuple(st.shape) != (4,):
+            raise ValueError("AGEM.load_state_dict: 'stats' must be a float32 tensor of 4 elements")
+        if int(sd["applied"]) < 0:
+            raise ValueError(f"AGEM.load_state_dict: 'applied' must be >= 0, got {sd['applied']!r}")
+        self._stats.copy_(st)
+        self.applied, self.valid = int(sd["applied"]), False
