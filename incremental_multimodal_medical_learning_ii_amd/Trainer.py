@@ -58,6 +58,7 @@ Two extensions behind the same entry points (both off unless asked for):
 from __future__ import annotations
 
 import copy
+import inspect
 import math
 import os
 from typing import Dict, List, Optional, Sequence
@@ -70,6 +71,8 @@ from torch.utils.data import ConcatDataset, DataLoader, RandomSampler, Subset, T
 from . import functional as Fh
 from . import kernels as K
 from . import optim as cxr_optim
+from .contrastive import (RETRIEVAL_KS, JointContrastiveTrainer, check_agem_options, check_distill_options, check_ks,
+                          retrieval_metrics)
 from .DataRetrieval import CHEXPERT_COMPETITION_CLASSES, basic_create_prompts, create_prompts
 from .health_multimodal.text import get_cxr_bert_inference
 from .models import myLinearModel, myMLP
@@ -133,6 +136,53 @@ def change_values(tensor):
     return new_tensor.float().to(tensor.device)
 
 
+# `joint_encoders` -> the keywords of `JointContrastiveTrainer.__init__`, whose signature declares (and whose body validates) the
+# step's options.  A key is the keyword of the same name, except:
+JOINT_RENAMED = {"contrastive_loss": "loss"}                      # key -> keyword, where the two differ
+JOINT_OWN_KEYS = ("image_model", "retrieval", "ewc_batches")      # read by `Trainer` itself
+# (master key, member keys, what the group configures, what the adapter schedules lack): a member needs its master, all need joint mode
+JOINT_GROUPS = (("ewc_lambda", ("ewc_gamma", "ewc_fisher", "ewc_batches"), "elastic weight consolidation", "such penalty"),
+                ("distill_weight", ("distill_temperature",), "similarity distillation", "teacher"),
+                ("agem_memory", ("agem_batch", "agem_every", "agem_seed"), "A-GEM's episodic memory", "such memory"))
+# the rest of the signature: the models, `lr` and the group are `Trainer`'s own arguments, the last two are not offered here
+_STEP_KEYWORDS = set(inspect.signature(JointContrastiveTrainer.__init__).parameters) - {
+    "self", "image_model", "text_model", "lr", "group", "train_mlm_head", "two_streams"}
+JOINT_STEP_KEYS = {**{k: k for k in _STEP_KEYWORDS - set(JOINT_RENAMED.values())}, **JOINT_RENAMED}     # key -> keyword
+
+
+def joint_options(joint_encoders):
+    """`Trainer`'s `joint_encoders`, checked before anything is built -> (the keywords of `JointContrastiveTrainer` it sets, the values
+    of `JOINT_OWN_KEYS`).  A dict, or the pair (image_model, temperature).  A key that is neither a keyword of the step's constructor
+    nor in the tables above is refused; a key whose value is None counts as not given, as does "augment": False (a seed without a
+    spec is then dropped); `OPTIM` is the optimiser unless "optim" names one.  The groups configure the joint trainer: without an
+    "image_model" there is none, and their keys are refused."""
+    if joint_encoders is None:
+        return {}, dict.fromkeys(JOINT_OWN_KEYS)
+    je = dict(joint_encoders) if isinstance(joint_encoders, dict) else {"image_model": joint_encoders[0], "temperature": joint_encoders[1]}
+    unknown = [k for k in je if k not in JOINT_STEP_KEYS and k not in JOINT_OWN_KEYS]
+    if unknown:
+        raise ValueError(f"joint_encoders: unknown key(s) {unknown}; the valid keys are {sorted([*JOINT_STEP_KEYS, *JOINT_OWN_KEYS])}")
+    for master, members, what, lacks in JOINT_GROUPS:
+        given = [k for k in (master,) + members if je.get(k) is not None]
+        if given and je.get("image_model") is None:
+            raise ValueError(f"joint_encoders: {given} configure {what} of the joint-encoder step and need joint mode "
+                             f"(an 'image_model'); the adapter schedules have no {lacks}")
+        if given and je.get(master) is None:
+            raise ValueError(f"joint_encoders: {given} are options of '{master}' and were given without it")
+    nb = je.get("ewc_batches")
+    if nb is not None and (isinstance(nb, bool) or not isinstance(nb, int) or nb < 1):
+        raise ValueError(f"joint_encoders['ewc_batches'] must be an integer >= 1, got {nb!r}")
+    kw = {JOINT_STEP_KEYS[k]: v for k, v in je.items() if k in JOINT_STEP_KEYS and v is not None}
+    check_distill_options(kw.get("distill_weight"), kw.get("distill_temperature"))
+    check_agem_options(*(kw.get(k) for k in ("agem_memory", "agem_batch", "agem_every", "agem_seed")))
+    kw["temperature"] = float(kw.get("temperature", 0.07))
+    kw.setdefault("optim", OPTIM)
+    if kw.get("augment") in (None, False):
+        kw.pop("augment", None)
+        kw.pop("augment_seed", None)
+    return kw, {k: je[k] if k == "image_model" else je.get(k) for k in JOINT_OWN_KEYS}     # (a dict without a model: KeyError)
+
+
 class Trainer:
     def __init__(self, single_prompt, prompts, class_names, loss_name, lr, device, writer, bert_encoder=None, joint_encoders=None,
                  process_group=None):
@@ -140,11 +190,11 @@ class Trainer:
         `TextInferenceEngine`; default `get_cxr_bert_inference()` as at `Trainer.py:109` (Hub fetch, or the offline
         synthetic model when CXRK_SYNTHETIC_WEIGHTS=1).  `joint_encoders` (optional, see the module docstring): a dict with
         "image_model" (an `ImageModel` on `device`) and optionally "temperature" (default 0.07) — no adapters are created, the
-        trainable parameters are the two encoders.  `process_group`: the data-parallel group (default: the default group when
+        trainable parameters are the two encoders; `joint_options` checks the dict before anything is built and refuses a key it does
+        not know.  `process_group`: the data-parallel group (default: the default group when
         `torch.distributed` is initialised)."""
-        self._ewc_batches = self._check_ewc_keys(joint_encoders)
-        self._check_distill_keys(joint_encoders)
-        self._check_agem_keys(joint_encoders)
+        step_options, own = joint_options(joint_encoders)
+        self._ewc_batches = own["ewc_batches"]      # None: `consolidate` reads every batch of its loader
         self._agem_logged = (0, 0)         # (projected, applied) of `optim.AGEM` at the last epoch log
         self.pos_mean_counter = 0
         self.neg_mean_counter = 0
@@ -183,29 +233,13 @@ class Trainer:
         self._retrieval_ks = None          # joint_encoders={..., "retrieval": True | (k, ...)}: val / test add Retrieval/* metrics
         self._retrieval_result = None
         if joint_encoders is not None:
-            from .contrastive import JointContrastiveTrainer
-            je = dict(joint_encoders) if isinstance(joint_encoders, dict) else {"image_model": joint_encoders[0], "temperature": joint_encoders[1]}
-            self.image_model = je["image_model"]
+            self.image_model = own["image_model"]
             if OPTIM not in ("adam", "sgd"):
                 raise Exception
-            self._joint = JointContrastiveTrainer(self.image_model, self.bert_encoder.model, lr=lr,
-                                                  temperature=float(je.get("temperature", 0.07)), group=process_group,
-                                                  optim=je["optim"] if je.get("optim") is not None else OPTIM,
-                                                  **{k: je[k] for k in ("weight_decay", "max_grad_norm", "warmup_steps", "total_steps",
-                                                                        "lr_decay", "min_lr_ratio", "ewc_lambda", "ewc_gamma", "ewc_fisher",
-                                                                        "distill_weight", "distill_temperature", "agem_memory", "agem_batch",
-                                                                        "agem_every", "agem_seed")
-                                                     if je.get(k) is not None},
-                                                  positives=je.get("positives"), learn_temperature=bool(je.get("learn_temperature", False)),
-                                                  **({"log_scale_bounds": tuple(je["log_scale_bounds"])} if "log_scale_bounds" in je else {}),
-                                                  **({"loss": je["contrastive_loss"]} if "contrastive_loss" in je else {}),
-                                                  **({"sigmoid_bias": je["sigmoid_bias"]} if je.get("sigmoid_bias") is not None else {}),
-                                                  **({"micro_batch": je["micro_batch"]} if je.get("micro_batch") is not None else {}),
-                                                  **({"augment": je["augment"], "augment_seed": je.get("augment_seed")}
-                                                     if je.get("augment") not in (None, False) else {}))
+            self._joint = JointContrastiveTrainer(self.image_model, self.bert_encoder.model, lr=lr, group=process_group, **step_options)
             print("*** JOINT ENCODER TRAINING (%s over the global batch): no adapters ***"
                   % ("pairwise sigmoid loss" if self._joint.loss == "sigmoid" else "InfoNCE"))
-            self._retrieval_ks = self._parse_retrieval(je.get("retrieval"))
+            self._retrieval_ks = self._parse_retrieval(own["retrieval"])
         params = []
         if self._joint is not None:
             self.image_adapter = self.text_adapter = None
@@ -258,59 +292,6 @@ class Trainer:
         self._flat_copy = None
         self._reset_counters = torch.zeros(2, dtype=torch.int64, device=device)
         self._reset_total = 0
-
-    EWC_KEYS = ("ewc_lambda", "ewc_gamma", "ewc_fisher", "ewc_batches")
-
-    @staticmethod
-    def _check_ewc_keys(joint_encoders):
-        """the "ewc_*" entries of `joint_encoders`, checked before anything is built -> "ewc_batches" (None: every batch of the
-        loader).  They configure the joint trainer: without an "image_model" there is none, and they are refused."""
-        if not isinstance(joint_encoders, dict):
-            return None
-        given = [k for k in Trainer.EWC_KEYS if joint_encoders.get(k) is not None]
-        if given and joint_encoders.get("image_model") is None:
-            raise ValueError(f"joint_encoders: {given} configure elastic weight consolidation of the joint-encoder step and need joint "
-                             f"mode (an 'image_model'); the adapter schedules have no such penalty")
-        if given and joint_encoders.get("ewc_lambda") is None:
-            raise ValueError(f"joint_encoders: {given} are options of 'ewc_lambda' and were given without it")
-        nb = joint_encoders.get("ewc_batches")
-        if nb is not None and (isinstance(nb, bool) or not isinstance(nb, int) or nb < 1):
-            raise ValueError(f"joint_encoders['ewc_batches'] must be an integer >= 1, got {nb!r}")
-        return nb
-
-    DISTILL_KEYS = ("distill_weight", "distill_temperature")
-
-    @staticmethod
-    def _check_distill_keys(joint_encoders) -> None:
-        """the "distill_*" entries of `joint_encoders`, checked before anything is built.  They configure the joint trainer: without an
-        "image_model" there is none, and they are refused."""
-        if not isinstance(joint_encoders, dict):
-            return
-        given = [k for k in Trainer.DISTILL_KEYS if joint_encoders.get(k) is not None]
-        if given and joint_encoders.get("image_model") is None:
-            raise ValueError(f"joint_encoders: {given} configure similarity distillation of the joint-encoder step and need joint mode "
-                             f"(an 'image_model'); the adapter schedules have no teacher")
-        if given and joint_encoders.get("distill_weight") is None:
-            raise ValueError(f"joint_encoders: {given} are options of 'distill_weight' and were given without it")
-        from .contrastive import check_distill_options
-        check_distill_options(joint_encoders.get("distill_weight"), joint_encoders.get("distill_temperature"))
-
-    AGEM_KEYS = ("agem_memory", "agem_batch", "agem_every", "agem_seed")
-
-    @staticmethod
-    def _check_agem_keys(joint_encoders) -> None:
-        """the "agem_*" entries of `joint_encoders`, checked before anything is built.  They configure the joint trainer: without an
-        "image_model" there is none, and they are refused."""
-        if not isinstance(joint_encoders, dict):
-            return
-        given = [k for k in Trainer.AGEM_KEYS if joint_encoders.get(k) is not None]
-        if given and joint_encoders.get("image_model") is None:
-            raise ValueError(f"joint_encoders: {given} configure A-GEM's episodic memory of the joint-encoder step and need joint mode "
-                             f"(an 'image_model'); the adapter schedules have no such memory")
-        if given and joint_encoders.get("agem_memory") is None:
-            raise ValueError(f"joint_encoders: {given} are options of 'agem_memory' and were given without it")
-        from .contrastive import check_agem_options
-        check_agem_options(*(joint_encoders.get(k) for k in Trainer.AGEM_KEYS))
 
     # ------------------------------------------------------------------------------------------------ data
     @staticmethod
@@ -696,26 +677,31 @@ class Trainer:
         encoders, InfoNCE over the global batch, backward, gradient all-reduce, fused optimiser step.  With
         `joint_encoders={..., "positives": "labels" | "text"}` the pairs' keys are hashed from the shard's host tensors (the labels
         need not go to the device) and the loss is the multi-positive one."""
-        if len(batch) < 3:
-            raise ValueError("joint-encoder training expects loaders that yield (images, input_ids, attention_mask[, labels]); got a "
-                             f"batch of {len(batch)} tensors")
-        images, ids, mask = batch[0], batch[1], batch[2]
-        positives = self._joint.positives
-        if positives == "labels" and len(batch) < 4:
-            raise ValueError("joint-encoder training with positives='labels' needs the labels: the loader must yield (images, input_ids, "
-                             f"attention_mask, labels [B, C]); got a batch of {len(batch)} tensors")
-        n = images.shape[0]
-        lo, hi = self._shard(n) if self.world > 1 else (0, n)
-        if self.world > 1 and n % self.world:
-            raise ValueError(f"joint-encoder training shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
-        dev = self.device
-        keys = None
-        if positives is not None:   # once per step, where the loader left the tensors
-            keys = self._joint.pair_keys(ids[lo:hi], mask[lo:hi], batch[3][lo:hi] if positives == "labels" else None)
-        loss = self._joint.step(images[lo:hi].to(dev, non_blocking=True), ids[lo:hi].to(dev, non_blocking=True),
-                                mask[lo:hi].to(dev, non_blocking=True), keys=keys)
+        images, ids, mask, keys = self._joint_shard(batch)
+        loss = self._joint.step(images, ids, mask, keys=keys)
         self._bert_cache.clear()
         return loss
+
+    def _joint_shard(self, batch, who="joint-encoder training"):
+        """A loader batch `(images, input_ids, attention_mask[, labels])` -> this rank's rows of it, on the device, and their keys:
+        (images, input_ids, attention_mask, keys or None).  The keys (`pair_keys`: None unless the joint trainer has positives) are
+        hashed once, where the loader left the tensors.  `who` names the caller in the refusals of a short batch and of rows that do
+        not divide over the ranks.  The first tensor is cut and moved whatever it holds: evaluation passes the image embeddings it
+        already has."""
+        positives = self._joint.positives
+        if len(batch) < 3:
+            raise ValueError(f"{who} expects loaders that yield (images, input_ids, attention_mask[, labels]); got a batch of "
+                             f"{len(batch)} tensors")
+        if positives == "labels" and len(batch) < 4:
+            raise ValueError(f"{who} with positives='labels' needs the labels: the loader must yield (images, input_ids, "
+                             f"attention_mask, labels [B, C]); got a batch of {len(batch)} tensors")
+        n = batch[0].shape[0]
+        if self.world > 1 and n % self.world:
+            raise ValueError(f"{who} shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
+        lo, hi = self._shard(n) if self.world > 1 else (0, n)
+        images, ids, mask = (t[lo:hi] for t in batch[:3])
+        keys = self._joint.pair_keys(ids, mask, batch[3][lo:hi] if positives == "labels" else None)
+        return (*(t.to(self.device, non_blocking=True) for t in (images, ids, mask)), keys)
 
     def train(self, train_loader, criterion, epoch, CONTINUAL_LEARNING=None, threshold=None, scheduler=None, part=None,
               epochs=None, actual_task=None):
@@ -748,37 +734,27 @@ class Trainer:
                                 current_task=None, last_batch=0, actual_task=None):
         """One epoch on the single label column `current_task` (`Trainer.py:608-680`); returns the running iteration.  (Joint-encoder
         mode: the InfoNCE step has no label columns — the task is defined by what its loader yields, `current_task` only numbers it.)"""
-        batch_idx = last_batch
-        self._set_mode(True)
-        cl = CONTINUAL_LEARNING == "myCL" and actual_task is not None and actual_task > 1
-        names = [self.class_names[current_task]]
-        for batch in train_loader:
-            if cl:
-                self.model_copy()
-            batch_idx += 1
-            loss = self._train_step(batch, names, criterion, label_cols=current_task)
-            if cl:
-                self.myIncremental(threshold, batch_idx)
-            if self.writer is not None:
-                self.writer.add_scalar('train/Loss', loss, batch_idx)
-        if cl:
-            self.myIncremental_save_log(batch_idx)
-        self._log_temperature(epoch)
-        return batch_idx
+        return self._class_incremental_epoch(train_loader, criterion, epoch, CONTINUAL_LEARNING, threshold, last_batch, actual_task,
+                                             [self.class_names[current_task]], current_task)
 
     def train_class_more_labels_incremental(self, train_loader, criterion, epoch, CONTINUAL_LEARNING=None, threshold=None,
                                             current_task=None, last_batch=0, actual_task=None):
         """One epoch on label columns `[:current_task+1]` (`Trainer.py:682-756`); returns the running iteration.  (Joint-encoder mode:
         as in `train_class_incremental`.)"""
+        return self._class_incremental_epoch(train_loader, criterion, epoch, CONTINUAL_LEARNING, threshold, last_batch, actual_task,
+                                             self.class_names[:current_task + 1], slice(0, current_task + 1))
+
+    def _class_incremental_epoch(self, train_loader, criterion, epoch, CONTINUAL_LEARNING, threshold, last_batch, actual_task, names,
+                                 label_cols):
+        """the epoch loop of the two class-incremental schedules: they differ in the classes `names` and the label columns of a task"""
         batch_idx = last_batch
         self._set_mode(True)
         cl = CONTINUAL_LEARNING == "myCL" and actual_task is not None and actual_task > 1
-        names = self.class_names[:current_task + 1]
         for batch in train_loader:
             if cl:
                 self.model_copy()
             batch_idx += 1
-            loss = self._train_step(batch, names, criterion, label_cols=slice(0, current_task + 1))
+            loss = self._train_step(batch, names, criterion, label_cols=label_cols)
             if cl:
                 self.myIncremental(threshold, batch_idx)
             if self.writer is not None:
@@ -825,7 +801,6 @@ class Trainer:
     def _parse_retrieval(opt):
         """the "retrieval" entry of `joint_encoders`: None / False -> off (None), True -> Recall@1/5/10, a sequence of positive
         integers -> those cut-offs"""
-        from .contrastive import RETRIEVAL_KS, check_ks
         if opt is None or opt is False:
             return None
         if opt is True:
@@ -837,20 +812,13 @@ class Trainer:
     def _retrieval_collect(self, acc, batch, new_embs):
         """one evaluation batch of the retrieval set: this rank's shard of the image embeddings `_eval_loop` already has, and the
         paired reports through the text encoder (under no_grad, eval mode: no dropout, no augmentation)"""
-        n = new_embs.shape[0]
-        if self.world > 1 and n % self.world:
-            raise ValueError(f"retrieval evaluation shards each batch evenly: {n} rows over {self.world} ranks (use drop_last)")
-        lo, hi = self._shard(n) if self.world > 1 else (0, n)
-        ids, mask = batch[1][lo:hi], batch[2][lo:hi]
-        keys = self._joint.pair_keys(ids, mask, batch[3][lo:hi] if self._joint.positives == "labels" else None)
-        acc[0].append(new_embs[lo:hi])
-        acc[1].append(self.bert_encoder.model.get_projected_text_embeddings(ids.to(self.device), mask.to(self.device),
-                                                                            normalize_embeddings=False))
+        embs, ids, mask, keys = self._joint_shard((new_embs,) + tuple(batch[1:]), "retrieval evaluation")
+        acc[0].append(embs)
+        acc[1].append(self.bert_encoder.model.get_projected_text_embeddings(ids, mask, normalize_embeddings=False))
         if keys is not None:
             acc[2].append(keys.to(self.device))
 
     def _retrieval_finish(self, acc):
-        from .contrastive import retrieval_metrics
         if not acc[0]:
             return None
         return retrieval_metrics(torch.cat(acc[0]).contiguous(), torch.cat(acc[1]).contiguous(),
@@ -941,20 +909,22 @@ class Trainer:
     def _joint_shards(self, loader, what):
         """this rank's shard of every batch of `loader`, on the device, cut as `_joint_step` cuts it (with its keys when the trainer
         has positives)"""
-        positives, dev = self._joint.positives, self.device
         for batch in loader:
-            if len(batch) < 3 or (positives == "labels" and len(batch) < 4):
-                raise ValueError(f"Trainer.{what} expects the batches of joint-encoder training: (images, input_ids, "
-                                 f"attention_mask[, labels]); got a batch of {len(batch)} tensors")
-            images, ids, mask = batch[0], batch[1], batch[2]
-            n = images.shape[0]
-            if self.world > 1 and n % self.world:
-                raise ValueError(f"joint-encoder training shards the batch evenly: {n} rows over {self.world} ranks (use drop_last)")
-            lo, hi = self._shard(n) if self.world > 1 else (0, n)
-            out = (images[lo:hi].to(dev, non_blocking=True), ids[lo:hi].to(dev, non_blocking=True), mask[lo:hi].to(dev, non_blocking=True))
-            if positives is not None:   # the keys, hashed where the loader left the tensors
-                out += (self._joint.pair_keys(ids[lo:hi], mask[lo:hi], batch[3][lo:hi] if positives == "labels" else None),)
-            yield out
+            shard = self._joint_shard(batch, f"Trainer.{what}")
+            yield shard if shard[3] is not None else shard[:3]
+
+    def end_task(self, loader) -> None:
+        """The task boundary of the incremental schedules: after a task that another one follows, whatever the joint trainer was
+        configured with, in this order -- `consolidate(loader)` ("ewc_lambda"), `snapshot_teacher()` ("distill_weight"),
+        `remember(loader)` ("agem_memory").  `loader` is the finished task's.  Nothing in adapter mode.  Every rank calls it."""
+        if self._joint is None:
+            return
+        if self._joint.ewc is not None:               # anchor this task before the next one starts
+            self.consolidate(loader)
+        if self._joint.distill_weight is not None:    # this task's encoders teach the next one
+            self.snapshot_teacher()
+        if self._joint.memory is not None:            # rows of this task constrain the next one's updates
+            self.remember(loader)
 
     def remember(self, loader) -> int:
         """End of a task with `joint_encoders={..., "agem_memory": M}`: each batch of `loader` sharded as in

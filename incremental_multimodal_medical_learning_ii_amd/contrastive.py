@@ -48,6 +48,7 @@ a step issues exactly the calls it always did.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Optional, Tuple
 
@@ -340,6 +341,22 @@ def check_agem_options(memory, batch, every, seed) -> tuple:
     return memory, batch, 1 if every is None else every, 0 if seed is None else seed
 
 
+def _host_collective_device(group) -> str:
+    """where the tensor of a collective on host integers has to live: RCCL moves device memory, gloo host memory"""
+    import torch.distributed as dist
+    return "cuda" if dist.get_backend(group) == "nccl" else "cpu"
+
+
+def _broadcast_state(seed: int, counter: int, group) -> Tuple[int, int]:
+    """the (seed, counter) of a random stream -> rank 0's, on every rank: one broadcast of two int64 (the 64-bit seed travels as its
+    two's-complement reading)"""
+    import torch.distributed as dist
+    t = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed, counter], dtype=torch.int64, device=_host_collective_device(group))
+    dist.broadcast(t, src=0 if group is None else dist.get_global_rank(group, 0), group=group)
+    s, c = (int(v) for v in t.cpu())
+    return s & (2 ** 64 - 1), c
+
+
 class JointContrastiveTrainer:
     def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, lr: float = 1e-4,
                  temperature: float = 0.07, group=None, train_mlm_head: bool = False, two_streams: Optional[bool] = None,
@@ -498,13 +515,7 @@ class JointContrastiveTrainer:
         version = getattr(tm, "_dropout_version", None)
         if self.world == 1 or not getattr(tm, "dropout_enabled", False) or version == self._dropout_synced:
             return
-        import torch.distributed as dist
-        seed, counter = tm.dropout_state
-        dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
-        t = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed, counter], dtype=torch.int64, device=dev)
-        dist.broadcast(t, src=0 if self.group is None else dist.get_global_rank(self.group, 0), group=self.group)
-        s, c = (int(v) for v in t.cpu())
-        tm.dropout_state = (s & (2 ** 64 - 1), c)
+        tm.dropout_state = _broadcast_state(*tm.dropout_state, self.group)
         self._dropout_synced = tm._dropout_version
 
     @property
@@ -530,13 +541,7 @@ class JointContrastiveTrainer:
         time (on every rank, in the same program order)."""
         if self.world == 1 or self._augment is None or self._augment_version == self._augment_synced:
             return
-        import torch.distributed as dist
-        seed, counter = self._augment
-        dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
-        t = torch.tensor([seed - 2 ** 64 if seed >= 2 ** 63 else seed, counter], dtype=torch.int64, device=dev)
-        dist.broadcast(t, src=0 if self.group is None else dist.get_global_rank(self.group, 0), group=self.group)
-        s, c = (int(v) for v in t.cpu())
-        self._augment = [s & (2 ** 64 - 1), c]
+        self._augment = list(_broadcast_state(*self._augment, self.group))
         self._augment_synced = self._augment_version
 
     def _step_forward_loss(self, images, input_ids, attention_mask, labels, keys) -> torch.Tensor:
@@ -705,9 +710,10 @@ class JointContrastiveTrainer:
         self.optimizer.zero_grad()
         self.sync_dropout_state()
         self.sync_augment_state()
-        if self.world > 1 and self._spans:
-            works, fired = [], []
+        works, fired = [], []      # without spans both stay empty: the final reduce then takes the whole buffer and waits for nothing
+        on_ready = None
 
+        if self.world > 1 and self._spans:
             def on_ready(tag: str) -> None:
                 span = self._spans.get(tag)
                 if span is None:
@@ -718,26 +724,40 @@ class JointContrastiveTrainer:
                 fired.append(tag)
                 works.extend(self.optimizer.all_reduce_span(span[0], span[1], self.group))
 
-            if chunked:
-                loss = self._chunked_forward_backward(images, input_ids, attention_mask, labels, keys, slices, on_ready)
-            else:
-                self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = on_ready
-                try:
-                    loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
-                finally:
-                    self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
-                self._backward(loss)
-            self.last_overlapped = tuple(fired)
-            self.optimizer.all_reduce_grads(self.group, skip=[self._spans[t] for t in fired], pending=works)
+        if chunked:
+            loss = self._chunked_forward_backward(images, input_ids, attention_mask, labels, keys, slices, on_ready)
         else:
-            if chunked:
-                loss = self._chunked_forward_backward(images, input_ids, attention_mask, labels, keys, slices, None)
-            else:
-                loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)
-                self._backward(loss)
-            if self.world > 1:
-                self.optimizer.all_reduce_grads(self.group)
+            self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = on_ready
+            try:
+                loss = self._step_forward_loss(images, input_ids, attention_mask, labels, keys)   # the hook is captured by the two autograd nodes here
+            finally:
+                self.image_model.grad_ready_hook = self.text_model.grad_ready_hook = None
+            self._backward(loss)
+        if on_ready is not None:
+            self.last_overlapped = tuple(fired)
+        if self.world > 1:
+            self.optimizer.all_reduce_grads(self.group, skip=[self._spans[t] for t in fired], pending=works)
         return loss
+
+    @contextlib.contextmanager
+    def _contrastive_only(self):
+        """While it is open `_gradient` is that of the contrastive loss alone, on the images as they are: no augmentation (its counter
+        does not move) and no teacher.  What `consolidate` estimates and what the A-GEM reference is taken from."""
+        augment, self._augment = self._augment, None
+        self._distill_off = True
+        try:
+            yield
+        finally:
+            self._augment = augment
+            self._distill_off = False
+
+    def _stored_gradient(self, batch) -> torch.Tensor:
+        """`_gradient` of a stored batch `(images, input_ids, attention_mask[, labels | keys])`: a fourth tensor of more than one
+        dimension is taken as labels, a 1-D one as keys"""
+        extra = batch[3] if len(batch) > 3 else None
+        labels = extra if extra is not None and extra.dim() > 1 else None
+        keys = extra if extra is not None and extra.dim() == 1 else None
+        return self._gradient(batch[0], batch[1], batch[2], labels, keys)
 
     def step(self, images: torch.Tensor, input_ids: torch.Tensor, attention_mask: torch.Tensor,
              labels: Optional[torch.Tensor] = None, keys: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -779,16 +799,8 @@ class JointContrastiveTrainer:
         if self.agem.valid and k % self.agem_every != 0:
             return
         n = min(rows if self.agem_batch is None else self.agem_batch, len(self.memory))
-        batch = self.memory.sample(n, step=k)
-        extra = batch[3] if len(batch) > 3 else None
-        augment, self._augment = self._augment, None
-        self._distill_off = True
-        try:
-            self._gradient(batch[0], batch[1], batch[2], extra if extra is not None and extra.dim() > 1 else None,
-                           extra if extra is not None and extra.dim() == 1 else None)
-        finally:
-            self._augment = augment
-            self._distill_off = False
+        with self._contrastive_only():
+            self._stored_gradient(self.memory.sample(n, step=k))
         self.agem.store_reference()
 
     def remember(self, batches) -> int:
@@ -801,9 +813,8 @@ class JointContrastiveTrainer:
         kept = self.memory.add_task(batches)
         if self.world > 1:
             import torch.distributed as dist
-            dev = "cuda" if dist.get_backend(self.group) == "nccl" else "cpu"
             total = len(self.memory)
-            t = torch.tensor([total, -total], dtype=torch.int64, device=dev)
+            t = torch.tensor([total, -total], dtype=torch.int64, device=_host_collective_device(self.group))
             dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
             hi, lo = int(t[0]), -int(t[1])
             if hi != lo:
@@ -832,24 +843,16 @@ class JointContrastiveTrainer:
         used = 0
         if self.ewc.fisher == "empirical":
             self.ewc.begin_estimate()
-            augment, self._augment = self._augment, None      # the images as they are; the counter does not move
-            self._distill_off = True                          # the Fisher diagonal of the contrastive loss alone: no teacher runs
-            try:
+            with self._contrastive_only():      # the Fisher diagonal of the contrastive loss alone, of the images as they are
                 for batch in batches:
                     if max_batches is not None and used >= max_batches:
                         break
                     if len(batch) < 3:
                         raise ValueError("consolidate: a batch is (images, input_ids, attention_mask[, labels | keys]); got "
                                          f"{len(batch)} tensors")
-                    extra = batch[3] if len(batch) > 3 else None
-                    labels = extra if extra is not None and extra.dim() > 1 else None
-                    keys = extra if extra is not None and extra.dim() == 1 else None
-                    self._gradient(batch[0], batch[1], batch[2], labels, keys)
+                    self._stored_gradient(batch)
                     self.ewc.accumulate()
                     used += 1
-            finally:
-                self._augment = augment
-                self._distill_off = False
         self.ewc.consolidate()
         return used
 

@@ -122,23 +122,26 @@ def _setup(args, kind):
     if joint:
         im, engine = _joint_models(args, device)
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine,
-                             joint_encoders={"image_model": im, "temperature": args.temperature,
-                                             "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None)),
-                                             "learn_temperature": bool(getattr(args, "learn_temperature", False)),
-                                             "contrastive_loss": getattr(args, "contrastive_loss", None) or "infonce",
-                                             "sigmoid_bias": getattr(args, "sigmoid_bias", None),
-                                             "micro_batch": getattr(args, "micro_batch", None),
-                                             **optimiser_from_args(args, kind, train_loader),
-                                             **ewc_from_args(args),
-                                             **distill_from_args(args),
-                                             **agem_from_args(args),
-                                             "augment": augment_from_args(args),
-                                             "retrieval": retrieval_from_args(args)})
+                             joint_encoders=joint_encoders_from_args(args, im, kind, train_loader))
     else:
         from .health_multimodal.text import get_cxr_bert_inference
         engine = get_cxr_bert_inference(args.pretrained_text, device="cuda")
         trainer = TR.Trainer(args.single_prompt, prompts, class_names, "standard", args.lr, device, writer, bert_encoder=engine)
     return trainer, writer, train_loader, val_loader, test_loader
+
+
+def joint_encoders_from_args(args, image_model, kind=None, train_loader=None) -> dict:
+    """the `joint_encoders` dict of `--joint`: every flag of the north-star step as the key `Trainer` reads"""
+    return {"image_model": image_model, "temperature": args.temperature,
+            "positives": {"pair": None}.get(getattr(args, "positives", "pair"), getattr(args, "positives", None)),
+            "learn_temperature": bool(getattr(args, "learn_temperature", False)),
+            "contrastive_loss": getattr(args, "contrastive_loss", None) or "infonce",
+            "sigmoid_bias": getattr(args, "sigmoid_bias", None),
+            "micro_batch": getattr(args, "micro_batch", None),
+            **optimiser_from_args(args, kind, train_loader),
+            **continual_from_args(args),
+            "augment": augment_from_args(args),
+            "retrieval": retrieval_from_args(args)}
 
 
 def retrieval_from_args(args):
@@ -171,45 +174,24 @@ def optimiser_from_args(args, kind=None, train_loader=None) -> dict:
     return out
 
 
-EWC_LAMBDA = 1e4     # F is a squared mean gradient, so useful strengths are large
-
-
-def ewc_from_args(args) -> dict:
-    """`--cl ewc` / `--ewc-lambda` / `--ewc-batches` / `--ewc-gamma` / `--ewc-fisher` -> the `joint_encoders` keys they set (without
-    `--cl ewc`: an empty dict)"""
-    if getattr(args, "cl", None) != "ewc":
-        return {}
-    out = {"ewc_lambda": EWC_LAMBDA if args.ewc_lambda is None else args.ewc_lambda}
-    for flag in ("ewc_batches", "ewc_gamma", "ewc_fisher"):
-        if getattr(args, flag, None) is not None:
-            out[flag] = getattr(args, flag)
-    return out
-
-
+EWC_LAMBDA = 1e4         # F is a squared mean gradient, so useful strengths are large
 DISTILL_WEIGHT = 1.0     # beta of --cl lwf: the distillation term enters at the weight of the contrastive loss
+AGEM_MEMORY = 256        # rows kept per task and rank by --cl agem
+# --cl value -> (the master key of its `joint_encoders` group, that key's default, the group's other flags); a flag and the key it
+# sets share a name
+CONTINUAL = {"ewc": ("ewc_lambda", EWC_LAMBDA, ("ewc_batches", "ewc_gamma", "ewc_fisher")),
+             "lwf": ("distill_weight", DISTILL_WEIGHT, ("distill_temperature",)),
+             "agem": ("agem_memory", AGEM_MEMORY, ("agem_batch", "agem_every"))}
 
 
-def distill_from_args(args) -> dict:
-    """`--cl lwf` / `--distill-weight` / `--distill-temperature` -> the `joint_encoders` keys they set (without `--cl lwf`: an empty
-    dict)"""
-    if getattr(args, "cl", None) != "lwf":
+def continual_from_args(args) -> dict:
+    """`--cl ewc | lwf | agem` and the flags of that method (`--ewc-*`, `--distill-*`, `--agem-*`) -> the `joint_encoders` keys they
+    set: the master key always (its default unless the flag is given), the others when given.  Any other `--cl`: an empty dict."""
+    if getattr(args, "cl", None) not in CONTINUAL:
         return {}
-    out = {"distill_weight": DISTILL_WEIGHT if args.distill_weight is None else args.distill_weight}
-    if getattr(args, "distill_temperature", None) is not None:
-        out["distill_temperature"] = args.distill_temperature
-    return out
-
-
-AGEM_MEMORY = 256     # rows kept per task and rank by --cl agem
-
-
-def agem_from_args(args) -> dict:
-    """`--cl agem` / `--agem-memory` / `--agem-batch` / `--agem-every` -> the `joint_encoders` keys they set (without `--cl agem`: an
-    empty dict)"""
-    if getattr(args, "cl", None) != "agem":
-        return {}
-    out = {"agem_memory": AGEM_MEMORY if args.agem_memory is None else args.agem_memory}
-    for flag in ("agem_batch", "agem_every"):
+    master, default, flags = CONTINUAL[args.cl]
+    out = {master: default if getattr(args, master) is None else getattr(args, master)}
+    for flag in flags:
         if getattr(args, flag, None) is not None:
             out[flag] = getattr(args, flag)
     return out
@@ -278,12 +260,8 @@ def class_incremental(args):
                                 last_batch, actual_task)
                 if args.cl == "profCL" and actual_task > 1:
                     trainer.profIncremental(epoch, args.epochs, actual_task, threshold)
-            if args.cl == "ewc" and actual_task < len(tasks_order):      # anchor this task before the next one starts
-                trainer.consolidate(train_loader[actual_task - 1])
-            if args.cl == "lwf" and actual_task < len(tasks_order):      # this task's encoders teach the next one
-                trainer.snapshot_teacher()
-            if args.cl == "agem" and actual_task < len(tasks_order):     # rows of this task constrain the next one's updates
-                trainer.remember(train_loader[actual_task - 1])
+            if actual_task < len(tasks_order):      # --cl ewc | lwf | agem: what the finished task leaves for the next one
+                trainer.end_task(train_loader[actual_task - 1])
             trainer.val(val_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
             metrics = trainer.test(test_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
     finally:
@@ -309,12 +287,8 @@ def data_incremental(args):
                               actual_task=part)
                 if args.cl == "profCL":
                     trainer.profIncremental(epoch, args.epochs, part, threshold)
-            if args.cl == "ewc" and part < args.parts:
-                trainer.consolidate(train_loader[part - 1])
-            if args.cl == "lwf" and part < args.parts:
-                trainer.snapshot_teacher()
-            if args.cl == "agem" and part < args.parts:
-                trainer.remember(train_loader[part - 1])
+            if part < args.parts:
+                trainer.end_task(train_loader[part - 1])
             train_loader[part - 1] = None
             trainer.val(val_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
             metrics = trainer.test(test_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)

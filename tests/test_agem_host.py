@@ -345,24 +345,26 @@ def test_trainer_refuses_the_keys_without_joint_mode():
     im = object()
     for key in ("agem_batch", "agem_every", "agem_seed"):
         with pytest.raises(ValueError, match="agem_memory"):
-            TR.Trainer._check_agem_keys({"image_model": im, key: 2})
+            TR.joint_options({"image_model": im, key: 2})
     for bad in (0, -3, 2.5, True):
         with pytest.raises(ValueError, match="agem_memory"):
-            TR.Trainer._check_agem_keys({"image_model": im, "agem_memory": bad})
+            TR.joint_options({"image_model": im, "agem_memory": bad})
         with pytest.raises(ValueError, match="agem_every"):
-            TR.Trainer._check_agem_keys({"image_model": im, "agem_memory": 8, "agem_every": bad})
-    assert TR.Trainer._check_agem_keys({"image_model": im, "agem_memory": 8, "agem_batch": 4}) is None
-    assert TR.Trainer._check_agem_keys({"image_model": im}) is None and TR.Trainer._check_agem_keys(None) is None
+            TR.joint_options({"image_model": im, "agem_memory": 8, "agem_every": bad})
+    # (the removed checker returned None for what it accepted; the one function returns what it passes on)
+    step, own = TR.joint_options({"image_model": im, "agem_memory": 8, "agem_batch": 4})
+    assert (step["agem_memory"], step["agem_batch"]) == (8, 4) and "agem_every" not in step and own["image_model"] is im
+    assert "agem_memory" not in TR.joint_options({"image_model": im})[0] and TR.joint_options(None)[0] == {}
 
 
 def test_drivers_arguments():
     a = drivers.parse_args(["class-inc", "--joint"])
-    assert drivers.agem_from_args(a) == {}
+    assert drivers.continual_from_args(a) == {}
     a = drivers.parse_args(["class-inc", "--joint", "--cl", "agem"])
-    assert drivers.agem_from_args(a) == {"agem_memory": drivers.AGEM_MEMORY} and drivers.AGEM_MEMORY == 256
-    assert drivers.ewc_from_args(a) == {} and drivers.distill_from_args(a) == {}
+    # the whole dict: no "ewc_*" and no "distill_*" key
+    assert drivers.continual_from_args(a) == {"agem_memory": drivers.AGEM_MEMORY} and drivers.AGEM_MEMORY == 256
     a = drivers.parse_args(["data-inc", "--joint", "--cl", "agem", "--agem-memory", "64", "--agem-batch", "32", "--agem-every", "4"])
-    assert drivers.agem_from_args(a) == {"agem_memory": 64, "agem_batch": 32, "agem_every": 4}
+    assert drivers.continual_from_args(a) == {"agem_memory": 64, "agem_batch": 32, "agem_every": 4}
     for argv in (["class-inc", "--cl", "agem"],                                    # needs --joint
                  ["zero-joint", "--joint", "--cl", "agem"],                         # a single task: nothing to remember between
                  ["class-inc", "--joint", "--agem-memory", "10"],                   # the options need --cl agem

@@ -181,13 +181,15 @@ def test_trainer_refuses_the_keys_without_joint_mode():
             TR.Trainer(True, [], [], "standard", 1e-3, "cpu", None, bert_encoder=object(), joint_encoders=je)
     im = object()
     with pytest.raises(ValueError, match="without it"):
-        TR.Trainer._check_distill_keys({"image_model": im, "distill_temperature": 0.1})
+        TR.joint_options({"image_model": im, "distill_temperature": 0.1})
     with pytest.raises(ValueError, match="distill_weight"):
-        TR.Trainer._check_distill_keys({"image_model": im, "distill_weight": -2.0})
+        TR.joint_options({"image_model": im, "distill_weight": -2.0})
     with pytest.raises(ValueError, match="distill_temperature"):
-        TR.Trainer._check_distill_keys({"image_model": im, "distill_weight": 1.0, "distill_temperature": 0.0})
-    assert TR.Trainer._check_distill_keys({"image_model": im, "distill_weight": 0.0, "distill_temperature": 0.1}) is None
-    assert TR.Trainer._check_distill_keys({"image_model": im}) is None and TR.Trainer._check_distill_keys(None) is None
+        TR.joint_options({"image_model": im, "distill_weight": 1.0, "distill_temperature": 0.0})
+    # (the removed checker returned None for what it accepted; the one function returns what it passes on)
+    step, own = TR.joint_options({"image_model": im, "distill_weight": 0.0, "distill_temperature": 0.1})
+    assert (step["distill_weight"], step["distill_temperature"]) == (0.0, 0.1) and own["image_model"] is im
+    assert "distill_weight" not in TR.joint_options({"image_model": im})[0] and TR.joint_options(None)[0] == {}
     t = TR.Trainer.__new__(TR.Trainer)
     t._joint = None
     with pytest.raises(ValueError, match="distill_weight"):
@@ -196,13 +198,13 @@ def test_trainer_refuses_the_keys_without_joint_mode():
 
 def test_drivers_arguments():
     a = drivers.parse_args(["class-inc", "--joint"])
-    assert drivers.distill_from_args(a) == {}
+    assert drivers.continual_from_args(a) == {}
     a = drivers.parse_args(["class-inc", "--joint", "--cl", "lwf"])
-    assert drivers.distill_from_args(a) == {"distill_weight": 1.0} and drivers.DISTILL_WEIGHT == 1.0 and drivers.ewc_from_args(a) == {}
+    assert drivers.continual_from_args(a) == {"distill_weight": 1.0} and drivers.DISTILL_WEIGHT == 1.0     # the whole dict: no "ewc_*" key
     a = drivers.parse_args(["data-inc", "--joint", "--cl", "lwf", "--distill-weight", "0.5", "--distill-temperature", "0.2"])
-    assert drivers.distill_from_args(a) == {"distill_weight": 0.5, "distill_temperature": 0.2}
+    assert drivers.continual_from_args(a) == {"distill_weight": 0.5, "distill_temperature": 0.2}
     a = drivers.parse_args(["data-inc", "--joint", "--cl", "lwf", "--distill-weight", "0"])
-    assert drivers.distill_from_args(a) == {"distill_weight": 0.0}
+    assert drivers.continual_from_args(a) == {"distill_weight": 0.0}
     for argv in (["class-inc", "--cl", "lwf"],                                      # needs --joint
                  ["zero-joint", "--joint", "--cl", "lwf"],                           # a single task: no teacher to take between tasks
                  ["class-inc", "--joint", "--distill-weight", "1"],                  # the options need --cl lwf

@@ -258,22 +258,22 @@ def test_trainer_refuses_the_keys_without_joint_mode():
             TR.Trainer(True, [], [], "standard", 1e-3, "cpu", None, bert_encoder=object(), joint_encoders=je)
     im = object()
     with pytest.raises(ValueError, match="ewc_lambda"):
-        TR.Trainer._check_ewc_keys({"image_model": im, "ewc_gamma": 0.5})
+        TR.joint_options({"image_model": im, "ewc_gamma": 0.5})
     for bad in (0, -3, 2.5, True):
         with pytest.raises(ValueError, match="ewc_batches"):
-            TR.Trainer._check_ewc_keys({"image_model": im, "ewc_lambda": 1.0, "ewc_batches": bad})
-    assert TR.Trainer._check_ewc_keys({"image_model": im, "ewc_lambda": 1.0, "ewc_batches": 3}) == 3
-    assert TR.Trainer._check_ewc_keys({"image_model": im}) is None and TR.Trainer._check_ewc_keys(None) is None
+            TR.joint_options({"image_model": im, "ewc_lambda": 1.0, "ewc_batches": bad})
+    assert TR.joint_options({"image_model": im, "ewc_lambda": 1.0, "ewc_batches": 3})[1]["ewc_batches"] == 3
+    assert TR.joint_options({"image_model": im})[1]["ewc_batches"] is None and TR.joint_options(None)[1]["ewc_batches"] is None
 
 
 def test_drivers_arguments():
     a = drivers.parse_args(["class-inc", "--joint"])
-    assert drivers.ewc_from_args(a) == {}
+    assert drivers.continual_from_args(a) == {}
     a = drivers.parse_args(["class-inc", "--joint", "--cl", "ewc"])
-    assert drivers.ewc_from_args(a) == {"ewc_lambda": drivers.EWC_LAMBDA}
+    assert drivers.continual_from_args(a) == {"ewc_lambda": drivers.EWC_LAMBDA}
     a = drivers.parse_args(["data-inc", "--joint", "--cl", "ewc", "--ewc-lambda", "3e5", "--ewc-batches", "8", "--ewc-gamma", "0.9",
                             "--ewc-fisher", "identity"])
-    assert drivers.ewc_from_args(a) == {"ewc_lambda": 3e5, "ewc_batches": 8, "ewc_gamma": 0.9, "ewc_fisher": "identity"}
+    assert drivers.continual_from_args(a) == {"ewc_lambda": 3e5, "ewc_batches": 8, "ewc_gamma": 0.9, "ewc_fisher": "identity"}
     for argv in (["class-inc", "--cl", "ewc"],                                     # needs --joint
                  ["zero-joint", "--joint", "--cl", "ewc"],                          # a single task: nothing to consolidate between
                  ["class-inc", "--joint", "--ewc-lambda", "10"],                    # the options need --cl ewc
