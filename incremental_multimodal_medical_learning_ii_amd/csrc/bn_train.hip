@@ -84,35 +84,49 @@ struct ColMap {
 };
 
 // Batch statistics in ONE pass over z: a thread accumulates d = z - s and d^2 against the shift s = z[first row of the block] (so
-// the squares do not cancel against a large mean); part[by] = (block mean, block M2 = sum (z - block mean)^2).  The final kernel
-// merges the blocks with Chan's formula: n, mean, M2 <- n + nb, mean + delta nb / (n + nb), M2 + M2b + delta^2 n nb / (n + nb).
+// the squares do not cancel against a large mean); part[by] = (block mean, block M2 = sum (z - block mean)^2).  The block mean is
+// s + sum(d) / nb where the shift is the better origin (|sum d| <= |sum z|: offset columns, where sum(d) is small and exact), and
+// sum(z) / nb where zero is (a column whose mean is small against its spread: there the shifted sums grow to |s - mean| nb and
+// their rounding, ~ulp(s), would be tens of ulps of the mean itself).  The final kernel merges the blocks with Chan's formula:
+// n, mean, M2 <- n + nb, mean + delta nb / (n + nb), M2 + M2b + delta^2 n nb / (n + nb).
 __global__ __launch_bounds__(256) void colstats_partial_kernel(const void* __restrict__ x, long plane, long rows, int C, int rows_per, int cql,
                                                                float* __restrict__ part_mean, float* __restrict__ part_m2) {
   __shared__ float sh[2][256][8];
   const ColMap m(cql, C);
   const long r0 = (long)blockIdx.y * rows_per, r1 = min(rows, r0 + rows_per);
-  float s1[8], s2[8], sft[8];
+  float s0[8], s1[8], s2[8], sft[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) { s1[q] = 0.f; s2[q] = 0.f; sft[q] = 0.f; }
+  for (int q = 0; q < 8; ++q) { s0[q] = 0.f; s1[q] = 0.f; s2[q] = 0.f; sft[q] = 0.f; }
   if (m.col < C) {
     ld8(x, plane, r0 * C + m.col, sft);
     for (long r = r0 + m.rl; r < r1; r += m.rln) {
       float v[8]; ld8(x, plane, r * C + m.col, v);
 #pragma unroll
-      for (int q = 0; q < 8; ++q) { const float d = v[q] - sft[q]; s1[q] += d; s2[q] = fmaf(d, d, s2[q]); }
+      for (int q = 0; q < 8; ++q) { const float d = v[q] - sft[q]; s0[q] += v[q]; s1[q] += d; s2[q] = fmaf(d, d, s2[q]); }
     }
   }
 #pragma unroll
   for (int q = 0; q < 8; ++q) { sh[0][threadIdx.x][q] = s1[q]; sh[1][threadIdx.x][q] = s2[q]; }
   __syncthreads();
-  if (m.rl == 0 && m.col < C) {
+  const bool owner = m.rl == 0 && m.col < C;
+  const int cqn = 1 << cql;
+  if (owner) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      for (int i = 1; i < m.rln; ++i) { s1[q] += sh[0][i * cqn + m.cq][q]; s2[q] += sh[1][i * cqn + m.cq][q]; }
+  }
+  __syncthreads();      // the plain sums go through the same LDS (a third array would cost the kernel two blocks per CU)
+#pragma unroll
+  for (int q = 0; q < 8; ++q) sh[0][threadIdx.x][q] = s0[q];
+  __syncthreads();
+  if (owner) {
     const float nb = (float)(r1 - r0);
-    const int cqn = 1 << cql;
 #pragma unroll
     for (int q = 0; q < 8; ++q) {
-      float a = s1[q], b = s2[q];
-      for (int i = 1; i < m.rln; ++i) { a += sh[0][i * cqn + m.cq][q]; b += sh[1][i * cqn + m.cq][q]; }
-      part_mean[(long)blockIdx.y * C + m.col + q] = sft[q] + a / nb;
+      const float a = s1[q], b = s2[q];
+      float t = s0[q];
+      for (int i = 1; i < m.rln; ++i) t += sh[0][i * cqn + m.cq][q];
+      part_mean[(long)blockIdx.y * C + m.col + q] = fabsf(t) < fabsf(a) ? t / nb : sft[q] + a / nb;
       part_m2[(long)blockIdx.y * C + m.col + q] = b - a * a / nb;
     }
   }
