@@ -9,6 +9,7 @@
 //  * eval scoring (Trainer.py:797-837)
 #include "cxrk.h"
 #include "cxrk_common.h"
+#include "flat_buffers.h"
 
 using namespace cxrk;
 
@@ -285,10 +286,8 @@ __global__ __launch_bounds__(256) void logit_scale_grad_kernel(const float* __re
                                                                const float* __restrict__ upstream, float scale,
                                                                float* __restrict__ dtheta, int accumulate) {
   __shared__ float sh[16];
-  float s1 = 0.f, s2 = 0.f;
-  for (long i = threadIdx.x; i < n1; i += 256) s1 += part1[i];
-  for (long i = threadIdx.x; i < n2; i += 256) s2 += part2[i];
-  const float s = block_sum(s1, sh) + block_sum(s2, sh);
+  const float s1 = block_fold(part1, n1, sh);
+  const float s = s1 + block_fold(part2, n2, sh);
   if (threadIdx.x == 0) { const float v = upstream[0] * scale * s; dtheta[0] = accumulate ? dtheta[0] + v : v; }
 }
 
@@ -350,13 +349,11 @@ __global__ __launch_bounds__(256) void sigmoid_pairs_kernel(float* __restrict__ 
   }
 }
 
-// out[0] (+)= scale * sum part[0..n); single block, fixed order.
-__global__ __launch_bounds__(256) void sigmoid_pairs_loss_kernel(const float* __restrict__ part, long n, float scale,
-                                                                 float* __restrict__ out, int accumulate) {
+// out[0] (+)= scale * sum part[0..n); single block, fixed order.  The last launch of the sigmoid loss and of the BCE loss.
+__global__ __launch_bounds__(256) void scaled_fold_kernel(const float* __restrict__ part, long n, float scale,
+                                                          float* __restrict__ out, int accumulate) {
   __shared__ float sh[16];
-  float s = 0.f;
-  for (long i = threadIdx.x; i < n; i += 256) s += part[i];
-  s = block_sum(s, sh);
+  const float s = block_fold(part, n, sh);
   if (threadIdx.x == 0) out[0] = accumulate ? out[0] + s * scale : s * scale;
 }
 
@@ -504,13 +501,6 @@ __global__ __launch_bounds__(256) void bce_posneg_kernel(const float* __restrict
   }
   ls = block_sum(ls, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = ls;
-}
-__global__ void scalar_reduce_kernel(const float* __restrict__ part, int n, float scale, float* __restrict__ out) {
-  __shared__ float sh[16];
-  float s = 0.f;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) s += part[i];
-  s = block_sum(s, sh);
-  if (threadIdx.x == 0) out[0] = s * scale;
 }
 
 // Trainer.val scoring: score = (pos+1)/2 or (pos-neg+2)/4; pred = argmax([neg,pos]) ; logit diff kept for the BCE log.
@@ -732,7 +722,7 @@ extern "C" int cxrk_sigmoid_pairs_fwd_bwd_inplace(float* C, long ld, int rows, i
 extern "C" int cxrk_sigmoid_pairs_loss(const float* partials, long n, float scale, float* loss_out, int accumulate,
                                        hipStream_t stream) {
   CXRK_CHECK_ARG(partials && n > 0 && loss_out);
-  hipLaunchKernelGGL(sigmoid_pairs_loss_kernel, dim3(1), dim3(256), 0, stream, partials, n, scale, loss_out, accumulate);
+  hipLaunchKernelGGL(scaled_fold_kernel, dim3(1), dim3(256), 0, stream, partials, n, scale, loss_out, accumulate);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }
@@ -821,7 +811,7 @@ extern "C" int cxrk_bce_posneg_fwd_bwd(const float* cosv, const float* labels, l
   long nb = (B * C + 255) / 256; if (nb > 256) nb = 256;
   hipLaunchKernelGGL(bce_posneg_kernel, dim3((unsigned)nb), dim3(256), 0, stream, cosv, labels, B, C, ldlab, diff, logits, dcos, ws);
   CXRK_LAUNCH_CHECK();
-  hipLaunchKernelGGL(scalar_reduce_kernel, dim3(1), dim3(256), 0, stream, ws, (int)nb, 1.0f / (float)(B * C), loss);
+  hipLaunchKernelGGL(scaled_fold_kernel, dim3(1), dim3(256), 0, stream, ws, nb, 1.0f / (float)(B * C), loss, 0);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }

@@ -6,6 +6,7 @@
 //  * Trainer.myIncremental (Trainer.py:1556-1587): per-tensor min/max of |new-old|, thresholded restore + counters
 #include "cxrk.h"
 #include "cxrk_common.h"
+#include "flat_buffers.h"
 
 using namespace cxrk;
 
@@ -48,43 +49,14 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 }
 
 // ---- global gradient norm + clipped, masked AdamW (include/cxrk.h, "grad_sqnorm" / "adamw_clipped") -------------------
-// The partition is a function of n alone (never of the device): nparts blocks of 256 threads, block b's thread t takes the float4
-// groups (b * 256 + t) + j * nparts * 256, j = 0, 1, ..., four of them in flight in four accumulators.
-constexpr int SQN_THREADS = 256;
-constexpr int SQN_UNROLL = 4;
-constexpr long SQN_MAX_PARTS = 1024;
-static inline long sqnorm_nparts(long n) {
-  long nb = (n / 4 + (long)SQN_THREADS * SQN_UNROLL - 1) / ((long)SQN_THREADS * SQN_UNROLL);
-  return nb < 1 ? 1 : (nb > SQN_MAX_PARTS ? SQN_MAX_PARTS : nb);
-}
-
-__global__ __launch_bounds__(SQN_THREADS) void grad_sqnorm_kernel(const float* __restrict__ g, long n, float* __restrict__ part) {
-  __shared__ float sh[16];
-  const long n4 = n >> 2;
-  const long stride = (long)gridDim.x * SQN_THREADS;
-  float acc[SQN_UNROLL];
-#pragma unroll
-  for (int k = 0; k < SQN_UNROLL; ++k) acc[k] = 0.f;
-  for (long i = (long)blockIdx.x * SQN_THREADS + threadIdx.x; i < n4; i += SQN_UNROLL * stride) {
-    float4 x[SQN_UNROLL];
-#pragma unroll
-    for (int k = 0; k < SQN_UNROLL; ++k)
-      x[k] = (i + k * stride < n4) ? reinterpret_cast<const float4*>(g)[i + k * stride] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int k = 0; k < SQN_UNROLL; ++k) {
-      acc[k] = fmaf(x[k].x, x[k].x, acc[k]); acc[k] = fmaf(x[k].y, x[k].y, acc[k]);
-      acc[k] = fmaf(x[k].z, x[k].z, acc[k]); acc[k] = fmaf(x[k].w, x[k].w, acc[k]);
-    }
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0)                       // the n % 4 elements behind the last whole group
-    for (long j = n4 * 4; j < n; ++j) acc[0] = fmaf(g[j], g[j], acc[0]);
-  const float s = block_sum((acc[0] + acc[1]) + (acc[2] + acc[3]), sh);
-  if (threadIdx.x == 0) part[blockIdx.x] = s;
+__global__ __launch_bounds__(FLAT_THREADS) void grad_sqnorm_kernel(const float* __restrict__ g, long n, float* __restrict__ part) {
+  const float* const in[1] = {g};
+  flat_reduce<1, false, 1>(in, nullptr, n, part, [](const float (&v)[1], float&, float (&s)[1]) { s[0] = fmaf(v[0], v[0], s[0]); });
 }
 
 // One launch over the flat buffers; adam_kernel's moment / parameter lines in adam_kernel's order, so that with coef = 1 and no
-// decay the result is adam_kernel's (weight_decay = 0) bit for bit.  Every block re-derives the squared norm from the partials in the
-// same fixed order (thread t takes partials t, t + 256, ..., then the block sum), as weight_reset_kernel re-derives its threshold.
+// decay the result is adam_kernel's (weight_decay = 0) bit for bit.  Every block re-derives the squared norm from the partials
+// (block_fold), as weight_reset_kernel re-derives its threshold.
 __global__ __launch_bounds__(256) void adamw_clipped_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                             float* __restrict__ v, const unsigned char* __restrict__ mask, long n,
                                                             float lr, float b1, float b2, float eps, float decay_factor, int decays,
@@ -96,9 +68,7 @@ __global__ __launch_bounds__(256) void adamw_clipped_kernel(float* __restrict__ 
   __shared__ float sh[16];
   float norm = 0.f, coef = 1.f;
   if (part != nullptr) {
-    float t = 0.f;
-    for (int i = threadIdx.x; i < nparts; i += 256) t += part[i];
-    norm = fabsf(grad_scale) * sqrtf(block_sum(t, sh));
+    norm = fabsf(grad_scale) * sqrtf(block_fold(part, nparts, sh));
     if (max_norm > 0.f) coef = min_keep_nan(max_norm / (norm + 1e-6f), 1.f);   // clip_grad_norm_'s constants; NaN norm -> NaN
   }
   if (stats != nullptr && blockIdx.x == 0 && threadIdx.x == 0) { stats[0] = norm; stats[1] = coef; }
@@ -192,20 +162,19 @@ extern "C" int cxrk_adam_fused(float* p, const float* g, float* m, float* v, lon
   CXRK_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v));
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  long nb = (n / 4 + 255) / 256; if (nb > 4096) nb = 4096; if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)nb), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
+  hipLaunchKernelGGL(adam_kernel, dim3(flat_blocks(n)), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps, weight_decay,
                      (float)bc1, (float)sqrt(bc2), grad_scale);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }
 
-extern "C" size_t cxrk_grad_sqnorm_partials_bytes(long n) { return n > 0 ? (size_t)sqnorm_nparts(n) * sizeof(float) : 0; }
+extern "C" size_t cxrk_grad_sqnorm_partials_bytes(long n) { return n > 0 ? (size_t)flat_nparts(n) * sizeof(float) : 0; }
 
 extern "C" int cxrk_grad_sqnorm(const float* g, long n, float* partials, size_t ws_bytes, hipStream_t stream) {
   CXRK_CHECK_ARG(g && n > 0 && aligned16(g));
-  const long nb = sqnorm_nparts(n);
+  const long nb = flat_nparts(n);
   if (partials == nullptr || ws_bytes < (size_t)nb * sizeof(float)) return CXRK_ERR_WS;
-  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)nb), dim3(SQN_THREADS), 0, stream, g, n, partials);
+  hipLaunchKernelGGL(grad_sqnorm_kernel, dim3((unsigned)nb), dim3(FLAT_THREADS), 0, stream, g, n, partials);
   CXRK_LAUNCH_CHECK();
   return CXRK_OK;
 }
@@ -216,13 +185,12 @@ extern "C" int cxrk_adamw_clipped(float* p, const float* g, float* m, float* v, 
   CXRK_CHECK_ARG(p && g && m && v && n > 0 && step >= 1);
   CXRK_CHECK_ARG(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v));
   CXRK_CHECK_ARG(partials != nullptr || !(max_norm > 0.f));     // clipping (or monitoring, max_norm = inf) needs the partial sums
-  const long np = sqnorm_nparts(n);
+  const long np = flat_nparts(n);
   if (partials != nullptr && ws_bytes < (size_t)np * sizeof(float)) return CXRK_ERR_WS;
   const double bc1 = 1.0 - pow((double)beta1, (double)step);
   const double bc2 = 1.0 - pow((double)beta2, (double)step);
   const float decay_factor = (float)(1.0 - (double)lr * (double)weight_decay);
-  long nb = (n / 4 + 255) / 256; if (nb > 4096) nb = 4096; if (nb < 1) nb = 1;
-  hipLaunchKernelGGL(adamw_clipped_kernel, dim3((unsigned)nb), dim3(256), 0, stream, p, g, m, v, decay_mask, n, lr, beta1, beta2, eps,
+  hipLaunchKernelGGL(adamw_clipped_kernel, dim3(flat_blocks(n)), dim3(256), 0, stream, p, g, m, v, decay_mask, n, lr, beta1, beta2, eps,
                      decay_factor, (int)(weight_decay != 0.f), (float)bc1, (float)sqrt(bc2), grad_scale, max_norm, partials, (int)np,
                      stats);
   CXRK_LAUNCH_CHECK();

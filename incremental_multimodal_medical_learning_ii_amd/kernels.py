@@ -1538,9 +1538,25 @@ def adam_fused(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale
                               float(weight_decay), int(step), float(grad_scale), _stream()), "cxrk_adam_fused")
 
 
-def grad_sqnorm_nparts(n: int) -> int:
-    """number of fp32 partial sums `grad_sqnorm` writes for n elements: a function of n alone (include/cxrk.h, "grad_sqnorm")"""
+def flat_nparts(n: int) -> int:
+    """number of blocks, and of fp32 partial sums per sum, of a reduction over a flat buffer of n elements (`grad_sqnorm`,
+    `ewc_penalty`, `agem_dots`): a function of n alone (csrc/flat_buffers.h)"""
     return _lib.load().cxrk_grad_sqnorm_partials_bytes(int(n)) // 4
+
+
+grad_sqnorm_nparts = ewc_penalty_nparts = agem_dots_nparts = flat_nparts
+
+
+def _partials_out(out: Optional[torch.Tensor], name: str, k: int, device):
+    """where a flat reduction writes its k partial sums: `out`, else the stream's workspace -> (buffer, its bytes); the sums are
+    its first k floats once the call has accepted it"""
+    if out is None:
+        ws = workspace(4 * k, device)
+    else:
+        ws = _chk(out, name + ".out")
+        if not out.is_contiguous():
+            raise ValueError(name + ".out: must be contiguous")
+    return ws, ws.numel() * 4
 
 
 def grad_sqnorm(g: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1551,17 +1567,10 @@ def grad_sqnorm(g: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     if g.dim() != 1 or not g.is_contiguous() or g.numel() == 0:
         raise ValueError("grad_sqnorm.g: expected a non-empty contiguous 1-D buffer")
     n = g.numel()
-    nbytes = lib.cxrk_grad_sqnorm_partials_bytes(n)
-    if out is None:
-        ws = workspace(nbytes, g.device)
-        ws_bytes = ws.numel() * 4
-    else:
-        ws = _chk(out, "grad_sqnorm.out")
-        if not out.is_contiguous():
-            raise ValueError("grad_sqnorm.out: must be contiguous")
-        ws_bytes = out.numel() * 4
+    k = flat_nparts(n)
+    ws, ws_bytes = _partials_out(out, "grad_sqnorm", k, g.device)
     check(lib.cxrk_grad_sqnorm(_p(g), n, _p(ws), ws_bytes, _stream()), "cxrk_grad_sqnorm")
-    return ws[:nbytes // 4]
+    return ws[:k]
 
 
 def adamw_clipped(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale: float = 1.0, max_norm: float = 0.0,
@@ -1622,11 +1631,6 @@ def ewc_consolidate(F: Optional[torch.Tensor], acc: Optional[torch.Tensor], anch
     check(lib.cxrk_ewc_consolidate(_p(F), _p(acc), _p(anchor), _p(p), n, float(gamma), float(scale), _stream()), "cxrk_ewc_consolidate")
 
 
-def ewc_penalty_nparts(n: int) -> int:
-    """number of fp32 partial sums `ewc_penalty` writes for n elements: `grad_sqnorm_nparts(n)` (include/cxrk.h, "ewc_penalty")"""
-    return _lib.load().cxrk_ewc_penalty_partials_bytes(int(n)) // 4
-
-
 def ewc_penalty(g: torch.Tensor, p: torch.Tensor, anchor: torch.Tensor, F: Optional[torch.Tensor], strength: float,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """g += strength * F * (p - anchor) in place, and the per-block partial sums of F * (p - anchor)^2 -> [nparts] (in `out`, else in
@@ -1638,23 +1642,10 @@ def ewc_penalty(g: torch.Tensor, p: torch.Tensor, anchor: torch.Tensor, F: Optio
     _flat(anchor, "ewc_penalty.anchor", n)
     if F is not None:
         _flat(F, "ewc_penalty.F", n)
-    nbytes = lib.cxrk_ewc_penalty_partials_bytes(n)
-    if out is None:
-        ws = workspace(nbytes, g.device)
-        ws_bytes = ws.numel() * 4
-    else:
-        ws = _chk(out, "ewc_penalty.out")
-        if not out.is_contiguous():
-            raise ValueError("ewc_penalty.out: must be contiguous")
-        ws_bytes = out.numel() * 4
+    k = flat_nparts(n)
+    ws, ws_bytes = _partials_out(out, "ewc_penalty", k, g.device)
     check(lib.cxrk_ewc_penalty(_p(g), _p(p), _p(anchor), _p(F), n, float(strength), _p(ws), ws_bytes, _stream()), "cxrk_ewc_penalty")
-    return ws[:nbytes // 4]
-
-
-def agem_dots_nparts(n: int) -> int:
-    """number of blocks of `agem_dots` for n elements, `grad_sqnorm_nparts(n)`: it writes 2 * nparts floats (include/cxrk.h,
-    "agem_dots")"""
-    return _lib.load().cxrk_agem_dots_partials_bytes(int(n)) // 8
+    return ws[:k]
 
 
 def agem_dots(g: torch.Tensor, gref: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1664,17 +1655,10 @@ def agem_dots(g: torch.Tensor, gref: torch.Tensor, out: Optional[torch.Tensor] =
     lib = _lib.load()
     n = _flat(g, "agem_dots.g").numel()
     _flat(gref, "agem_dots.gref", n)
-    nbytes = lib.cxrk_agem_dots_partials_bytes(n)
-    if out is None:
-        ws = workspace(nbytes, g.device)
-        ws_bytes = ws.numel() * 4
-    else:
-        ws = _chk(out, "agem_dots.out")
-        if not out.is_contiguous():
-            raise ValueError("agem_dots.out: must be contiguous")
-        ws_bytes = out.numel() * 4
+    k = 2 * flat_nparts(n)
+    ws, ws_bytes = _partials_out(out, "agem_dots", k, g.device)
     check(lib.cxrk_agem_dots(_p(g), _p(gref), n, _p(ws), ws_bytes, _stream()), "cxrk_agem_dots")
-    return ws[:nbytes // 4]
+    return ws[:k]
 
 
 def agem_project(g: torch.Tensor, gref: torch.Tensor, partials: torch.Tensor, stats: torch.Tensor) -> None:
@@ -1685,9 +1669,8 @@ def agem_project(g: torch.Tensor, gref: torch.Tensor, partials: torch.Tensor, st
     n = _flat(g, "agem_project.g").numel()
     _flat(gref, "agem_project.gref", n)
     _chk(partials, "agem_project.partials")
-    if not partials.is_contiguous() or partials.numel() * 4 != lib.cxrk_agem_dots_partials_bytes(n):
-        raise ValueError(f"agem_project.partials: must be the {lib.cxrk_agem_dots_partials_bytes(n) // 4} contiguous floats of "
-                         f"agem_dots for {n} elements")
+    if not partials.is_contiguous() or partials.numel() != 2 * flat_nparts(n):
+        raise ValueError(f"agem_project.partials: must be the {2 * flat_nparts(n)} contiguous floats of agem_dots for {n} elements")
     _chk(stats, "agem_project.stats")
     if not stats.is_contiguous() or stats.numel() != 4:
         raise ValueError("agem_project.stats: must be 4 contiguous floats")

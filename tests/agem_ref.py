@@ -9,20 +9,10 @@ from ewc_ref import U, block_of, f32, gamma_k  # noqa: F401
 
 
 # ---- the two kernels in float64 -----------------------------------------------------------------------------------------------
-def _by_block(x: np.ndarray, nparts: int) -> np.ndarray:
-    """float64 sums of x over the kernel's partition (grad_sqnorm's): group i of four elements belongs to block
-    (i mod (nparts * 256)) div 256; the n mod 4 tail to block 0"""
-    n4 = x.size // 4
-    out = np.zeros(nparts, dtype=np.float64)
-    np.add.at(out, (np.arange(n4) % (nparts * 256)) // 256, x[:4 * n4].reshape(n4, 4).sum(1))
-    out[0] += x[4 * n4:].sum()
-    return out
-
-
 def dots_partials(g, gref, nparts: int):
-    """(shares of sum g * gref, shares of sum gref^2, shares of sum |g * gref|) per block, float64"""
+    """(shares of sum g * gref, shares of sum gref^2, shares of sum |g * gref|) per block of the kernel's partition, float64"""
     gd, rd = g.double().numpy(), gref.double().numpy()
-    return _by_block(gd * rd, nparts), _by_block(rd * rd, nparts), _by_block(np.abs(gd * rd), nparts)
+    return R.by_block(gd * rd, nparts), R.by_block(rd * rd, nparts), R.by_block(np.abs(gd * rd), nparts)
 
 
 def dots(g, gref):

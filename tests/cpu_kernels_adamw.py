@@ -13,22 +13,30 @@ def grad_sqnorm_nparts(n: int) -> int:
     return min(1024, max(1, -(-(n // 4) // 1024)))
 
 
-def grad_sqnorm(g, out=None):
-    n = g.numel()
-    nparts = grad_sqnorm_nparts(n)
-    if out is not None and out.numel() < nparts:
-        raise RuntimeError("cxrk_grad_sqnorm: workspace too small (cxrk code -2)")
-    n4 = n // 4
-    sq = g.detach().float() ** 2
+def by_block(terms, nparts):
+    """fp32 sums of per-element terms over the partition of the flat reductions (the module's docstring)"""
+    n4 = terms.numel() // 4
     part = torch.zeros(nparts, dtype=torch.float32)
     if n4:
         block = (torch.arange(n4) % (nparts * 256)) // 256
-        part.index_add_(0, block, sq[:4 * n4].view(n4, 4).sum(1))
-    part[0] += sq[4 * n4:].sum()
+        part.index_add_(0, block, terms[:4 * n4].view(n4, 4).sum(1))
+    part[0] += terms[4 * n4:].sum()
+    return part
+
+
+def partials_out(part, out):
+    """the partial sums where the kernel leaves them: at the front of `out` when given"""
     if out is None:
         return part
-    out[:nparts].copy_(part)
-    return out[:nparts]
+    out[:part.numel()].copy_(part)
+    return out[:part.numel()]
+
+
+def grad_sqnorm(g, out=None):
+    nparts = grad_sqnorm_nparts(g.numel())
+    if out is not None and out.numel() < nparts:
+        raise RuntimeError("cxrk_grad_sqnorm: workspace too small (cxrk code -2)")
+    return partials_out(by_block(g.detach().float() ** 2, nparts), out)
 
 
 def adamw_clipped(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, max_norm=0.0, decay_mask=None, partials=None,

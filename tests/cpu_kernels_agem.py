@@ -1,27 +1,16 @@
 """TEST-ONLY: tests/cpu_kernels_ewc.py plus torch emulations of `kernels.agem_dots` and `kernels.agem_project`, so that `optim.AGEM`
-runs on gloo / CPU.  fp32, the kernels' formulas and partition (grad_sqnorm's: block b holds the groups of four i with
-(i mod (nparts * 256)) div 256 == b, the n mod 4 tail goes to block 0; include/cxrk.h, "agem_dots"); the order of the additions inside
-a block is torch's.  Never imported by the package."""
+runs on gloo / CPU.  fp32, the kernels' formulas and partition (`cpu_kernels_adamw.by_block`; include/cxrk.h, "agem_dots"); the order
+of the additions inside a block is torch's.  Never imported by the package."""
 import torch
 
 from cpu_kernels_ewc import *  # noqa: F401,F403
-from cpu_kernels_ewc import grad_sqnorm_nparts
+from cpu_kernels_ewc import by_block, grad_sqnorm_nparts, partials_out
 
 _BAD = "bad argument / shape / alignment (cxrk code -1)"
 
 
 def agem_dots_nparts(n: int) -> int:
     return grad_sqnorm_nparts(n)
-
-
-def _by_block(terms, nparts):
-    n4 = terms.numel() // 4
-    part = torch.zeros(nparts, dtype=torch.float32)
-    if n4:
-        block = (torch.arange(n4) % (nparts * 256)) // 256
-        part.index_add_(0, block, terms[:4 * n4].view(n4, 4).sum(1))
-    part[0] += terms[4 * n4:].sum()
-    return part
 
 
 def agem_dots(g, gref, out=None):
@@ -32,11 +21,7 @@ def agem_dots(g, gref, out=None):
     if out is not None and out.numel() < 2 * nparts:
         raise RuntimeError("cxrk_agem_dots: workspace too small (cxrk code -2)")
     with torch.no_grad():
-        part = torch.cat([_by_block(g * gref, nparts), _by_block(gref * gref, nparts)])
-    if out is None:
-        return part
-    out[:2 * nparts].copy_(part)
-    return out[:2 * nparts]
+        return partials_out(torch.cat([by_block(g * gref, nparts), by_block(gref * gref, nparts)]), out)
 
 
 def agem_project(g, gref, partials, stats):

@@ -1,11 +1,11 @@
 """TEST-ONLY: tests/cpu_kernels_adamw.py plus torch emulations of `kernels.fisher_accumulate`, `kernels.ewc_consolidate`,
 `kernels.ewc_penalty` and `kernels.sgd`, so that `optim.EWC` runs on gloo / CPU.  fp32, the kernels' formulas and the penalty's
-partition (grad_sqnorm's: block b holds the groups of four i with (i mod (nparts * 256)) div 256 == b, the n mod 4 tail goes to block
-0; include/cxrk.h, "ewc_penalty"); the order of the additions inside a block is torch's.  Never imported by the package."""
+partition (`cpu_kernels_adamw.by_block`; include/cxrk.h, "ewc_penalty"); the order of the additions inside a block is torch's.  Never
+imported by the package."""
 import torch
 
 from cpu_kernels_adamw import *  # noqa: F401,F403
-from cpu_kernels_adamw import grad_sqnorm_nparts
+from cpu_kernels_adamw import by_block, grad_sqnorm_nparts, partials_out
 
 _BAD = "bad argument / shape / alignment (cxrk code -1)"
 
@@ -45,17 +45,7 @@ def ewc_penalty(g, p, anchor, F, strength, out=None):
         d = p - anchor
         t = d if F is None else F * d
         g.add_(_f(strength) * t)
-        terms = t * d
-    n4 = n // 4
-    part = torch.zeros(nparts, dtype=torch.float32)
-    if n4:
-        block = (torch.arange(n4) % (nparts * 256)) // 256
-        part.index_add_(0, block, terms[:4 * n4].view(n4, 4).sum(1))
-    part[0] += terms[4 * n4:].sum()
-    if out is None:
-        return part
-    out[:nparts].copy_(part)
-    return out[:nparts]
+        return partials_out(by_block(t * d, nparts), out)
 
 
 def sgd(p, g, lr, weight_decay=0.0, grad_scale=1.0):

@@ -48,16 +48,8 @@ def penalty_terms(p, anchor, F):
 
 
 def penalty_partials(p, anchor, F, nparts: int) -> np.ndarray:
-    """float64 partial sums of the terms over the kernel's partition (grad_sqnorm's): group i of four elements belongs to block
-    (i mod (nparts * 256)) div 256; the n mod 4 tail to block 0"""
-    x = penalty_terms(p, anchor, F).numpy()
-    n4 = x.size // 4
-    per_group = x[:4 * n4].reshape(n4, 4).sum(1)
-    block = (np.arange(n4) % (nparts * 256)) // 256
-    out = np.zeros(nparts, dtype=np.float64)
-    np.add.at(out, block, per_group)
-    out[0] += x[4 * n4:].sum()
-    return out
+    """float64 partial sums of the terms over the kernel's partition (`optim_ref.by_block`)"""
+    return R.by_block(penalty_terms(p, anchor, F).numpy(), nparts)
 
 
 def block_of(i: int, n: int, nparts: int) -> int:

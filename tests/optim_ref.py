@@ -3,7 +3,18 @@ gradient norm, `torch.nn.utils.clip_grad_norm_`'s coefficient, `torch.optim.Adam
 closed form of `optim.LRSchedule`.  tests/test_adamw_host.py pins it to torch; the GPU tests compare the kernels with it."""
 import math
 
+import numpy as np
 import torch
+
+
+def by_block(terms: np.ndarray, nparts: int) -> np.ndarray:
+    """float64 sums of per-element terms over the partition of the flat reductions (grad_sqnorm, ewc_penalty, agem_dots): group i of
+    four elements belongs to block (i mod (nparts * 256)) div 256; the n mod 4 tail to block 0"""
+    n4 = terms.size // 4
+    out = np.zeros(nparts, dtype=np.float64)
+    np.add.at(out, (np.arange(n4) % (nparts * 256)) // 256, terms[:4 * n4].reshape(n4, 4).sum(1))
+    out[0] += terms[4 * n4:].sum()
+    return out
 
 
 def grad_norm(g: torch.Tensor, grad_scale: float = 1.0) -> float:

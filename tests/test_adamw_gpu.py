@@ -49,16 +49,8 @@ def bits(t):
 
 
 def partials_ref(g: torch.Tensor, nparts: int) -> np.ndarray:
-    """float64 partial sums over the kernel's partition: group i of four elements belongs to block (i mod (nparts * 256)) div 256;
-    the n mod 4 tail to block 0"""
-    x = g.double().numpy() ** 2
-    n4 = x.size // 4
-    per_group = x[:4 * n4].reshape(n4, 4).sum(1)
-    block = (np.arange(n4) % (nparts * 256)) // 256
-    out = np.zeros(nparts, dtype=np.float64)
-    np.add.at(out, block, per_group)
-    out[0] += x[4 * n4:].sum()
-    return out
+    """float64 partial sums of g^2 over the kernel's partition (`optim_ref.by_block`)"""
+    return R.by_block(g.double().numpy() ** 2, nparts)
 
 
 # ------------------------------------------------------------------------------------------------ the norm kernel
