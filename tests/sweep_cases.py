@@ -2,7 +2,9 @@
 (tests/test_sweep_host.py on the CPU, tests/test_sweep_gpu.py on the GPU).
 
   cases(family)            the frozen-dataclass cases of family "A" (attention), "B32" / "BPL" (dense GEMM on fp32 / planes operands),
-                           "C" (column reductions), "D" (row-wise heads); a pure function of (SEED, family, index)
+                           "C" (column reductions), "D" (row-wise heads), "E" (BERT row kernels: LayerNorm, embedding, gelu',
+                           planes_add_rows), "F" (image-side non-GEMM kernels: max-pool, layout, spatial mean, BatchNorm folding, the
+                           train-mode BatchNorm chain); a pure function of (SEED, family, index)
   legal(case)              the rules the entry points check (include/cxrk.h), restated; every generated case satisfies them
   build(case)              CPU inputs (float32; masks int64, decision bits uint8, winners int32)
   evaluate(case, inp, dt)  the operation's defining formula in torch on the CPU in dtype `dt`
@@ -23,6 +25,10 @@ planes output 2^-16 |ref| (exact_ref.assert_two_roundings, statement 1).  Attent
 floors (2e-5 forward, 5e-5 backward, 1e-6 column means, 3e-4 planes / split mode) per row or per column, or 8 e32 where that is
 larger: e32 is the same comparator on evaluate(..., float32) -- torch on the CPU, never a kernel -- maximised over the family's
 cases of one (output group, profile); the table E32 below is pinned from both sides by tests/test_sweep_host.py.
+E and F: copies, maxima and winning taps bit for bit; sums of a few terms elementwise against a derived multiple of 2^-24 on the
+magnitudes of their terms (max-pool backward 3: at most four terms; embedding gradient count + 2; planes_add_rows 2; spatial mean P + 2,
+its backward 3: fl(1 / P), the product, the optional addition); gelu' as in the GEMM epilogue; everything else per row or per column
+against max(floor, 8 e32) as above.
 
 No GPU and no library import here."""
 from __future__ import annotations
@@ -36,7 +42,7 @@ from typing import Dict, List, Tuple
 import torch
 
 SEED = 20261020
-NCASES = {"A": 105, "B32": 96, "BPL": 96, "C": 104, "D": 112}
+NCASES = {"A": 105, "B32": 96, "BPL": 96, "C": 104, "D": 112, "E": 111, "F": 102}
 FLOOR_REL = 1e-3     # a row / column below 1e-3 of its tensor's scale is judged as if it were at 1e-3 (today's metric judges it at 1)
 U24 = 2.0 ** -24
 ERF_TOL = 2.0 ** -16      # test_gelu_epilogue_writers (exact_ref.assert_two_roundings): what the library promises around erf
@@ -753,8 +759,523 @@ def _eval_d(c: HeadCase, inp, dt):
             "din": (inp["dout"].to(dt) / c.n)[:, None].expand(c.rows, c.n, c.cols).reshape(c.rows * c.n, c.cols)}
 
 
+# ================================================================================================================ family E
+E_LN_H = (4, 8, 60, 64, 72, 100, 128, 256, 504, 512, 520, 768, 1016, 1023, 1024)
+E_LNF_ROWS = (1, 3, 4, 5, 17, 257, 4099)
+E_LNB_ROWS = (1, 15, 16, 17, 255, 16383, 16385, 16400)      # from 16383 on with H <= 128 only
+E_EPS = (1e-12, 1e-5)
+E_LN_PROFILES = ("randn", "row_offset", "row_scale", "outlier", "near_constant")
+E_EMB_L, E_EMB_H = (1, 7, 32, 512), (8, 100, 768)
+E_EB_T, E_EB_H = (1, 31, 32, 33, 63, 64, 65, 1025, 4099), (1, 8, 72, 257, 768)
+E_EB_PATTERNS = ("one", "distinct", "zipf", "chunk_aligned", "long_then_split")
+E_GELU_N = (1, 255, 256, 257, 65537)
+E_ADD_ROWS, E_ADD_COLS, E_ADD_PAD = (1, 5, 8200), (8, 136, 512), (0, 4, 520)
+E_COUNTS = (("ln_fwd", 30), ("ln_bwd", 32), ("embed_ln_fwd", 8), ("embed_bwd", 27), ("gelu_bwd", 5), ("planes_add_rows", 9))
+EMBED_CH = 32              # sorted entries per chunk of the embedding gradient (csrc/embed.hip)
+ADD_ROWS_CAP = 2048        # blocks of 256 threads, 8 columns each (csrc/bert.hip cxrk_planes_add_rows)
+
+
+@dataclass(frozen=True)
+class RowCase:
+    index: int
+    op: str                 # ln_fwd, ln_bwd, embed_ln_fwd, embed_bwd, gelu_bwd, planes_add_rows
+    rows: int = 1           # LayerNorm rows / tokens T / gelu n / add_rows rows
+    H: int = 8              # LayerNorm and embedding width / add_rows cols
+    eps: float = 1e-12
+    res: bool = False       # ln_fwd: a residual; ln_bwd: dx_add
+    accumulate: bool = False
+    dxsum: str = "none"     # ln_bwd: "none", "fresh", "acc"
+    planes: bool = False    # ln_bwd: dx written as planes (the forward writes both forms wherever the planes form is legal)
+    L: int = 1              # embed_ln_fwd: positions
+    V: int = 1              # embedding rows
+    pattern: str = ""       # embed_bwd
+    pad: int = 0            # planes_add_rows: ld - cols
+    profile: str = "base"
+
+
+def _op_of(counts, i: int):
+    for op, cnt in counts:
+        if i < cnt:
+            return op, i
+        i -= cnt
+    raise IndexError(i)
+
+
+def _gen_e(i: int, sched: Schedule) -> RowCase:
+    op, k = _op_of(E_COUNTS, i)
+    S = lambda dim, strata: sched(op + "." + dim, strata)      # noqa: E731
+    if op == "ln_fwd":
+        return RowCase(i, op, rows=S("rows", E_LNF_ROWS), H=S("H", E_LN_H), eps=S("eps", E_EPS), res=S("res", (True, False)),
+                       profile=S("profile", E_LN_PROFILES))
+    if op == "ln_bwd":
+        rows = S("rows", E_LNB_ROWS)
+        H = S("H", E_LN_H if rows < 16383 else [h for h in E_LN_H if h <= 128])
+        vec = H % 4 == 0                                          # bert.hip ln_bwd_vec_ok: planes and dxsum need the float4 kernel
+        return RowCase(i, op, rows=rows, H=H, res=S("dx_add", (False, True)), accumulate=S("accumulate", (True, False)),
+                       dxsum=S("dxsum", ("none", "fresh", "acc")) if vec else "none", planes=S("planes", (False, True)) if vec else False,
+                       profile=S("profile", E_LN_PROFILES))
+    if op == "embed_ln_fwd":
+        L, H = S("L", E_EMB_L), S("H", E_EMB_H)
+        whole = S("whole", (True, False))
+        r = _rng("E." + op, k)
+        T = L * r.randint(1, max(1, 600 // L)) + (0 if whole else r.randint(1, max(1, L - 1)))
+        if L == 7 and whole:
+            T = 14                                                # a last block of two rows: two idle waves
+        return RowCase(i, op, rows=T, H=H, L=L, V=r.randint(2, 300))
+    if op == "embed_bwd":
+        T = S("T", E_EB_T)
+        pattern = S("pattern", E_EB_PATTERNS if T > 100 else E_EB_PATTERNS[:4])      # >= 3 chunks and a split chunk need T > 96
+        return RowCase(i, op, rows=T, H=S("H", E_EB_H), V=T + 7, pattern=pattern)
+    if op == "gelu_bwd":
+        return RowCase(i, op, rows=S("n", E_GELU_N))
+    return RowCase(i, op, rows=E_ADD_ROWS[k % 3], H=E_ADD_COLS[k // 3], pad=S("pad", E_ADD_PAD))      # every rows x cols pair
+
+
+def _legal_e(c: RowCase) -> bool:
+    if c.op in ("ln_fwd", "embed_ln_fwd"):       # bert.hip:872,881 (planes output: the vec8 kernel, H % 8 == 0)
+        return c.rows > 0 and 0 < c.H <= 1024 and c.L > 0 and c.V > 0
+    if c.op == "ln_bwd":                         # bert.hip:928,931
+        ok = c.rows > 0 and 0 < c.H <= 1024 and c.dxsum in ("none", "fresh", "acc")
+        return ok and (c.H % 4 == 0 or (not c.planes and c.dxsum == "none")) and (c.rows < 16383 or c.H <= 128)
+    if c.op == "embed_bwd":                      # embed.hip:100
+        return 0 < c.rows < (1 << 31) and c.H > 0 and c.V > 0
+    if c.op == "gelu_bwd":                       # bert.hip:838
+        return c.rows > 0
+    return c.rows > 0 and c.H > 0 and c.H % 8 == 0 and (c.H + c.pad) % 4 == 0 and (c.rows * c.H) % 8 == 0      # bert.hip:829
+
+
+def ln_bwd_launch(rows: int) -> Tuple[int, int, int]:
+    """(blocks asked for, rows per block, blocks launched) of the LayerNorm backward (csrc/bert.hip ln_bwd_blocks, launch_ln_bwd)"""
+    nb0 = max(1, min(1024, (rows + 15) // 16))
+    rows_per = -(-rows // nb0)
+    return nb0, rows_per, -(-rows // rows_per)
+
+
+def _ln_values(c: RowCase, g) -> torch.Tensor:
+    x = _randn(g, c.rows, c.H)
+    if c.profile == "row_offset":
+        sign = torch.where(torch.rand(c.rows, generator=g) < 0.5, -1.0, 1.0)
+        x = x + (sign * 10.0 ** (1.0 + 2.0 * torch.rand(c.rows, generator=g)))[:, None]
+    elif c.profile == "row_scale":
+        x = x * (10.0 ** (torch.rand(c.rows, generator=g) * 8.0 - 4.0))[:, None]
+    elif c.profile == "outlier":
+        x[torch.arange(c.rows), torch.randint(0, c.H, (c.rows,), generator=g)] *= 1e4
+    elif c.profile == "near_constant":
+        x = 1.0 + 1e-3 * x
+    return x
+
+
+def _ln_stats(x, eps: float):
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    rstd = 1.0 / torch.sqrt((d * d).mean(-1, keepdim=True) + eps)
+    return d * rstd, rstd
+
+
+def embed_ids(c: RowCase) -> torch.Tensor:
+    """int64 ids [T] of an embed_bwd case; the runs of the list sorted by (id, position) are what the patterns shape"""
+    r = _rng("E.ids", c.index)
+    T, V = c.rows, c.V
+    if c.pattern == "one":
+        return torch.full((T,), r.randrange(V), dtype=torch.int64)
+    if c.pattern == "distinct":
+        return torch.tensor(r.sample(range(V), T), dtype=torch.int64)
+    if c.pattern == "zipf":
+        ids = [min(V - 1, int(r.paretovariate(1.1)) - 1) for _ in range(T)]
+        ids[r.randrange(T)] = 0
+        if T > 1:
+            ids[r.randrange(T)] = V - 1
+        return torch.tensor(ids, dtype=torch.int64)
+    if c.pattern == "chunk_aligned":
+        runs, left = [], T
+        while left > 0:
+            n = min(left, EMBED_CH * r.randint(1, 3))
+            runs.append(n)
+            left -= n
+    else:      # long_then_split: a run over chunks 0, 1, 2 that ends inside chunk 2, whose rest is one second run; then the same
+        runs, left = [], T      # motif again behind a short run, then short runs
+        for n in (70 + r.randint(0, 20), 40, 3, 2 * EMBED_CH + r.randint(5, 25), 60):
+            if left >= n:
+                runs.append(n)
+                left -= n
+        while left > 0:
+            n = min(left, r.randint(1, 40))
+            runs.append(n)
+            left -= n
+    vals = sorted(r.sample(range(V), len(runs)))
+    pos = list(range(T))
+    r.shuffle(pos)
+    ids = torch.empty(T, dtype=torch.int64)
+    at = 0
+    for v, n in zip(vals, runs):      # ascending ids over ascending runs: the sorted list has exactly these runs, in this order
+        ids[torch.tensor(pos[at:at + n])] = v
+        at += n
+    return ids
+
+
+def embed_chunks(ids: torch.Tensor):
+    """(runs per chunk of the sorted list, chunks the longest boundary-finished run covers): the host view of csrc/embed.hip"""
+    s = sorted(ids.tolist())
+    chunks = [s[i:i + EMBED_CH] for i in range(0, len(s), EMBED_CH)]
+    nruns = [len(set(ch)) for ch in chunks]
+    span = {}
+    for k, ch in enumerate(chunks):
+        for v in set(ch):
+            span.setdefault(v, set()).add(k)
+    return nruns, max(len(v) for v in span.values())
+
+
+def _build_e(c: RowCase):
+    g = _gen("E", c.index)
+    if c.op == "ln_fwd":
+        inp = {"x": _ln_values(c, g), "gamma": 1.0 + 0.5 * _randn(g, c.H), "beta": _randn(g, c.H)}
+        if c.res:      # the two summands cancel to the profile's values: the sum the kernel forms is what is normalised
+            inp["res"] = _randn(g, c.rows, c.H) * inp["x"].abs().amax(1, keepdim=True).clamp_min(1e-30) * 0.5
+            inp["x"] = inp["x"] - inp["res"]
+        return inp
+    if c.op == "ln_bwd":
+        xhat, rstd = _ln_stats(_ln_values(c, g).double(), c.eps)
+        inp = {"dy": _randn(g, c.rows, c.H), "xhat": xhat.float(), "rstd": rstd.float().reshape(-1), "gamma": 1.0 + 0.5 * _randn(g, c.H)}
+        if c.res:
+            inp["dx_add"] = _randn(g, c.rows, c.H) * inp["rstd"][:, None]
+        if c.accumulate:
+            inp["dgamma0"], inp["dbeta0"] = _randn(g, c.H) * math.sqrt(c.rows), _randn(g, c.H) * math.sqrt(c.rows)
+        if c.dxsum == "acc":
+            inp["dxsum0"] = _randn(g, c.H) * float(inp["rstd"].max()) * math.sqrt(c.rows)
+        return inp
+    if c.op == "embed_ln_fwd":
+        ids = torch.randint(0, c.V, (c.rows,), generator=g)
+        ids[0], ids[-1] = 0, c.V - 1
+        if c.rows == 1:
+            ids[0] = c.V - 1
+        return {"ids": ids, "word": _randn(g, c.V, c.H), "pos": _randn(g, c.L, c.H), "type": _randn(g, c.H), "gamma": 1.0 + 0.5 * _randn(g, c.H),
+                "beta": _randn(g, c.H)}
+    if c.op == "embed_bwd":
+        return {"ids": embed_ids(c), "dx": _randn(g, c.rows, c.H), "dword0": _randn(g, c.V, c.H)}
+    if c.op == "gelu_bwd":
+        pre = torch.linspace(-12.0, 12.0, c.rows)[torch.randperm(c.rows, generator=g)] + 0.01 * _randn(g, c.rows)
+        return {"pre": pre if c.rows > 1 else torch.tensor([0.7]), "dy": _randn(g, c.rows)}
+    return {"src": _randn(g, c.rows, c.H), "dst0": _randn(g, c.rows, c.H) * 3.0}
+
+
+def _eval_e(c: RowCase, inp, dt, rows_used=None):
+    if c.op in ("ln_fwd", "embed_ln_fwd"):
+        if c.op == "ln_fwd":
+            x = inp["x"].to(dt) + (inp["res"].to(dt) if c.res else 0.0)
+        else:
+            x = inp["word"].to(dt)[inp["ids"]] + inp["pos"].to(dt)[torch.arange(c.rows) % c.L] + inp["type"].to(dt)
+        xhat, rstd = _ln_stats(x, c.eps)
+        return {"y": xhat * inp["gamma"].to(dt) + inp["beta"].to(dt), "xhat": xhat, "rstd": rstd}
+    if c.op == "ln_bwd":
+        dy, xhat, rstd = inp["dy"].to(dt), inp["xhat"].to(dt), inp["rstd"].to(dt)[:, None]
+        gy = dy * inp["gamma"].to(dt)
+        dx = rstd * (gy - gy.mean(1, keepdim=True) - xhat * (gy * xhat).mean(1, keepdim=True))
+        if c.res:
+            dx = dx + inp["dx_add"].to(dt)
+        u = slice(0, rows_used)
+        out = {"dx": dx, "dgamma": (dy * xhat)[u].sum(0), "dbeta": dy[u].sum(0)}
+        if c.accumulate:
+            out["dgamma"], out["dbeta"] = out["dgamma"] + inp["dgamma0"].to(dt), out["dbeta"] + inp["dbeta0"].to(dt)
+        if c.dxsum != "none":
+            out["dxsum"] = dx[u].sum(0) + (inp["dxsum0"].to(dt) if c.dxsum == "acc" else 0.0)
+        return out
+    if c.op == "embed_bwd":
+        base, dx, ids = inp["dword0"].to(dt), inp["dx"].to(dt), inp["ids"]
+        count = torch.zeros(c.V, dtype=torch.float64).index_add_(0, ids, torch.ones(c.rows, dtype=torch.float64))
+        mag = base.abs().double().index_add(0, ids, dx.abs().double())
+        return {"dword": base.index_add(0, ids, dx), "mag:dword": (count[:, None] + 2.0) * U24 * mag}
+    if c.op == "gelu_bwd":
+        dy = inp["dy"].to(dt)
+        ref = dy * _gelu_grad(inp["pre"].to(dt))
+        return {"dx": ref, "mag:dx": ERF_TOL * dy.abs().double() + 2.0 * U24 * ref.abs().double()}
+    src, dst = _seen(None, inp["src"], True, dt), inp["dst0"].to(dt)
+    return {"dst": dst + src, "mag:dst": 2.0 * U24 * (dst.abs() + src.abs()).double()}
+
+
+# ================================================================================================================ family F
+F_POOL_HW, F_POOL_N, F_POOL_C = (1, 2, 3, 4, 7, 8, 13, 16, 17), (1, 2), (4, 8, 24, 64, 136)
+F_POOL_PROFILES = ("randn", "relu", "constant", "negative")
+F_LAY_C, F_LAY_PAD = (1, 3, 4, 5), ("C", "4", "8")
+F_LAY_PAIRS = tuple((C, Cp) for C in F_LAY_C for Cp in sorted({C, 4, 8}) if Cp >= C)      # every (C, Cpad) there is: ten
+F_SM_P, F_SM_C = (1, 2, 49, 50, 256, 1025), (1, 8, 130, 136, 2048)
+F_FOLD_TAPS, F_FOLD_C, F_FOLD_KO = (1, 9, 49), ((3, 4), (3, 8), (64, 64), (60, 64)), (1, 5, 64)
+F_BN_ROWS, F_BN_C = (1, 2, 3, 16, 257, 4097), (8, 24, 136, 1024)
+F_BN_RES, F_BN_RELU, F_BN_MOM, F_BN_RATIO = ("none", "f32", "pl"), ("none", "relu", "mask"), (0.0, 0.1), (0, 30, 300, 3000)
+F_COUNTS = (("maxpool", 36), ("layout", len(F_LAY_PAIRS)), ("spatial_mean", 12), ("bn_fold", 8), ("bn_train", 36))
+BN_EPS = 1e-5
+BN_GRID_CAP = 16384        # blocks of 256 threads, 8 columns each, of bn_apply and bn_train_dz (csrc/bn_train.hip grid_for)
+
+
+@dataclass(frozen=True)
+class ImgCase:
+    index: int
+    op: str                 # maxpool (forward and backward, fp32 and planes), layout (both transforms), spatial_mean, bn_fold, bn_train
+    N: int = 1
+    H: int = 1
+    W: int = 1
+    C: int = 8
+    Cpad: int = 0           # layout, bn_fold
+    relu: str = "none"      # maxpool: "mask" = relu_mask of the fp32 backward; bn_train: "none", "relu", "mask" (ReLU with decision bits)
+    P: int = 1              # spatial_mean pixels
+    add: bool = False       # spatial_mean_bwd_pl
+    taps: int = 1           # bn_fold
+    Ko: int = 1
+    rows: int = 1           # bn_train
+    planes: bool = False    # bn_train: z, dy, y, dz in planes storage
+    residual: str = "none"  # bn_train: "none", "f32", "pl"
+    momentum: float = 0.0
+    running: bool = False
+    accumulate: bool = False
+    profile: str = "base"   # maxpool profile; bn_train: "offset<|mean| / std>"
+
+
+def _gen_f(i: int, sched: Schedule) -> ImgCase:
+    op, k = _op_of(F_COUNTS, i)
+    S = lambda dim, strata: sched(op + "." + dim, strata)      # noqa: E731
+    r = _rng("F." + op, k)
+    if op == "maxpool":
+        return ImgCase(i, op, N=S("N", F_POOL_N), H=S("H", F_POOL_HW), W=S("W", F_POOL_HW), C=S("C", F_POOL_C),
+                       relu=S("relu_mask", ("mask", "none")), profile=S("profile", F_POOL_PROFILES))
+    if op == "layout":
+        C, Cpad = F_LAY_PAIRS[k]
+        H = r.randint(1, 19)
+        return ImgCase(i, op, N=r.randint(1, 3), H=H, W=r.choice([w for w in range(1, 300) if w != H]), C=C, Cpad=Cpad)
+    if op == "spatial_mean":
+        P, C = S("P", F_SM_P), S("C", F_SM_C)
+        return ImgCase(i, op, N=min(r.randint(1, 3), max(1, C_MAX_BYTES // (9 * P * C))), P=P, C=C, add=S("add", (True, False)))      # x and add
+    if op == "bn_fold":
+        C, Cpad = S("C", F_FOLD_C)
+        return ImgCase(i, op, C=C, Cpad=Cpad, taps=S("taps", F_FOLD_TAPS), Ko=S("Ko", F_FOLD_KO))
+    planes, rows = S("planes", (False, True)), S("rows", F_BN_ROWS)
+    C = S("C", [v for v in F_BN_C if 13 * rows * v <= C_MAX_BYTES])      # z, dy and the residual, 4 bytes each, and the vectors
+    return ImgCase(i, op, rows=rows, C=C, planes=planes, residual=S("residual", F_BN_RES), relu=S("relu", F_BN_RELU),
+                   momentum=S("momentum", F_BN_MOM), running=S("running", (True, False)), accumulate=S("accumulate", (False, True)),
+                   profile=f"offset{S('ratio', F_BN_RATIO)}")
+
+
+def _legal_f(c: ImgCase) -> bool:
+    if c.op == "maxpool":                        # conv_misc.hip:293,302 (fp32: C % 4; the planes kernels, :312,323, run where C % 8 == 0)
+        return c.N > 0 and c.H > 0 and c.W > 0 and c.C % 4 == 0
+    if c.op == "layout":                         # conv_misc.hip:280,286
+        return c.N > 0 and c.C > 0 and c.Cpad >= c.C
+    if c.op == "spatial_mean":                   # conv_misc.hip:333,339 (the planes backward, :346, runs where C % 8 == 0)
+        return c.N > 0 and c.P > 0 and c.C > 0
+    if c.op == "bn_fold":                        # conv_misc.hip:261 (the planes form, :271, runs where Cpad % 8 == 0)
+        return c.Ko > 0 and c.taps > 0 and c.C > 0 and c.Cpad >= c.C
+    ok = c.rows > 0 and c.C > 0 and c.C % 8 == 0                                  # bn_train.hip:264,312
+    return ok and c.relu in F_BN_RELU and c.residual in F_BN_RES                  # :265: decision bits only with the ReLU
+
+
+def pool_out(n: int) -> int:
+    return (n - 1) // 2 + 1
+
+
+def _planes_exact(t32: torch.Tensor) -> torch.Tensor:
+    """the values rounded to what planes storage holds (hi + lo, exact in float32): one tensor serves the fp32 and the planes kernels"""
+    hi, lo = canonical_planes(t32.contiguous())
+    return hi.float() + lo.float()
+
+
+def pool_winners(x32: torch.Tensor):
+    """torch's own 3x3 / stride 2 / pad 1 max-pool of float32 NHWC values: (flat NCHW indices [N, C, Ho, Wo], winning taps r * 3 + s as uint8
+    NHWC): the first maximum in scan order under ties"""
+    N, H, W, C = x32.shape
+    _, ind = torch.nn.functional.max_pool2d(x32.permute(0, 3, 1, 2).contiguous(), 3, 2, 1, return_indices=True)
+    ho, wo = torch.arange(ind.shape[2])[:, None], torch.arange(ind.shape[3])[None, :]
+    tap = (ind // W - (2 * ho - 1)) * 3 + (ind % W - (2 * wo - 1))
+    return ind, tap.permute(0, 2, 3, 1).contiguous().to(torch.uint8)
+
+
+def pool_backward(c: ImgCase, ind, dy, dt, mask_out=None, mask_in=None):
+    """(dx, the magnitude sum of its terms) NHWC from flat NCHW winners; mask_out [N, Ho, Wo, C] masks the windows, mask_in the pixels"""
+    dy = dy.to(dt) * (mask_out.to(dt) if mask_out is not None else 1.0)
+    dyn = dy.permute(0, 3, 1, 2).reshape(c.N, c.C, -1)
+    res = []
+    for t in (dyn, dyn.abs()):
+        d = torch.zeros(c.N, c.C, c.H * c.W, dtype=dt).scatter_add_(2, ind.reshape(c.N, c.C, -1), t)
+        d = d.view(c.N, c.C, c.H, c.W).permute(0, 2, 3, 1)
+        res.append(d * mask_in.to(dt) if mask_in is not None else d)
+    return res[0], res[1]
+
+
+def bn_signs(rows: int, C: int, g) -> torch.Tensor:
+    """+-1 alternating down every column from a random start: the two-cluster columns of the bn_train profile"""
+    phase = torch.randint(0, 2, (C,), generator=g)
+    return 1.0 - 2.0 * ((torch.arange(rows)[:, None] + phase[None, :]) % 2).float()
+
+
+def _build_f(c: ImgCase):
+    g = _gen("F", c.index)
+    if c.op == "maxpool":
+        x = _randn(g, c.N, c.H, c.W, c.C)
+        if c.profile == "relu":
+            x = torch.relu(x)
+        elif c.profile == "constant":
+            x = torch.full_like(x, _rng("F.const", c.index).choice((0.75, 0.0, -2.0)))
+        elif c.profile == "negative":
+            x = -x.abs() - 0.1
+        return {"x": _planes_exact(x), "dy": _planes_exact(_randn(g, c.N, pool_out(c.H), pool_out(c.W), c.C))}
+    if c.op == "layout":
+        return {"x": _randn(g, c.N, c.C, c.H, c.W), "x2": _randn(g, c.N, c.H, c.W, c.C)}
+    if c.op == "spatial_mean":
+        inp = {"x": _randn(g, c.N, c.P, c.C) + 0.5, "dy": _randn(g, c.N, c.C)}
+        if c.add:
+            inp["add"] = _randn(g, c.N, c.P, c.C)
+        return inp
+    if c.op == "bn_fold":
+        gamma = 1.0 + 0.5 * _randn(g, c.Ko)
+        gamma[torch.rand(c.Ko, generator=g) < 0.3] = 0.0
+        gamma[_rng("F.fold", c.index).randrange(c.Ko)] = 0.0
+        rvar = torch.tensor([1e-10, 1.0, 1e4])[torch.randint(0, 3, (c.Ko,), generator=g)]
+        return {"w": _randn(g, c.Ko, c.taps, c.C), "gamma": gamma, "beta": _randn(g, c.Ko), "rmean": _randn(g, c.Ko) * rvar.sqrt(), "rvar": rvar}
+    # bn_train.  Every column holds two clusters, offset +- std (1 + N(0, 1) / 4), and beta and the residual are small against gamma:
+    # y stays away from zero (the ReLU decision is unambiguous on all but a sliver, test_decision_bits_cap) while half of it is negative
+    ratio = float(c.profile[6:])
+    std = 10.0 ** (torch.rand(c.C, generator=g) * 1.5 - 1.0)
+    sign = torch.where(torch.rand(c.C, generator=g) < 0.5, -1.0, 1.0)
+    z = std * (sign * ratio + bn_signs(c.rows, c.C, g) * (1.0 + 0.25 * _randn(g, c.rows, c.C)))
+    gamma = (0.5 + torch.rand(c.C, generator=g)) * torch.where(torch.rand(c.C, generator=g) < 0.5, -1.0, 1.0)
+    beta = gamma * (0.15 + 0.1 * torch.rand(c.C, generator=g)) * torch.where(torch.rand(c.C, generator=g) < 0.5, -1.0, 1.0)
+    inp = {"z": z, "gamma": gamma, "beta": beta, "dy": _randn(g, c.rows, c.C)}
+    if c.residual != "none":
+        inp["res"] = 0.05 * gamma.abs() * _randn(g, c.rows, c.C)
+    if c.running:
+        inp["rmean0"], inp["rvar0"] = _randn(g, c.C) * std, (0.5 + torch.rand(c.C, generator=g)) * std * std
+    if c.accumulate:
+        inp["dgamma0"], inp["dbeta0"] = _randn(g, c.C) * math.sqrt(c.rows), _randn(g, c.C) * math.sqrt(c.rows)
+    return inp
+
+
+def bn_forward(c: ImgCase, inp, dt):
+    z, n = _seen(None, inp["z"], c.planes, dt), c.rows
+    gamma, beta = inp["gamma"].to(dt), inp["beta"].to(dt)
+    mean = z.sum(0) / n
+    d = z - mean
+    var = (d * d).sum(0) / n
+    rstd = 1.0 / torch.sqrt(var + BN_EPS)
+    out = {"mean": mean, "var": var, "scale": gamma * rstd, "shift": beta - mean * gamma * rstd, "rstd": rstd}
+    if c.running:
+        out["rmean"] = (1.0 - c.momentum) * inp["rmean0"].to(dt) + c.momentum * mean
+        out["rvar"] = (1.0 - c.momentum) * inp["rvar0"].to(dt) + c.momentum * var * (n / (n - 1.0) if n > 1 else 1.0)
+    if n == 1:      # torch refuses one value per channel: the normalised value is 0 / 0 in the limit; only the statistics are defined
+        return out
+    pre = d * rstd * gamma + beta
+    if c.residual != "none":
+        pre = pre + _seen(None, inp["res"], c.residual == "pl", dt)
+    out["aux:pre"] = pre
+    out["y"] = torch.relu(pre) if c.relu != "none" else pre
+    return out
+
+
+def bn_backward(c: ImgCase, inp, dt, fwd, bits=None):
+    """the backward of the chain from the forward's (mean, rstd) in `dt` and GIVEN ReLU decisions (bool [rows, C]; None: no ReLU)"""
+    z, n = _seen(None, inp["z"], c.planes, dt), c.rows
+    dym = inp["dy"] * bits.float() if bits is not None else inp["dy"]          # exact in float32; then stored as dy is
+    dy = _seen(None, dym, c.planes, dt)
+    mean, rstd, gamma = fwd["mean"].to(dt), fwd["rstd"].to(dt), inp["gamma"].to(dt)
+    sumdy, dot = dy.sum(0), (dy * (z - mean)).sum(0)
+    dg, a = rstd * dot, gamma * rstd
+    cc = -a * rstd * dg / n
+    out = {"sumdy": sumdy, "dot": dot, "A": a, "B": -a * sumdy / n - cc * mean, "Cc": cc, "dgamma": dg, "dbeta": sumdy,
+           "dz": a * (dy - sumdy / n - (z - mean) * rstd * dg / n)}
+    if c.accumulate:
+        out["dgamma"], out["dbeta"] = dg + inp["dgamma0"].to(dt), sumdy + inp["dbeta0"].to(dt)
+    if n == 2:
+        # two values per channel: xhat = +-1 up to eps, and dz vanishes identically (what is left is eps / var of its terms): a
+        # column has no scale of its own to be judged by, and the value is what the rounding of B against Cc z leaves.  What
+        # bn_train_dz computes is still well defined: A dy + (Cc z + B) of the coefficients it is GIVEN.  The evaluation returns that
+        # form (equal to the line above in exact arithmetic), and check() judges a dz against the same form of the coefficients
+        # that came with it (kind "form"), each of which is judged per column on its own
+        out["dz"] = a * dy + (cc * z + out["B"])
+        out["aux:dy"], out["aux:z"] = dy.double(), z.double()
+    return out
+
+
+def _eval_f(c: ImgCase, inp, dt):
+    if c.op == "maxpool":
+        x32 = inp["x"]
+        ind, tap = pool_winners(x32)
+        y = x32.permute(0, 3, 1, 2).reshape(c.N, c.C, -1).gather(2, ind.reshape(c.N, c.C, -1)).view(ind.shape).permute(0, 2, 3, 1).to(dt)
+        dx, m = pool_backward(c, ind, inp["dy"], dt, mask_in=(x32 > 0) if c.relu == "mask" else None)
+        dxp, mp = pool_backward(c, ind, inp["dy"], dt, mask_out=y > 0)
+        return {"y": y, "idx": tap, "dx": dx, "mag:dx": 3.0 * U24 * m.double(), "dx_pl": dxp, "mag:dx_pl": 3.0 * U24 * mp.double()}
+    if c.op == "layout":
+        y = torch.zeros(c.N, c.H, c.W, c.Cpad, dtype=dt)
+        y[..., :c.C] = inp["x"].to(dt).permute(0, 2, 3, 1)
+        return {"nhwc": y, "nchw": inp["x2"].to(dt).permute(0, 3, 1, 2).contiguous()}
+    if c.op == "spatial_mean":
+        x, dy, add = inp["x"].to(dt), inp["dy"].to(dt), (inp["add"].to(dt) if c.add else None)
+        dx = (dy / c.P)[:, None, :].expand(c.N, c.P, c.C)
+        dxp = dx + add if c.add else dx
+        # backward: dy * fl(1 / P) (+ add): two roundings, three with the addition; the planes form adds its storage tolerance (check)
+        return {"y": x.mean(1), "mag:y": (c.P + 2) * U24 * x.abs().double().mean(1), "dx": dx.contiguous(), "mag:dx": 3.0 * U24 * dx.abs().double(),
+                "dx_pl": dxp.contiguous(), "mag:dx_pl": 3.0 * U24 * (dx.abs() + (add.abs() if c.add else 0.0)).double()}
+    if c.op == "bn_fold":
+        rstd = 1.0 / torch.sqrt(inp["rvar"].to(dt) + BN_EPS)
+        scale = inp["gamma"].to(dt) * rstd
+        ws = torch.zeros(c.Ko, c.taps, c.Cpad, dtype=dt)
+        ws[..., :c.C] = inp["w"].to(dt) * scale[:, None, None]
+        return {"w_scaled": ws.view(c.Ko, -1), "scale": scale, "shift": inp["beta"].to(dt) - inp["rmean"].to(dt) * scale, "rstd": rstd}
+    out = bn_forward(c, inp, dt)
+    if c.rows > 1:
+        out.update(bn_backward(c, inp, dt, out, (out["y"] > 0) if c.relu != "none" else None))
+    return out
+
+
+# how an output of E / F is judged: "row" / "col": row_scaled / col_scaled against max(floor, 8 e32); "exact": bit for bit;
+# "sum": elementwise against the derived bound the evaluation returns as "mag:<name>"
+_KIND = {"ln_fwd": {"y": "row", "xhat": "row", "rstd": "row"}, "embed_ln_fwd": {"y": "row", "xhat": "row", "rstd": "row"},
+         "ln_bwd": {"dx": "row", "dgamma": "col", "dbeta": "col", "dxsum": "col"}, "embed_bwd": {"dword": "sum"}, "gelu_bwd": {"dx": "sum"},
+         "planes_add_rows": {"dst": "sum"}, "maxpool": {"y": "exact", "idx": "exact", "dx": "sum", "dx_pl": "sum"},
+         "layout": {"nhwc": "exact", "nchw": "exact"}, "spatial_mean": {"y": "sum", "dx": "sum", "dx_pl": "sum"},
+         "bn_fold": {"w_scaled": "row", "scale": "col", "shift": "col", "rstd": "col"},
+         "bn_train": {k: "col" for k in ("mean", "var", "scale", "shift", "rstd", "rmean", "rvar", "y", "sumdy", "dot", "A", "B", "Cc", "dgamma",
+                                         "dbeta", "dz")}}
+
+
+def kind_of(case, name: str) -> str:
+    if case.op == "bn_train" and name == "dz" and case.rows == 2:
+        return "form"     # bn_backward
+    return _KIND[case.op][name]
+
+
+def exact_equal(got: torch.Tensor, ref: torch.Tensor) -> Tuple[float, tuple]:
+    """0 where the values and the signs of their zeros are those of the reference, else infinitely wrong at the first difference"""
+    got, ref = got.detach().cpu(), ref.detach().cpu()
+    assert got.shape == ref.shape, (tuple(got.shape), tuple(ref.shape))
+    got, ref = got.double(), ref.double()
+    bad = (got != ref) | (torch.signbit(got) != torch.signbit(ref))
+    return (math.inf, tuple(bad.nonzero()[0].tolist())) if bool(bad.any()) else (0.0, ())
+
+
+def _check_ef(case, ref, got, split, planes_out):
+    res = []
+    for name, g in got.items():
+        kind, r = kind_of(case, name), ref[name]
+        if kind == "exact":
+            res.append((name,) + exact_equal(g, r))
+        elif kind == "form":      # fma(A, dy, fma(Cc, z, B)) rounds twice: 3 * 2^-24 on the three magnitudes, as test_grid_stride_wrap
+            t = [got["A"].double().cpu() * ref["aux:dy"], got["Cc"].double().cpu() * ref["aux:z"], got["B"].double().cpu().expand_as(r)]
+            extra = PLANES_TOL * (t[0] + t[1] + t[2]).abs() if name in planes_out else None
+            res.append((name,) + forward_bound(g, t[0] + t[1] + t[2], t[0].abs() + t[1].abs() + t[2].abs(), 3.0 * U24, extra))
+        elif kind == "sum":
+            extra = PLANES_TOL * r.abs().double() if name in planes_out else None
+            res.append((name,) + forward_bound(g, r, ref["mag:" + name], 1.0, extra))
+        else:
+            r2 = r.reshape(-1, 1) if name == "rstd" and kind == "row" else r
+            ratio, idx = (row_scaled if kind == "row" else col_scaled)(g.reshape(r2.shape), r2)
+            res.append((name, ratio / bound_of(case, name, split, name in planes_out), idx))
+    return res
+
+
+def decision_threshold(case: ImgCase, ref, planes_out: bool = False) -> torch.Tensor:
+    """[1, C]: below this |pre-activation| a ReLU decision may differ from the reference's -- the bound of y itself, per column"""
+    scale = ref["y"].abs().double().max(0, keepdim=True).values
+    return bound_of(case, "y", False, planes_out) * scale.clamp_min(FLOOR_REL * float(scale.max()))
+
+
 # ================================================================================================================ one interface
-_GENS = {"A": _gen_a, "B32": _gen_b, "BPL": _gen_b, "C": _gen_c, "D": _gen_d}
+_GENS = {"A": _gen_a, "B32": _gen_b, "BPL": _gen_b, "C": _gen_c, "D": _gen_d, "E": _gen_e, "F": _gen_f}
 _CACHE: Dict[str, list] = {}
 
 
@@ -766,21 +1287,21 @@ def cases(family: str) -> list:
 
 
 def family_of(case) -> str:
-    return {AttnCase: "A", ColCase: "C", HeadCase: "D"}.get(type(case)) or case.family
+    return {AttnCase: "A", ColCase: "C", HeadCase: "D", RowCase: "E", ImgCase: "F"}.get(type(case)) or case.family
 
 
 def legal(case) -> bool:
     if isinstance(case, AttnCase):      # bert.hip:942,989: 4 <= dH <= 64, dH % 4 == 0, 1 <= L <= 512; bert.hip:973,1020: B, nH > 0
         return 4 <= case.dH <= 64 and case.dH % 4 == 0 and 1 <= case.L <= 512 and case.B > 0 and case.nH > 0
-    return {GemmCase: _legal_b, ColCase: _legal_c, HeadCase: _legal_d}[type(case)](case)
+    return {GemmCase: _legal_b, ColCase: _legal_c, HeadCase: _legal_d, RowCase: _legal_e, ImgCase: _legal_f}[type(case)](case)
 
 
 def build(case) -> Dict[str, torch.Tensor]:
-    return {AttnCase: _build_a, GemmCase: _build_b, ColCase: _build_c, HeadCase: _build_d}[type(case)](case)
+    return {AttnCase: _build_a, GemmCase: _build_b, ColCase: _build_c, HeadCase: _build_d, RowCase: _build_e, ImgCase: _build_f}[type(case)](case)
 
 
 def evaluate(case, inp, dt) -> Dict[str, torch.Tensor]:
-    return {AttnCase: _eval_a, GemmCase: _eval_b, ColCase: _eval_c, HeadCase: _eval_d}[type(case)](case, inp, dt)
+    return {AttnCase: _eval_a, GemmCase: _eval_b, ColCase: _eval_c, HeadCase: _eval_d, RowCase: _eval_e, ImgCase: _eval_f}[type(case)](case, inp, dt)
 
 
 def reference(case, inp) -> Dict[str, torch.Tensor]:
@@ -792,7 +1313,7 @@ def describe(case) -> str:
 
 
 # ---------------------------------------------------------------------------------------------------------------- bounds of A, C, D
-BACKWARD = {"dqkv", "dx", "dy", "dcos", "din", "grad"}
+BACKWARD = {"dqkv", "dx", "dy", "dcos", "din", "grad", "dgamma", "dbeta", "dxsum", "A", "B", "Cc", "dz"}
 
 
 def group(case, name: str) -> Tuple[str, str]:
@@ -801,26 +1322,32 @@ def group(case, name: str) -> Tuple[str, str]:
         return "A." + name, case.profile
     if isinstance(case, ColCase):
         return f"C.{case.op}.{name}", case.profile
-    return f"D.{case.op}.{name}", case.profile
+    if isinstance(case, ImgCase) and case.op == "bn_train" and case.rows <= 3:
+        # two or three values per channel: dz and its coefficients are what a cancellation leaves (dz vanishes identically at n = 2)
+        return f"F.bn_train.{name}", f"{case.profile}/n{case.rows}"
+    return f"{family_of(case)}.{case.op}.{name}", case.profile
 
 
 def floor_of(case, name: str, split: bool = False, planes_out: bool = False) -> float:
     """the project's existing bounds: 2e-5 forward, 5e-5 backward, 1e-6 for a column mean (test_train_mode_batchnorm_kernels), and
     3e-4 for planes tensors / split-bf16 mode"""
-    f = 1e-6 if (isinstance(case, ColCase) and name == "mean") else 5e-5 if name in BACKWARD else 2e-5
+    col_mean = name == "mean" and (isinstance(case, ColCase) or getattr(case, "op", "") == "bn_train")
+    f = 1e-6 if col_mean else 5e-5 if name in BACKWARD else 2e-5
     if split or planes_out or (isinstance(case, ColCase) and case.planes):
         f = max(f, 3e-4)
     return f
 
 
 # measured by tests/test_sweep_host.py::test_e32_table (evaluate(..., float32) against float64 through the family's comparator,
-# maximised over the cases of the key), rounded up to two digits; that test keeps every entry within [measured, 2 measured]
+# maximised over the cases of the key) on two hosts -- the CPU-only one and the GPU host: the larger figure times 1.4 where twice the
+# smaller allows it, else the larger figure itself, rounded up to two digits; that test keeps every entry within [measured, 2 measured]
+# (2 measured times E32_HOST_RATIO for the few keys below)
 E32: Dict[Tuple[str, str], float] = {
-    ('A.ctx', 'base'): 1.9e-06,
+    ('A.ctx', 'base'): 2e-06,
     ('A.ctx', 'flat'): 7.6e-07,
     ('A.ctx', 'std30_outlier'): 3.7e-05,
     ('A.ctx', 'std8'): 1.1e-05,
-    ('A.dqkv', 'base'): 3.1e-06,
+    ('A.dqkv', 'base'): 2.2e-06,
     ('A.dqkv', 'flat'): 1.5e-06,
     ('A.dqkv', 'std30_outlier'): 0.00062,
     ('A.dqkv', 'std8'): 0.00025,
@@ -848,11 +1375,11 @@ E32: Dict[Tuple[str, str], float] = {
     ('D.bce.logits', 'base'): 8.4e-08,
     ('D.bce.loss', 'base'): 1.8e-07,
     ('D.bce.score', 'base'): 5.1e-06,
-    ('D.cosine.cos', 'base'): 1.8e-05,
+    ('D.cosine.cos', 'base'): 5.7e-05,
     ('D.cosine.dx', 'base'): 4.6e-07,
     ('D.cosine.dy', 'base'): 2.2e-06,
-    ('D.cosine.max', 'base'): 3.3e-06,
-    ('D.cosine.mean', 'base'): 3.6e-06,
+    ('D.cosine.max', 'base'): 1.1e-05,
+    ('D.cosine.mean', 'base'): 1.1e-05,
     ('D.cosine.xn', 'base'): 2.2e-07,
     ('D.cosine.yn', 'base'): 1.8e-07,
     ('D.group_mean.din', 'base'): 6.2e-08,
@@ -868,6 +1395,247 @@ E32: Dict[Tuple[str, str], float] = {
     ('D.l2norm.dx', 'base'): 1.5e-07,
     ('D.l2norm.norm', 'base'): 2.1e-07,
     ('D.l2norm.xhat', 'base'): 2.4e-07,
+    ('E.embed_ln_fwd.rstd', 'base'): 2.3e-07,
+    ('E.embed_ln_fwd.xhat', 'base'): 3.1e-07,
+    ('E.embed_ln_fwd.y', 'base'): 4.4e-07,
+    ('E.ln_bwd.dbeta', 'near_constant'): 4.2e-05,
+    ('E.ln_bwd.dbeta', 'outlier'): 2e-05,
+    ('E.ln_bwd.dbeta', 'randn'): 6.3e-05,
+    ('E.ln_bwd.dbeta', 'row_offset'): 3.6e-05,
+    ('E.ln_bwd.dbeta', 'row_scale'): 4.7e-05,
+    ('E.ln_bwd.dgamma', 'near_constant'): 1.2e-05,
+    ('E.ln_bwd.dgamma', 'outlier'): 4.4e-05,
+    ('E.ln_bwd.dgamma', 'randn'): 6.8e-05,
+    ('E.ln_bwd.dgamma', 'row_offset'): 2.9e-05,
+    ('E.ln_bwd.dgamma', 'row_scale'): 4.2e-05,
+    ('E.ln_bwd.dx', 'near_constant'): 9e-06,
+    ('E.ln_bwd.dx', 'outlier'): 5.9e-07,
+    ('E.ln_bwd.dx', 'randn'): 2.9e-07,
+    ('E.ln_bwd.dx', 'row_offset'): 6.2e-06,
+    ('E.ln_bwd.dx', 'row_scale'): 2.7e-07,
+    ('E.ln_bwd.dxsum', 'near_constant'): 4.6e-05,
+    ('E.ln_bwd.dxsum', 'outlier'): 1.8e-05,
+    ('E.ln_bwd.dxsum', 'randn'): 6.2e-05,
+    ('E.ln_bwd.dxsum', 'row_offset'): 4.7e-05,
+    ('E.ln_bwd.dxsum', 'row_scale'): 7.3e-05,
+    ('E.ln_fwd.rstd', 'near_constant'): 3.4e-06,
+    ('E.ln_fwd.rstd', 'outlier'): 3.1e-07,
+    ('E.ln_fwd.rstd', 'randn'): 2.3e-07,
+    ('E.ln_fwd.rstd', 'row_offset'): 1.5e-05,
+    ('E.ln_fwd.rstd', 'row_scale'): 3e-07,
+    ('E.ln_fwd.xhat', 'near_constant'): 0.00022,
+    ('E.ln_fwd.xhat', 'outlier'): 2.9e-07,
+    ('E.ln_fwd.xhat', 'randn'): 3.2e-07,
+    ('E.ln_fwd.xhat', 'row_offset'): 9.1e-05,
+    ('E.ln_fwd.xhat', 'row_scale'): 3.6e-07,
+    ('E.ln_fwd.y', 'near_constant'): 0.00025,
+    ('E.ln_fwd.y', 'outlier'): 3e-07,
+    ('E.ln_fwd.y', 'randn'): 3e-07,
+    ('E.ln_fwd.y', 'row_offset'): 9.8e-05,
+    ('E.ln_fwd.y', 'row_scale'): 4.1e-07,
+    ('F.bn_fold.rstd', 'base'): 1.2e-07,
+    ('F.bn_fold.scale', 'base'): 1.2e-07,
+    ('F.bn_fold.shift', 'base'): 2.7e-06,
+    ('F.bn_fold.w_scaled', 'base'): 1.5e-07,
+    ('F.bn_train.A', 'offset0'): 2.1e-07,
+    ('F.bn_train.A', 'offset0/n2'): 1.6e-07,
+    ('F.bn_train.A', 'offset0/n3'): 2.8e-07,
+    ('F.bn_train.A', 'offset30'): 2.7e-07,
+    ('F.bn_train.A', 'offset30/n2'): 2.4e-07,
+    ('F.bn_train.A', 'offset300'): 2.7e-07,
+    ('F.bn_train.A', 'offset300/n2'): 2.1e-07,
+    ('F.bn_train.A', 'offset300/n3'): 2.4e-07,
+    ('F.bn_train.A', 'offset3000'): 2.8e-07,
+    ('F.bn_train.A', 'offset3000/n2'): 2.2e-07,
+    ('F.bn_train.A', 'offset3000/n3'): 2.6e-07,
+    ('F.bn_train.B', 'offset0'): 5.9e-06,
+    ('F.bn_train.B', 'offset0/n2'): 2.2e-07,
+    ('F.bn_train.B', 'offset0/n3'): 3.2e-06,
+    ('F.bn_train.B', 'offset30'): 0.00023,
+    ('F.bn_train.B', 'offset30/n2'): 9.1e-05,
+    ('F.bn_train.B', 'offset300'): 0.0082,
+    ('F.bn_train.B', 'offset300/n2'): 3.4e-05,
+    ('F.bn_train.B', 'offset300/n3'): 0.0012,
+    ('F.bn_train.B', 'offset3000'): 0.012,
+    ('F.bn_train.B', 'offset3000/n2'): 0.00029,
+    ('F.bn_train.B', 'offset3000/n3'): 0.0066,
+    ('F.bn_train.Cc', 'offset0'): 1.1e-05,
+    ('F.bn_train.Cc', 'offset0/n2'): 4.3e-07,
+    ('F.bn_train.Cc', 'offset0/n3'): 1.5e-06,
+    ('F.bn_train.Cc', 'offset30'): 0.00018,
+    ('F.bn_train.Cc', 'offset30/n2'): 2.2e-05,
+    ('F.bn_train.Cc', 'offset300'): 0.017,
+    ('F.bn_train.Cc', 'offset300/n2'): 3.4e-05,
+    ('F.bn_train.Cc', 'offset300/n3'): 0.00083,
+    ('F.bn_train.Cc', 'offset3000'): 0.012,
+    ('F.bn_train.Cc', 'offset3000/n2'): 0.00028,
+    ('F.bn_train.Cc', 'offset3000/n3'): 0.0024,
+    ('F.bn_train.dbeta', 'offset0'): 1.6e-05,
+    ('F.bn_train.dbeta', 'offset0/n2'): 1.2e-07,
+    ('F.bn_train.dbeta', 'offset0/n3'): 1.2e-07,
+    ('F.bn_train.dbeta', 'offset30'): 3.4e-05,
+    ('F.bn_train.dbeta', 'offset30/n2'): 2.3e-06,
+    ('F.bn_train.dbeta', 'offset300'): 5.1e-05,
+    ('F.bn_train.dbeta', 'offset300/n2'): 1.2e-07,
+    ('F.bn_train.dbeta', 'offset300/n3'): 1.2e-07,
+    ('F.bn_train.dbeta', 'offset3000'): 4.4e-06,
+    ('F.bn_train.dbeta', 'offset3000/n2'): 1.2e-07,
+    ('F.bn_train.dbeta', 'offset3000/n3'): 5.1e-06,
+    ('F.bn_train.dgamma', 'offset0'): 1.1e-05,
+    ('F.bn_train.dgamma', 'offset0/n2'): 1.6e-07,
+    ('F.bn_train.dgamma', 'offset0/n3'): 4e-06,
+    ('F.bn_train.dgamma', 'offset30'): 0.00032,
+    ('F.bn_train.dgamma', 'offset30/n2'): 0.00043,
+    ('F.bn_train.dgamma', 'offset300'): 0.011,
+    ('F.bn_train.dgamma', 'offset300/n2'): 0.00073,
+    ('F.bn_train.dgamma', 'offset300/n3'): 0.0009,
+    ('F.bn_train.dgamma', 'offset3000'): 0.012,
+    ('F.bn_train.dgamma', 'offset3000/n2'): 0.03,
+    ('F.bn_train.dgamma', 'offset3000/n3'): 0.054,
+    ('F.bn_train.dot', 'offset0'): 1.4e-05,
+    ('F.bn_train.dot', 'offset0/n2'): 1.6e-07,
+    ('F.bn_train.dot', 'offset0/n3'): 4e-06,
+    ('F.bn_train.dot', 'offset30'): 0.00015,
+    ('F.bn_train.dot', 'offset30/n2'): 3.5e-05,
+    ('F.bn_train.dot', 'offset300'): 0.0035,
+    ('F.bn_train.dot', 'offset300/n2'): 3.3e-05,
+    ('F.bn_train.dot', 'offset300/n3'): 0.00053,
+    ('F.bn_train.dot', 'offset3000'): 0.0049,
+    ('F.bn_train.dot', 'offset3000/n2'): 0.00029,
+    ('F.bn_train.dot', 'offset3000/n3'): 0.0066,
+    ('F.bn_train.dz', 'offset0'): 3.1e-07,
+    ('F.bn_train.dz', 'offset0/n3'): 4.9e-05,
+    ('F.bn_train.dz', 'offset30'): 4e-06,
+    ('F.bn_train.dz', 'offset300'): 4.5e-05,
+    ('F.bn_train.dz', 'offset300/n3'): 0.013,
+    ('F.bn_train.dz', 'offset3000'): 0.00013,
+    ('F.bn_train.dz', 'offset3000/n3'): 0.073,
+    ('F.bn_train.mean', 'offset0'): 0.0003,
+    ('F.bn_train.mean', 'offset0/n2'): 1.2e-07,
+    ('F.bn_train.mean', 'offset0/n3'): 1.8e-06,
+    ('F.bn_train.mean', 'offset30'): 3.1e-07,
+    ('F.bn_train.mean', 'offset30/n1'): 1.2e-07,
+    ('F.bn_train.mean', 'offset30/n2'): 1.2e-07,
+    ('F.bn_train.mean', 'offset300'): 3e-07,
+    ('F.bn_train.mean', 'offset300/n1'): 1.2e-07,
+    ('F.bn_train.mean', 'offset300/n2'): 1.2e-07,
+    ('F.bn_train.mean', 'offset300/n3'): 1.2e-07,
+    ('F.bn_train.mean', 'offset3000'): 2.8e-07,
+    ('F.bn_train.mean', 'offset3000/n1'): 1.2e-07,
+    ('F.bn_train.mean', 'offset3000/n2'): 1.2e-07,
+    ('F.bn_train.mean', 'offset3000/n3'): 1.7e-07,
+    ('F.bn_train.rmean', 'offset0'): 1.2e-07,
+    ('F.bn_train.rmean', 'offset0/n3'): 1.2e-07,
+    ('F.bn_train.rmean', 'offset30'): 1.9e-06,
+    ('F.bn_train.rmean', 'offset30/n1'): 3.8e-07,
+    ('F.bn_train.rmean', 'offset30/n2'): 1.2e-07,
+    ('F.bn_train.rmean', 'offset300'): 1.9e-07,
+    ('F.bn_train.rmean', 'offset300/n3'): 2.1e-07,
+    ('F.bn_train.rmean', 'offset3000'): 2.7e-07,
+    ('F.bn_train.rmean', 'offset3000/n1'): 1.2e-07,
+    ('F.bn_train.rmean', 'offset3000/n2'): 1.4e-07,
+    ('F.bn_train.rstd', 'offset0'): 2.3e-07,
+    ('F.bn_train.rstd', 'offset0/n2'): 1.6e-07,
+    ('F.bn_train.rstd', 'offset0/n3'): 2.3e-07,
+    ('F.bn_train.rstd', 'offset30'): 2.5e-07,
+    ('F.bn_train.rstd', 'offset30/n1'): 1.2e-07,
+    ('F.bn_train.rstd', 'offset30/n2'): 2e-07,
+    ('F.bn_train.rstd', 'offset300'): 2.4e-07,
+    ('F.bn_train.rstd', 'offset300/n1'): 1.2e-07,
+    ('F.bn_train.rstd', 'offset300/n2'): 1.6e-07,
+    ('F.bn_train.rstd', 'offset300/n3'): 2e-07,
+    ('F.bn_train.rstd', 'offset3000'): 2.3e-07,
+    ('F.bn_train.rstd', 'offset3000/n1'): 1.2e-07,
+    ('F.bn_train.rstd', 'offset3000/n2'): 2.2e-07,
+    ('F.bn_train.rstd', 'offset3000/n3'): 2e-07,
+    ('F.bn_train.rvar', 'offset0'): 1.2e-07,
+    ('F.bn_train.rvar', 'offset0/n3'): 1.2e-07,
+    ('F.bn_train.rvar', 'offset30'): 1.7e-07,
+    ('F.bn_train.rvar', 'offset30/n1'): 1.2e-07,
+    ('F.bn_train.rvar', 'offset30/n2'): 1.2e-07,
+    ('F.bn_train.rvar', 'offset300'): 1.2e-07,
+    ('F.bn_train.rvar', 'offset300/n3'): 1.9e-07,
+    ('F.bn_train.rvar', 'offset3000'): 1.5e-07,
+    ('F.bn_train.rvar', 'offset3000/n1'): 1.2e-07,
+    ('F.bn_train.rvar', 'offset3000/n2'): 1.3e-07,
+    ('F.bn_train.scale', 'offset0'): 2.1e-07,
+    ('F.bn_train.scale', 'offset0/n2'): 1.6e-07,
+    ('F.bn_train.scale', 'offset0/n3'): 2.8e-07,
+    ('F.bn_train.scale', 'offset30'): 2.7e-07,
+    ('F.bn_train.scale', 'offset30/n1'): 1.6e-07,
+    ('F.bn_train.scale', 'offset30/n2'): 2.4e-07,
+    ('F.bn_train.scale', 'offset300'): 2.7e-07,
+    ('F.bn_train.scale', 'offset300/n1'): 1.6e-07,
+    ('F.bn_train.scale', 'offset300/n2'): 2.1e-07,
+    ('F.bn_train.scale', 'offset300/n3'): 2.4e-07,
+    ('F.bn_train.scale', 'offset3000'): 2.8e-07,
+    ('F.bn_train.scale', 'offset3000/n1'): 1.4e-07,
+    ('F.bn_train.scale', 'offset3000/n2'): 2.2e-07,
+    ('F.bn_train.scale', 'offset3000/n3'): 2.6e-07,
+    ('F.bn_train.shift', 'offset0'): 5.5e-07,
+    ('F.bn_train.shift', 'offset0/n2'): 3.4e-06,
+    ('F.bn_train.shift', 'offset0/n3'): 1.1e-05,
+    ('F.bn_train.shift', 'offset30'): 4.8e-07,
+    ('F.bn_train.shift', 'offset30/n1'): 2.6e-07,
+    ('F.bn_train.shift', 'offset30/n2'): 2.7e-07,
+    ('F.bn_train.shift', 'offset300'): 4.2e-07,
+    ('F.bn_train.shift', 'offset300/n1'): 2e-07,
+    ('F.bn_train.shift', 'offset300/n2'): 2.7e-07,
+    ('F.bn_train.shift', 'offset300/n3'): 3.2e-07,
+    ('F.bn_train.shift', 'offset3000'): 5.4e-07,
+    ('F.bn_train.shift', 'offset3000/n1'): 1.9e-07,
+    ('F.bn_train.shift', 'offset3000/n2'): 3.4e-07,
+    ('F.bn_train.shift', 'offset3000/n3'): 4.4e-07,
+    ('F.bn_train.sumdy', 'offset0'): 4.5e-05,
+    ('F.bn_train.sumdy', 'offset0/n2'): 1.2e-07,
+    ('F.bn_train.sumdy', 'offset0/n3'): 1.2e-07,
+    ('F.bn_train.sumdy', 'offset30'): 3.4e-05,
+    ('F.bn_train.sumdy', 'offset30/n2'): 1.2e-07,
+    ('F.bn_train.sumdy', 'offset300'): 2.1e-05,
+    ('F.bn_train.sumdy', 'offset300/n2'): 1.2e-07,
+    ('F.bn_train.sumdy', 'offset300/n3'): 1.2e-07,
+    ('F.bn_train.sumdy', 'offset3000'): 3.8e-06,
+    ('F.bn_train.sumdy', 'offset3000/n2'): 1.2e-07,
+    ('F.bn_train.sumdy', 'offset3000/n3'): 1.2e-07,
+    ('F.bn_train.var', 'offset0'): 3e-07,
+    ('F.bn_train.var', 'offset0/n2'): 1.8e-07,
+    ('F.bn_train.var', 'offset0/n3'): 2.8e-07,
+    ('F.bn_train.var', 'offset30'): 3.4e-07,
+    ('F.bn_train.var', 'offset30/n1'): 1.2e-07,
+    ('F.bn_train.var', 'offset30/n2'): 1.2e-07,
+    ('F.bn_train.var', 'offset300'): 3.6e-07,
+    ('F.bn_train.var', 'offset300/n1'): 1.2e-07,
+    ('F.bn_train.var', 'offset300/n2'): 1.2e-07,
+    ('F.bn_train.var', 'offset300/n3'): 2.1e-07,
+    ('F.bn_train.var', 'offset3000'): 5.8e-07,
+    ('F.bn_train.var', 'offset3000/n1'): 1.2e-07,
+    ('F.bn_train.var', 'offset3000/n2'): 1.2e-07,
+    ('F.bn_train.var', 'offset3000/n3'): 3.9e-07,
+    ('F.bn_train.y', 'offset0'): 3.3e-07,
+    ('F.bn_train.y', 'offset0/n2'): 2.4e-07,
+    ('F.bn_train.y', 'offset0/n3'): 4.7e-07,
+    ('F.bn_train.y', 'offset30'): 6.6e-06,
+    ('F.bn_train.y', 'offset30/n2'): 2.4e-06,
+    ('F.bn_train.y', 'offset300'): 5.8e-05,
+    ('F.bn_train.y', 'offset300/n2'): 4.1e-05,
+    ('F.bn_train.y', 'offset300/n3'): 4.9e-05,
+    ('F.bn_train.y', 'offset3000'): 0.00051,
+    ('F.bn_train.y', 'offset3000/n2'): 0.00034,
+    ('F.bn_train.y', 'offset3000/n3'): 0.0012,
+}
+
+
+# keys whose float32 figure depends on the host beyond the factor two of test_e32_table.  The host moves the matrix products
+# (attention scores and contexts, pairwise cosines: the CPU BLAS blocks them by processor model) and, by an ulp, vectorised sums and
+# 1 / sqrt; the thread count moves no entry (measure_e32 runs on one thread, and 1, 8 and 16 threads measure the same).  Every entry is
+# the larger host's figure.  Most then still lie within twice the smaller host's; the ones below do not (the cosines, and maxima over
+# the 8 .. 24 values of a two-row BatchNorm case, where one ulp is a factor two): their upper limit is wider by this measured ratio,
+# larger host / smaller host, and by nothing else.
+E32_HOST_RATIO: Dict[Tuple[str, str], float] = {
+    ('D.cosine.cos', 'base'): 4.50,      # 5.5e-05 / 1.23e-05
+    ('D.cosine.max', 'base'): 4.29,      # 9.84e-06 / 2.31e-06
+    ('D.cosine.mean', 'base'): 3.94,      # 9.84e-06 / 2.51e-06
+    ('F.bn_train.dz', 'offset0/n3'): 2.16,      # 4.71e-05 / 2.2e-05
 }
 
 
@@ -883,6 +1651,8 @@ def check(case, ref, got, split: bool = False, planes_out=()) -> List[Tuple[str,
     """[(name, worst error / bound, index)] over the outputs present in `got`; <= 1 passes"""
     if isinstance(case, GemmCase):
         return _check_b(case, ref, got)
+    if isinstance(case, (RowCase, ImgCase)):
+        return _check_ef(case, ref, got, split, planes_out)
     cmp = comparator(case)
     res = []
     for name, g in got.items():
@@ -896,13 +1666,35 @@ def failures(case, results) -> str:
     return f"{describe(case)}: " + "; ".join(bad) if bad else ""
 
 
+def uses_e32(case, name: str) -> bool:
+    """outputs judged against max(floor, 8 e32): all of A, C, D; the "row" and "col" outputs of E and F"""
+    if name.startswith(("mag:", "aux:")):
+        return False
+    return not isinstance(case, (RowCase, ImgCase)) or kind_of(case, name) in ("row", "col")
+
+
+def compare(case, name: str, got, ref) -> Tuple[float, tuple]:
+    """the comparator's own figure (not yet divided by a bound) of one e32 output"""
+    if isinstance(case, (RowCase, ImgCase)):
+        ref = ref.reshape(-1, 1) if name == "rstd" and kind_of(case, name) == "row" else ref
+        return (row_scaled if kind_of(case, name) == "row" else col_scaled)(got.reshape(ref.shape), ref)
+    return comparator(case)(got, ref)
+
+
 def measure_e32(family: str) -> Dict[Tuple[str, str], float]:
-    """the comparator's figure for the reference formula in float32 (torch, CPU) against float64, maximised per (group, profile)"""
+    """the comparator's figure for the reference formula in float32 (torch, CPU) against float64, maximised per (group, profile).
+    One thread while it measures (restored afterwards): a reduction split over threads sums in an order that depends on their number."""
     out: Dict[Tuple[str, str], float] = {}
-    for c in cases(family):
-        inp = build(c)
-        ref, lo = reference(c, inp), evaluate(c, inp, torch.float32)
-        for name, r in ref.items():
-            k = group(c, name)
-            out[k] = max(out.get(k, 0.0), comparator(c)(lo[name], r)[0])
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        for c in cases(family):
+            inp = build(c)
+            ref, lo = reference(c, inp), evaluate(c, inp, torch.float32)
+            for name, r in ref.items():
+                if uses_e32(c, name):
+                    k = group(c, name)
+                    out[k] = max(out.get(k, 0.0), compare(c, name, lo[name], r)[0])
+    finally:
+        torch.set_num_threads(threads)
     return out

@@ -1,5 +1,8 @@
-"""Seeded differential sweep of the attention, GEMM, column-reduction and head kernels (cases, float64 references, comparators
-and bounds: tests/sweep_cases.py; what the sweep can see: tests/test_sweep_host.py).
+"""Seeded differential sweep of the attention, GEMM, column-reduction and head kernels, the BERT row kernels (LayerNorm, embedding,
+gelu', planes_add_rows) and the image-side non-GEMM kernels (max-pool, layout transforms, spatial mean, BatchNorm folding and the
+train-mode BatchNorm chain) (cases, float64 references, comparators and bounds: tests/sweep_cases.py; what the sweep can see:
+tests/test_sweep_host.py).  Families A to D run in both contraction precisions; the kernels of E and F neither dispatch nor store
+by that mode (kernels.py: only the GEMM and convolution launches read it), so they run once.
 
 Every input sits in a `memguard.Guarded` allocation and every output goes through `memguard.run_contract` (guards and pitch padding
 intact, every element written, bit-identical over an ordinary and a NaN-poisoned exact-size workspace, and a +-1e30 one where the
@@ -12,7 +15,8 @@ import torch
 import memguard as MG
 import sweep_cases as S
 
-pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("precision")]
+pytestmark = [pytest.mark.gpu]
+both_precisions = pytest.mark.usefixtures("precision")
 
 from incremental_multimodal_medical_learning_ii_amd import _lib as _cxr_lib  # noqa: E402
 from incremental_multimodal_medical_learning_ii_amd import kernels as K  # noqa: E402
@@ -79,19 +83,19 @@ def run(call, outs, ws):
 
 
 class Report:
-    def __init__(self, tag):
-        self.tag, self.worst, self.bad = tag, {}, []
+    def __init__(self, tag, mode=True):
+        self.tag, self.worst, self.bad, self.mode = tag, {}, [], mode      # mode: the test runs per contraction precision
 
     def add(self, case, results, form=""):
         for name, ratio, _ in results:
-            k = name + form
+            k = (name if self.mode else f"{case.op}.{name}") + form      # E and F hold several operations: figures per operation
             self.worst[k] = max(self.worst.get(k, 0.0), ratio)
         msg = S.failures(case, results)
         if msg:
             self.bad.append(form + " " + msg)
 
     def finish(self):
-        print(f"{self.tag} [{_cxr_lib.get_precision()}] worst error / bound: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(self.worst.items())))
+        print(f"{self.tag}{' [' + _cxr_lib.get_precision() + ']' if self.mode else ''} worst error / bound: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(self.worst.items())))
         assert not self.bad, "\n".join(self.bad)
 
 
@@ -125,6 +129,7 @@ def _attention(c, rep):
     G.check()
 
 
+@both_precisions
 @pytest.mark.parametrize("chunk", chunk_ids("A"))
 def test_attention(chunk):
     rep = Report("attention " + chunk)
@@ -178,6 +183,7 @@ def _gemm(c, rep):
     G.check()
 
 
+@both_precisions
 @pytest.mark.parametrize("chunk", chunk_ids("B32"))
 def test_gemm_f32(chunk):
     rep = Report("gemm fp32 " + chunk)
@@ -186,6 +192,7 @@ def test_gemm_f32(chunk):
     rep.finish()
 
 
+@both_precisions
 @pytest.mark.parametrize("chunk", chunk_ids("BPL"))
 def test_gemm_planes(chunk, wide):
     rep = Report(f"gemm planes {chunk} [{wide}]")
@@ -218,6 +225,7 @@ def _columns(c, rep):
     G.check()
 
 
+@both_precisions
 @pytest.mark.parametrize("chunk", chunk_ids("C"))
 def test_column_reductions(chunk):
     rep = Report("columns " + chunk)
@@ -294,9 +302,241 @@ def _heads(c, rep):
     G.check()
 
 
+@both_precisions
 @pytest.mark.parametrize("chunk", chunk_ids("D"))
 def test_heads(chunk):
     rep = Report("heads " + chunk)
     for c in chunk_cases("D", chunk):
         _heads(c, rep)
     rep.finish()
+
+
+# ================================================================================================================ E: BERT row kernels
+def _ln_forward(c, inp, ref, G, rep):
+    rows, H = c.rows, c.H
+    gam, bet = G.put(inp["gamma"], "gamma"), G.put(inp["beta"], "beta")
+    if c.op == "ln_fwd":
+        xd, rd = G.put(inp["x"], "x"), (G.put(inp["res"], "res") if c.res else None)
+        call = lambda y, yplane, o: cabi("cxrk_residual_ln_fwd", P(xd), P(rd), P(gam), P(bet), c.eps, rows, H, P(y), yplane, P(o["xhat"]), P(o["rstd"]))      # noqa: E731
+    else:
+        ids, word, pos, typ = (G.put(inp[k], k) for k in ("ids", "word", "pos", "type"))
+        call = lambda y, yplane, o: cabi("cxrk_embed_ln_fwd", P(ids), P(word), P(pos), P(typ), P(gam), P(bet), c.eps, rows, c.L, H, P(y), yplane,      # noqa: E731
+                                         P(o["xhat"]), P(o["rstd"]))
+    saved = {"xhat": Out((rows, H)), "rstd": Out((rows,))}
+    o = run(lambda o: call(o["y"], 0, o), dict(saved, y=Out((rows, H))), False)
+    rep.add(c, S.check(c, ref, {k: g.value() for k, g in o.items()}))
+    if H % 8 == 0:      # the planes output exists in the 8-column kernel only (bert.hip:874,883)
+        o = run(lambda o: call(o["y"], o["y"].stride(0), o), dict(saved, y=Out((2, rows, H), BF)), False)
+        rep.add(c, S.check(c, ref, {k: g.value() for k, g in o.items()}, planes_out=("y",)), "->planes")
+
+
+def _rows(c, rep):
+    inp = S.build(c)
+    ref = S.reference(c, inp)
+    G = Inputs()
+    rows, H = c.rows, c.H
+    if c.op in ("ln_fwd", "embed_ln_fwd"):
+        _ln_forward(c, inp, ref, G, rep)
+    elif c.op == "ln_bwd":
+        dy, xhat, rstd, gam = (G.put(inp[k], k) for k in ("dy", "xhat", "rstd", "gamma"))
+        add = G.put(inp["dx_add"], "dx_add") if c.res else None
+        outs = {"dx": Out((2, rows, H), BF) if c.planes else Out((rows, H)), "dgamma": Out((H,), init=inp.get("dgamma0")),
+                "dbeta": Out((H,), init=inp.get("dbeta0"))}
+        if c.dxsum != "none":
+            outs["dxsum"] = Out((H,), init=inp.get("dxsum0"))
+        o = run(lambda o: K.residual_ln_bwd(dy, xhat, rstd, gam, o["dgamma"], o["dbeta"], dx_add=add, accumulate=c.accumulate,
+                                            out=K.Planes(o["dx"]) if c.planes else o["dx"], dxsum=o.get("dxsum"), dxsum_accumulate=c.dxsum == "acc"),
+                outs, True)
+        rep.add(c, S.check(c, ref, {k: g.value() for k, g in o.items()}, planes_out=("dx",) if c.planes else ()))
+    elif c.op == "embed_bwd":      # the three workspace runs are three launches: bit-identical (run_contract)
+        ids, dx = G.put(inp["ids"], "ids"), G.put(inp["dx"], "dx")
+        o = run(lambda o: K.embed_bwd(ids, dx, o["dword"]), {"dword": Out((c.V, H), init=inp["dword0"])}, True)
+        rep.add(c, S.check(c, ref, {"dword": o["dword"].value()}))
+    elif c.op == "gelu_bwd":
+        dy, pre = G.put(inp["dy"], "dy"), G.put(inp["pre"], "pre")
+        o = run(lambda o: cabi("cxrk_gelu_bwd", P(dy), P(pre), rows, P(o["dx"])), {"dx": Out((rows,))}, False)
+        rep.add(c, S.check(c, ref, {"dx": o["dx"].value()}))
+    else:
+        src = G.planes(inp["src"], "src")
+        o = run(lambda o: K.planes_add_rows(src, o["dst"]), {"dst": Out((rows, H), ld=H + c.pad, init=inp["dst0"])}, False)
+        rep.add(c, S.check(c, ref, {"dst": o["dst"].value()}))
+    G.check()
+
+
+@pytest.mark.parametrize("chunk", chunk_ids("E"))
+def test_rows(chunk):
+    rep = Report("rows " + chunk, mode=False)
+    for c in chunk_cases("E", chunk):
+        _rows(c, rep)
+    rep.finish()
+
+
+# ================================================================================================================ F: image-side kernels
+def _maxpool(c, inp, ref, G, rep):
+    N, H, W, C = c.N, c.H, c.W, c.C
+    Ho, Wo = S.pool_out(H), S.pool_out(W)
+    xd, dyd = G.put(inp["x"], "x"), G.put(inp["dy"], "dy")
+    o = run(lambda o: cabi("cxrk_maxpool_fwd", P(xd), P(o["y"]), P(o["idx"]), N, H, W, C), {"y": Out((N, Ho, Wo, C)), "idx": Out((N, Ho, Wo, C), U8)}, False)
+    idx = o["idx"].t
+    got = {"y": o["y"].value(), "idx": idx.cpu()}
+    o = run(lambda o: cabi("cxrk_maxpool_bwd", P(dyd), P(idx), P(xd), P(o["dx"]), N, H, W, C, int(c.relu == "mask")), {"dx": Out((N, H, W, C))}, False)
+    got["dx"] = o["dx"].value()
+    rep.add(c, S.check(c, ref, got))
+    if C % 8:
+        return
+    xp, dyp = G.planes(inp["x"], "x planes"), G.planes(inp["dy"], "dy planes")
+    o = run(lambda o: cabi("cxrk_maxpool_fwd_pl", xp.ptr(), xp.plane, P(o["y"]), o["y"].stride(0), P(o["idx"]), N, H, W, C),
+            {"y": Out((2, N, Ho, Wo, C), BF), "idx": Out((N, Ho, Wo, C), U8)}, False)
+    idx, pooled = o["idx"].t, K.Planes(o["y"].t)
+    got = {"y": o["y"].value(), "idx": idx.cpu()}
+    o = run(lambda o: cabi("cxrk_maxpool_bwd_pl", dyp.ptr(), dyp.plane, P(idx), pooled.ptr(), P(o["dx_pl"]), N, H, W, C), {"dx_pl": Out((N, H, W, C))}, False)
+    got["dx_pl"] = o["dx_pl"].value()
+    rep.add(c, S.check(c, ref, got), "[planes]")
+
+
+def _bn_train(c, inp, ref, G, rep):
+    rows, C = c.rows, c.C
+    put = (lambda t, n: G.planes(t, n)) if c.planes else (lambda t, n: G.put(t, n))
+    fmt = lambda t: (t.ptr(), t.plane) if isinstance(t, K.Planes) else (t.data_ptr(), 0)      # noqa: E731
+    act = lambda: Out((2, rows, C), BF) if c.planes else Out((rows, C))      # noqa: E731
+    vec = lambda init=None: Out((C,), init=init)      # noqa: E731
+    zd, gam, bet = put(inp["z"], "z"), G.put(inp["gamma"], "gamma"), G.put(inp["beta"], "beta")
+    st = run(lambda o: K.colstats(zd, out=(o["mean"], o["var"])), {"mean": vec(), "var": vec()}, True)
+    mean, var = st["mean"].t, st["var"].t
+    outs = {"scale": vec(), "shift": vec(), "rstd": vec()}
+    if c.running:
+        outs.update(rmean=vec(inp["rmean0"]), rvar=vec(inp["rvar0"]))
+    co = run(lambda o: cabi("cxrk_bn_train_fwd_coeffs", P(mean), P(var), P(gam), P(bet), S.BN_EPS, rows, c.momentum, P(o["scale"]), P(o["shift"]),
+                            P(o["rstd"]), P(o.get("rmean")), P(o.get("rvar")), C), outs, False)
+    got = {k: g.value() for k, g in list(st.items()) + list(co.items())}
+    if rows == 1:      # one value per channel: the statistics and the coefficients are all that is defined
+        rep.add(c, S.check(c, ref, got))
+        return
+    res = None if c.residual == "none" else G.planes(inp["res"], "res") if c.residual == "pl" else G.put(inp["res"], "res")
+    rp, rpl = fmt(res) if res is not None else (None, 0)
+    outs = {"y": act()}
+    if c.relu == "mask":
+        outs["bits"] = Out((rows, C // 8), U8)
+    zp, zpl = fmt(zd)
+    ya = run(lambda o: cabi("cxrk_bn_apply", zp, zpl, P(co["scale"].t), P(co["shift"].t), rp, rpl, P(o["y"]), o["y"].stride(0) if c.planes else 0,
+                            P(o.get("bits")), rows, C, int(c.relu != "none")), outs, False)
+    got["y"] = ya["y"].value()
+    bits = None
+    if c.relu != "none":      # the decisions are those of the stored values, and the reference's wherever it is clear of zero by y's bound
+        bits = got["y"] > 0
+        if c.relu == "mask":
+            assert torch.equal(S.unpack_bits(ya["bits"].t.cpu(), C), bits), f"{S.describe(c)}: decision bits differ from the stored output"
+        clear = ref["aux:pre"].abs() > S.decision_threshold(c, ref, c.planes)
+        assert torch.equal(bits[clear], (ref["aux:pre"] > 0)[clear]), f"{S.describe(c)}: a ReLU decision differs where the reference is clear of zero"
+    back = S.bn_backward(c, inp, torch.float64, ref, bits)      # from the kernel's own decisions
+    dyd = put(inp["dy"] * bits.float() if bits is not None else inp["dy"], "dy")
+    dp, dpl = fmt(dyd)
+    sm = run(lambda o: K.colsum(dyd, o["sumdy"]), {"sumdy": vec()}, True)
+    dt = run(lambda o: K.coldot(dyd, zd, mean, out=o["dot"]), {"dot": vec()}, True)
+    outs = {"A": vec(), "B": vec(), "Cc": vec(), "dgamma": vec(inp["dgamma0"] if c.accumulate else None), "dbeta": vec(inp["dbeta0"] if c.accumulate else None)}
+    bc = run(lambda o: cabi("cxrk_bn_train_bwd_coeffs", P(gam), P(mean), P(co["rstd"].t), P(sm["sumdy"].t), P(dt["dot"].t), rows, P(o["A"]), P(o["B"]),
+                            P(o["Cc"]), P(o["dgamma"]), P(o["dbeta"]), int(c.accumulate), C), outs, False)
+    dz = run(lambda o: cabi("cxrk_bn_train_dz", dp, dpl, zp, zpl, P(bc["A"].t), P(bc["B"].t), P(bc["Cc"].t), P(o["dz"]), o["dz"].stride(0) if c.planes else 0,
+                            rows, C), {"dz": act()}, False)
+    got.update({k: g.value() for k, g in list(sm.items()) + list(dt.items()) + list(bc.items()) + list(dz.items())})
+    rep.add(c, S.check(c, dict(ref, **back), got, planes_out=("y", "dz") if c.planes else ()))
+
+
+def _image_side(c, rep):
+    inp = S.build(c)
+    ref = S.reference(c, inp)
+    G = Inputs()
+    if c.op == "maxpool":
+        _maxpool(c, inp, ref, G, rep)
+    elif c.op == "bn_train":
+        _bn_train(c, inp, ref, G, rep)
+    elif c.op == "layout":
+        N, C, H, W = c.N, c.C, c.H, c.W
+        xd, x2 = G.put(inp["x"], "x"), G.put(inp["x2"], "x2")
+        o = run(lambda o: cabi("cxrk_nchw_to_nhwc", P(xd), P(o["nhwc"]), N, C, H, W, c.Cpad), {"nhwc": Out((N, H, W, c.Cpad))}, False)
+        o2 = run(lambda o: cabi("cxrk_nhwc_to_nchw", P(x2), P(o["nchw"]), N, C, H, W), {"nchw": Out((N, C, H, W))}, False)
+        rep.add(c, S.check(c, ref, {"nhwc": o["nhwc"].t.cpu(), "nchw": o2["nchw"].t.cpu()}))
+    elif c.op == "spatial_mean":
+        N, Pn, C = c.N, c.P, c.C
+        xd, dyd = G.put(inp["x"], "x"), G.put(inp["dy"], "dy")
+        o = run(lambda o: cabi("cxrk_spatial_mean_fwd", P(xd), P(o["y"]), N, Pn, C), {"y": Out((N, C))}, False)
+        o2 = run(lambda o: cabi("cxrk_spatial_mean_bwd", P(dyd), P(o["dx"]), N, Pn, C), {"dx": Out((N, Pn, C))}, False)
+        rep.add(c, S.check(c, ref, {"y": o["y"].value(), "dx": o2["dx"].value()}))
+        if C % 8 == 0:
+            add = G.put(inp["add"], "add") if c.add else None
+            o = run(lambda o: cabi("cxrk_spatial_mean_bwd_pl", P(dyd), P(add), P(o["dx_pl"]), o["dx_pl"].stride(0), N, Pn, C),
+                    {"dx_pl": Out((2, N, Pn, C), BF)}, False)
+            rep.add(c, S.check(c, ref, {"dx_pl": o["dx_pl"].value()}, planes_out=("dx_pl",)), "[planes]")
+    else:
+        Ko, n = c.Ko, c.taps * c.Cpad
+        w, gam, bet, rm, rv = (G.put(inp[k], k) for k in ("w", "gamma", "beta", "rmean", "rvar"))
+        vecs = {"scale": Out((Ko,)), "shift": Out((Ko,)), "rstd": Out((Ko,))}
+        o = run(lambda o: cabi("cxrk_bn_fold", P(w), P(gam), P(bet), P(rm), P(rv), S.BN_EPS, Ko, c.taps, c.C, c.Cpad, P(o["w_scaled"]), P(o["scale"]),
+                               P(o["shift"]), P(o["rstd"])), dict(vecs, w_scaled=Out((Ko, n))), False)
+        rep.add(c, S.check(c, ref, {k: g.value() for k, g in o.items()}))
+        if c.Cpad % 8 == 0:
+            o = run(lambda o: cabi("cxrk_bn_fold_pl", P(w), P(gam), P(bet), P(rm), P(rv), S.BN_EPS, Ko, c.taps, c.C, c.Cpad, P(o["w_scaled"]),
+                                   o["w_scaled"].stride(0), P(o["scale"]), P(o["shift"]), P(o["rstd"])), dict(vecs, w_scaled=Out((2, Ko, n), BF)), False)
+            rep.add(c, S.check(c, ref, {k: g.value() for k, g in o.items()}, planes_out=("w_scaled",)), "[planes]")
+    G.check()
+
+
+@pytest.mark.parametrize("chunk", chunk_ids("F"))
+def test_image_side(chunk):
+    rep = Report("image side " + chunk, mode=False)
+    for c in chunk_cases("F", chunk):
+        _image_side(c, rep)
+    rep.finish()
+
+
+# ================================================================================================================ grid-stride wraps
+WRAP_ROWS, WRAP_C = 32768 + 8, 1024      # 8 * 256 * BN_GRID_CAP = 33 554 432 elements fill the capped grid once; 8192 lie past it
+
+
+def _pattern(n, mul, mod, dev):
+    """((i * mul) % mod - mod / 2) / 64 for i < n: exact in float32 on either device"""
+    i = torch.arange(n, dtype=torch.int64, device=dev)
+    return ((i * mul) % mod - mod // 2).float() / 64.0
+
+
+@pytest.mark.parametrize("op", ("bn_apply", "bn_train_dz"))
+def test_grid_stride_wrap(op):
+    """bn_apply and bn_train_dz cap their grids at 16384 blocks (csrc/bn_train.hip grid_for): one fp32 tensor just past
+    8 * 256 * 16384 elements, a strided sample and the whole second pass against float64.  The bounds are the roundings of the
+    kernels' own forms: fma(z, scale, shift) rounds once (2 * 2^-24 on |z scale| + |shift|, twice what it needs);
+    fma(A, dy, fma(Cc, z, B)) twice (3 * 2^-24 on the three magnitudes)."""
+    rows, C = WRAP_ROWS, WRAP_C
+    n = rows * C
+    assert n > 8 * 256 * S.BN_GRID_CAP
+    pick = torch.cat([torch.arange(0, 8 * 256 * S.BN_GRID_CAP, 997), torch.arange(8 * 256 * S.BN_GRID_CAP, n)])
+    cols = pick % C
+    vec = lambda k: _pattern(C, 29 + 2 * k, 257, "cpu") + 0.015625 * (k + 1)      # noqa: E731
+    G = Inputs()
+    z = MG.Guarded((rows, C), device=DEV, name="z")
+    z.t.view(-1).copy_(_pattern(n, 37, 1021, DEV))
+    z.must_write = False
+    zs = _pattern(n, 37, 1021, "cpu")[pick].double()
+    out = MG.Guarded((rows, C), device=DEV, name=op)
+    if op == "bn_apply":
+        sc, sh = vec(0), vec(1)
+        cabi("cxrk_bn_apply", z.data_ptr(), 0, P(G.put(sc, "scale")), P(G.put(sh, "shift")), None, 0, out.data_ptr(), 0, None, rows, C, 1)
+        a, b = zs * sc.double()[cols], sh.double()[cols]
+        ref, mag, cst = torch.relu(a + b), a.abs() + b.abs(), 2.0
+    else:
+        dy = MG.Guarded((rows, C), device=DEV, name="dy")
+        dy.t.view(-1).copy_(_pattern(n, 53, 509, DEV))
+        dy.must_write = False
+        A, B, Cc = vec(0), vec(1), vec(2)
+        cabi("cxrk_bn_train_dz", dy.data_ptr(), 0, z.data_ptr(), 0, P(G.put(A, "A")), P(G.put(B, "B")), P(G.put(Cc, "Cc")), out.data_ptr(), 0, rows, C)
+        ds = _pattern(n, 53, 509, "cpu")[pick].double()
+        t = [A.double()[cols] * ds, Cc.double()[cols] * zs, B.double()[cols]]
+        ref, mag, cst = t[0] + t[1] + t[2], t[0].abs() + t[1].abs() + t[2].abs(), 3.0
+        dy.check()
+    torch.cuda.synchronize()
+    out.check()
+    z.check()
+    G.check()
+    got = out.t.view(-1)[pick.to(DEV)].cpu()
+    ratio, at = S.forward_bound(got, ref, mag, cst * S.U24)
+    print(f"{op} wrap: worst error / bound {ratio:.3g} over {pick.numel()} elements, {n - 8 * 256 * S.BN_GRID_CAP} past the cap")
+    assert ratio <= 1.0, f"{op}: {ratio:.3g} x bound at flat index {int(pick[at[0]])}"

@@ -37,6 +37,12 @@ def test_generators_are_deterministic_and_legal(family):
         assert a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a), S.describe(c)
         biggest = max(t.numel() * t.element_size() for t in a.values())
         assert biggest < (64 << 20), S.describe(c)
+    if family in ("E", "F"):      # every case: all inputs of a case together stay under C_MAX_BYTES, and nothing is built that the case does not use
+        for c in first:
+            inp = S.build(c)
+            assert sum(t.numel() * t.element_size() for t in inp.values()) <= S.C_MAX_BYTES, S.describe(c)
+            if family == "F" and c.op == "bn_train":
+                assert ("res" in inp) == (c.residual != "none") and ("rvar0" in inp) == c.running and ("dgamma0" in inp) == c.accumulate
 
 
 def _dims(family):
@@ -127,6 +133,140 @@ def test_dispatch_coverage():
     Cc = S.cases("C")
     assert {c.op for c in Cc if c.planes} == set(S.C_OPS) == {c.op for c in Cc if not c.planes}
     assert any(c.op == "colsum" and c.accumulate for c in Cc) and any(c.op == "colsum" and c.planes and c.pad for c in Cc)
+
+
+def _by_op(family):
+    by = {}
+    for c in S.cases(family):
+        by.setdefault(c.op, []).append(c)
+    return by
+
+
+def _covered(cs, dims):
+    """every stratum of every dimension among the first max(n) of the cases `cs` (one operation's, in order)"""
+    first = cs[:max(len(s) for s, _ in dims.values())]
+    for name, (strata, get) in dims.items():
+        missing = set(strata) - {get(c) for c in first}
+        assert not missing, f"{cs[0].op}.{name}: strata {sorted(missing, key=str)} not among the first {len(first)} cases"
+
+
+def _covered_among(cs, pred, name, strata, get):
+    """a dimension whose strata list depends on another draw has a covering sequence per list (Schedule): the first len(strata)
+    of the cases that draw from this list hit all of it"""
+    sub = [c for c in cs if pred(c)][:len(strata)]
+    missing = set(strata) - {get(c) for c in sub}
+    assert len(sub) == len(strata) and not missing, f"{cs[0].op}.{name}: strata {sorted(missing, key=str)} not among the first {len(sub)} cases that draw them"
+
+
+def test_row_kernel_strata_are_hit():
+    by = _by_op("E")
+    assert {op: len(v) for op, v in by.items()} == dict(S.E_COUNTS)
+    _covered(by["ln_fwd"], {"H": (S.E_LN_H, lambda c: c.H), "rows": (S.E_LNF_ROWS, lambda c: c.rows), "eps": (S.E_EPS, lambda c: c.eps),
+                            "res": ((True, False), lambda c: c.res), "profile": (S.E_LN_PROFILES, lambda c: c.profile)})
+    _covered(by["ln_bwd"], {"rows": (S.E_LNB_ROWS, lambda c: c.rows), "dx_add": ((True, False), lambda c: c.res),
+                            "accumulate": ((True, False), lambda c: c.accumulate), "profile": (S.E_LN_PROFILES, lambda c: c.profile)})
+    lb = by["ln_bwd"]
+    _covered_among(lb, lambda c: c.rows < 16383, "H", S.E_LN_H, lambda c: c.H)
+    _covered_among(lb, lambda c: c.rows >= 16383, "H", [h for h in S.E_LN_H if h <= 128], lambda c: c.H)
+    _covered_among(lb, lambda c: c.H % 4 == 0, "dxsum", ("none", "fresh", "acc"), lambda c: c.dxsum)
+    _covered_among(lb, lambda c: c.H % 4 == 0, "planes", (False, True), lambda c: c.planes)
+    _covered_among(by["embed_bwd"], lambda c: c.rows > 100, "pattern", S.E_EB_PATTERNS, lambda c: c.pattern)
+    _covered_among(by["embed_bwd"], lambda c: c.rows < 100, "pattern", S.E_EB_PATTERNS[:4], lambda c: c.pattern)
+    assert set(S.E_LN_H) == {c.H for c in lb} and all(c.H <= 128 for c in lb if c.rows >= 16383)
+    assert {c.H for c in lb if c.rows >= 16383} == {h for h in S.E_LN_H if h <= 128}
+    vec = [c for c in lb if c.H % 4 == 0]
+    assert {c.dxsum for c in vec} == {"none", "fresh", "acc"} and {c.planes for c in vec} == {True, False}
+    assert any(c.dxsum == "acc" and c.res for c in vec) and any(c.accumulate and c.dxsum != "none" for c in vec)
+    _covered(by["embed_ln_fwd"], {"L": (S.E_EMB_L, lambda c: c.L), "H": (S.E_EMB_H, lambda c: c.H), "whole": ((True, False), lambda c: c.rows % c.L == 0)})
+    for c in by["embed_ln_fwd"]:
+        ids = S.build(c)["ids"]
+        assert int(ids.min()) == 0 or c.rows == 1
+        assert int(ids.max()) == c.V - 1
+    _covered(by["embed_bwd"], {"T": (S.E_EB_T, lambda c: c.rows), "H": (S.E_EB_H, lambda c: c.H)})
+    assert {c.pattern for c in by["embed_bwd"] if c.rows > 100} == set(S.E_EB_PATTERNS)
+    assert {c.pattern for c in by["embed_bwd"] if c.rows < 100} == set(S.E_EB_PATTERNS[:4])
+    assert all(float(S.build(c)["dword0"].abs().min()) > 0 for c in by["embed_bwd"][:3])
+    assert {c.rows for c in by["gelu_bwd"]} == set(S.E_GELU_N)
+    pre = S.build(by["gelu_bwd"][-1])["pre"]
+    assert all(float(S.build(c)["pre"].min()) < -11.9 and float(S.build(c)["pre"].max()) > 11.9 for c in by["gelu_bwd"] if c.rows > 1), pre
+    add = by["planes_add_rows"]
+    assert {(c.rows, c.H) for c in add} == {(r, h) for r in S.E_ADD_ROWS for h in S.E_ADD_COLS} and {c.pad for c in add} == set(S.E_ADD_PAD)
+
+
+def test_image_kernel_strata_are_hit():
+    by = _by_op("F")
+    assert {op: len(v) for op, v in by.items()} == dict(S.F_COUNTS)
+    _covered(by["maxpool"], {"H": (S.F_POOL_HW, lambda c: c.H), "W": (S.F_POOL_HW, lambda c: c.W), "N": (S.F_POOL_N, lambda c: c.N),
+                             "C": (S.F_POOL_C, lambda c: c.C), "profile": (S.F_POOL_PROFILES, lambda c: c.profile),
+                             "relu_mask": (("mask", "none"), lambda c: c.relu)})
+    assert any(c.H != c.W for c in by["maxpool"]) and any(c.C % 8 == 0 and c.H % 2 and c.W % 2 == 0 for c in by["maxpool"])
+    lay = by["layout"]
+    assert {(c.C, c.Cpad) for c in lay} == {(C, Cp) for C in S.F_LAY_C for Cp in (C, 4, 8) if Cp >= C} and all(c.H != c.W for c in lay)
+    _covered(by["spatial_mean"], {"P": (S.F_SM_P, lambda c: c.P), "C": (S.F_SM_C, lambda c: c.C), "add": ((True, False), lambda c: c.add)})
+    assert {c.add for c in by["spatial_mean"] if c.C % 8 == 0} == {True, False}
+    _covered(by["bn_fold"], {"taps": (S.F_FOLD_TAPS, lambda c: c.taps), "C": (S.F_FOLD_C, lambda c: (c.C, c.Cpad)), "Ko": (S.F_FOLD_KO, lambda c: c.Ko)})
+    for c in by["bn_fold"]:
+        inp = S.build(c)
+        assert bool((inp["gamma"] == 0).any()) and set(inp["rvar"].tolist()) <= {float(torch.tensor(1e-10)), 1.0, 1e4}
+    assert {v for c in by["bn_fold"] for v in S.build(c)["rvar"].tolist()} == {float(torch.tensor(1e-10)), 1.0, 1e4}
+    _covered(by["bn_train"], {"rows": (S.F_BN_ROWS, lambda c: c.rows), "C": (S.F_BN_C, lambda c: c.C), "residual": (S.F_BN_RES, lambda c: c.residual),
+                              "relu": (S.F_BN_RELU, lambda c: c.relu), "momentum": (S.F_BN_MOM, lambda c: c.momentum),
+                              "running": ((True, False), lambda c: c.running), "accumulate": ((True, False), lambda c: c.accumulate),
+                              "planes": ((True, False), lambda c: c.planes), "ratio": (S.F_BN_RATIO, lambda c: int(c.profile[6:]))})
+    bn = by["bn_train"]
+    _covered_among(bn, lambda c: c.rows < 4097, "C", S.F_BN_C, lambda c: c.C)
+    _covered_among(bn, lambda c: c.rows == 4097, "C", S.F_BN_C[:3], lambda c: c.C)
+    for c in by["bn_train"][::5]:      # the columns sit where the profile says: |mean| / std within a third of the stratum
+        z = S.build(c)["z"].double()
+        if c.rows >= 16 and int(c.profile[6:]):
+            ratio = z.mean(0).abs() / z.std(0)
+            assert float((ratio / int(c.profile[6:]) - 1).abs().max()) < 0.34, S.describe(c)
+
+
+def test_row_and_image_dispatch_coverage():
+    """the host logic of csrc/bert.hip, embed.hip, conv_misc.hip and the grid caps, restated: every path is reached by a case"""
+    E = _by_op("E")
+    fwd = E["ln_fwd"] + E["embed_ln_fwd"]
+    assert any(c.H % 8 == 0 for c in E["ln_fwd"]) and any(c.H % 8 for c in E["ln_fwd"])                    # ln_vec8_ok: vec8 / scalar
+    assert any(c.H % 8 == 0 for c in E["embed_ln_fwd"]) and any(c.H % 8 for c in E["embed_ln_fwd"])
+    assert any(c.H in (504, 512, 520) for c in E["ln_fwd"]) and any(c.H in (1016, 1024) for c in E["ln_fwd"])      # the edges of the 64-lane x 8 map
+    lb = E["ln_bwd"]
+    assert any(c.H % 4 == 0 for c in lb) and any(c.H % 4 for c in lb)                                      # ln_bwd_vec_ok: vec / scalar
+    assert any(c.dxsum == "none" for c in lb if c.H % 4 == 0) and any(c.dxsum != "none" for c in lb)       # np = 2, np = 3
+    regrid = [c for c in lb if S.ln_bwd_launch(c.rows)[1] > 16 and S.ln_bwd_launch(c.rows)[2] != S.ln_bwd_launch(c.rows)[0]]
+    assert any(c.dxsum != "none" for c in regrid), "rows_per > 16 with a recomputed block count, together with dxsum"
+    assert S.ln_bwd_launch(16385) == (1024, 17, 964) and S.ln_bwd_launch(16383) == (1024, 16, 1024) and S.ln_bwd_launch(17) == (2, 9, 2)
+    idle = {(4 - c.rows % 4) % 4 for c in fwd}                                                             # one wave per row, four rows per block
+    idle |= {max(0, 4 - (c.rows - (S.ln_bwd_launch(c.rows)[2] - 1) * S.ln_bwd_launch(c.rows)[1])) for c in lb}
+    assert idle >= {0, 1, 2, 3}, idle
+    runs_seen, spans = set(), []
+    for c in E["embed_bwd"]:
+        nruns, span = S.embed_chunks(S.build(c)["ids"])
+        runs_seen |= {min(n, 3) for n in nruns}
+        spans.append((c, nruns, span))
+        if c.pattern == "chunk_aligned":      # every run starts on a chunk edge
+            ids = sorted(S.build(c)["ids"].tolist())
+            assert all(i % S.EMBED_CH == 0 for i in range(1, len(ids)) if ids[i] != ids[i - 1]), S.describe(c)
+    assert runs_seen == {1, 2, 3}                                                                          # chunks of 1, 2 and more runs
+    for c, nruns, span in spans:
+        if c.pattern == "long_then_split":      # a run over chunks 0, 1, 2 ending inside chunk 2, which holds exactly one more run
+            ids = sorted(S.build(c)["ids"].tolist())
+            assert ids[0] == ids[64] != ids[95] and nruns[:3] == [1, 1, 2] and span >= 3, S.describe(c)
+    assert sum(c.pattern == "long_then_split" for c, _, _ in spans) >= 1
+    assert any(span >= 3 for c, _, span in spans if c.pattern == "zipf")
+    cap = 256 * S.ADD_ROWS_CAP
+    assert [c for c in E["planes_add_rows"] if c.rows * (c.H // 8) > cap] and any(c.rows * (c.H // 8) <= cap for c in E["planes_add_rows"])
+    assert 8200 * 64 > cap
+    Fm = _by_op("F")
+    pool = Fm["maxpool"]
+    # 3 x 3, stride 2, pad 1: the first window is always clipped above / left; the last one below / right exactly when the size is odd
+    assert any(c.H % 2 for c in pool) and any(c.W % 2 for c in pool) and any(c.H % 2 == 0 and c.H > 1 for c in pool) and any(c.W % 2 == 0 for c in pool)
+    assert any(c.H == 1 for c in pool) and any(c.W == 1 for c in pool)                                     # clipped on both sides at once
+    assert any(c.C % 8 == 0 and c.H % 2 for c in pool) and any(c.C % 8 == 0 and c.W % 2 for c in pool)     # H2 = (H + 1) / 2 of the planes backward
+    assert any(c.C % 8 for c in pool)
+    bn = [c for c in Fm["bn_train"] if c.rows > 1]
+    assert all(c.rows * (c.C // 8) <= 256 * S.BN_GRID_CAP for c in bn), "the wraps have their own test (test_grid_stride_wrap)"
+    assert {(c.planes, c.residual) for c in bn} >= {(False, "pl"), (True, "f32"), (True, "pl"), (False, "f32")}
 
 
 # ---------------------------------------------------------------------------------------------------------------- references
@@ -270,16 +410,161 @@ def test_head_references_against_torch():
         assert abs(float(loss) - float(ref["loss"])) < 1e-12 and float((cos.grad - ref["dcos"]).abs().max()) < 1e-15
 
 
+def test_layernorm_references_against_torch():
+    for c in _pick("E", lambda c: c.op == "ln_fwd" and c.rows <= 257, 6) + _pick("E", lambda c: c.op == "embed_ln_fwd", 3):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        if c.op == "ln_fwd":
+            x = inp["x"].double() + (inp["res"].double() if c.res else 0)
+        else:
+            x = F.embedding(inp["ids"], inp["word"].double()) + inp["pos"].double().repeat(-(-c.rows // c.L), 1)[:c.rows] + inp["type"].double()
+        y = F.layer_norm(x, (c.H,), inp["gamma"].double(), inp["beta"].double(), c.eps)
+        assert S.row_scaled(ref["y"], y)[0] < 1e-9, S.describe(c)
+        assert S.row_scaled(ref["rstd"], 1 / torch.sqrt(x.var(1, unbiased=False, keepdim=True) + c.eps))[0] < 1e-9
+    for c in _pick("E", lambda c: c.op == "ln_bwd" and c.rows <= 255, 10):
+        # the reference differentiates at the saved float32 xhat / rstd: equal to autograd through F.layer_norm of the values they
+        # were taken from (the first draw of the case's generator) up to their rounding
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        x = S._ln_values(c, S._gen("E", c.index)).double().requires_grad_(True)
+        g = inp["gamma"].double().requires_grad_(True)
+        b = torch.zeros(c.H, dtype=F64, requires_grad=True)
+        F.layer_norm(x, (c.H,), g, b, c.eps).backward(inp["dy"].double())
+        exp = x.grad + (inp["dx_add"].double() if c.res else 0)
+        # 2^-24 of xhat and rstd, amplified where a row's or a column's terms cancel
+        assert S.row_scaled(ref["dx"], exp)[0] < 1e-4, S.describe(c)
+        assert S.col_scaled(ref["dgamma"] - (inp["dgamma0"].double() if c.accumulate else 0), g.grad)[0] < 1e-4, S.describe(c)
+        assert S.col_scaled(ref["dbeta"] - (inp["dbeta0"].double() if c.accumulate else 0), b.grad)[0] < 1e-12, S.describe(c)
+        if c.dxsum != "none":
+            assert S.col_scaled(ref["dxsum"] - (inp["dxsum0"].double() if c.dxsum == "acc" else 0), ref["dx"].sum(0))[0] < 1e-12
+
+
+def test_embedding_and_elementwise_references_against_torch():
+    for c in _pick("E", lambda c: c.op == "embed_bwd", 6):
+        inp = S.build(c)
+        w = inp["dword0"].double().clone().requires_grad_(True)
+        F.embedding(inp["ids"], w).backward(inp["dx"].double())
+        exp = inp["dword0"].double().clone().index_add_(0, inp["ids"], inp["dx"].double())
+        ref = S.reference(c, inp)["dword"]
+        assert float((ref - exp).abs().max()) == 0.0 and float((ref - inp["dword0"].double() - w.grad).abs().max()) < 1e-12, S.describe(c)
+    for c in _pick("E", lambda c: c.op == "gelu_bwd", 5):
+        inp = S.build(c)
+        x = inp["pre"].double().requires_grad_(True)
+        F.gelu(x).backward(inp["dy"].double())
+        assert float((S.reference(c, inp)["dx"] - x.grad).abs().max()) < 1e-14
+    c = _pick("E", lambda c: c.op == "planes_add_rows", 1)[0]
+    inp = S.build(c)
+    hi, lo = S.canonical_planes(inp["src"])
+    assert torch.equal(S.reference(c, inp)["dst"], inp["dst0"].double() + hi.double() + lo.double())
+
+
+def _pool_scan(x32, last=False):
+    """winning taps by an explicit look at every window: the first (or the last) maximum in scan order (r, s)"""
+    N, H, W, C = x32.shape
+    xp = F.pad(x32.permute(0, 3, 1, 2), (1, 1, 1, 1), value=-math.inf)
+    win = xp.unfold(2, 3, 2).unfold(3, 3, 2).reshape(N, C, S.pool_out(H), S.pool_out(W), 9)
+    hit = win == win.max(-1, keepdim=True).values
+    tap = 8 - hit.flip(-1).float().argmax(-1) if last else hit.float().argmax(-1)
+    return tap.permute(0, 2, 3, 1).to(torch.uint8), win.max(-1).values.permute(0, 2, 3, 1)
+
+
+def test_image_references_against_torch():
+    for c in _pick("F", lambda c: c.op == "maxpool", 36):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        tap, val = _pool_scan(inp["x"])
+        assert torch.equal(ref["idx"], tap) and torch.equal(ref["y"], val.double()), S.describe(c)
+        x = inp["x"].double().requires_grad_(True)
+        xr = torch.relu(x) if c.relu == "mask" else x
+        y = F.max_pool2d(xr.permute(0, 3, 1, 2), 3, 2, 1)
+        y.backward(inp["dy"].double().permute(0, 3, 1, 2))
+        if c.relu != "mask" or c.profile in ("randn", "negative"):      # under ties among zeros relu(x) routes to the first zero: masked either way
+            assert float((ref["dx"] - x.grad).abs().max()) < 1e-12, S.describe(c)
+        # the planes backward: the gradient of max_pool(relu(x)) -- a window whose maximum is not positive passes nothing
+        x = inp["x"].double().requires_grad_(True)
+        F.max_pool2d(torch.relu(x).permute(0, 3, 1, 2), 3, 2, 1).backward(inp["dy"].double().permute(0, 3, 1, 2))
+        assert float((ref["dx_pl"] - x.grad * (inp["x"] > 0)).abs().max()) < 1e-12, S.describe(c)
+    for c in _pick("F", lambda c: c.op == "layout", 8):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        assert torch.equal(ref["nhwc"][..., :c.C], inp["x"].double().permute(0, 2, 3, 1)) and float(ref["nhwc"][..., c.C:].abs().sum()) == 0
+        assert torch.equal(ref["nchw"], torch.einsum("nhwc->nchw", inp["x2"].double()))
+    for c in _pick("F", lambda c: c.op == "spatial_mean", 12):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        x = inp["x"].double().requires_grad_(True)
+        x.mean(1).backward(inp["dy"].double())
+        assert float((ref["y"] - x.detach().mean(1)).abs().max()) < 1e-13 and float((ref["dx"] - x.grad).abs().max()) < 1e-15
+        assert float((ref["dx_pl"] - x.grad - (inp["add"].double() if c.add else 0)).abs().max()) < 1e-15
+    for c in _pick("F", lambda c: c.op == "bn_fold", 8):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        x = torch.randn(5, c.Ko, dtype=F64)
+        y = F.batch_norm(x, inp["rmean"].double(), inp["rvar"].double(), inp["gamma"].double(), inp["beta"].double(), False, 0.0, S.BN_EPS)
+        assert S.col_scaled(x * ref["scale"] + ref["shift"], y)[0] < 1e-9, S.describe(c)
+        w = ref["w_scaled"].view(c.Ko, c.taps, c.Cpad)
+        assert float(w[..., c.C:].abs().sum()) == 0 and float((w[..., :c.C] - inp["w"].double() * ref["scale"][:, None, None]).abs().max()) == 0
+
+
+def test_batchnorm_reference_against_torch():
+    for c in [c for c in S.cases("F") if c.op == "bn_train" and c.rows > 1]:
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        z = S._seen(None, inp["z"], c.planes, F64).requires_grad_(True)
+        g, b = inp["gamma"].double().requires_grad_(True), inp["beta"].double().requires_grad_(True)
+        rm, rv = (inp["rmean0"].double().clone(), inp["rvar0"].double().clone()) if c.running else (None, None)
+        y = F.batch_norm(z, rm, rv, g, b, True, c.momentum, S.BN_EPS)
+        if c.residual != "none":
+            y = y + S._seen(None, inp["res"], c.residual == "pl", F64)
+        y = torch.relu(y) if c.relu != "none" else y
+        assert S.col_scaled(ref["y"], y.detach())[0] < 1e-9, S.describe(c)
+        if c.running:
+            assert S.col_scaled(ref["rmean"], rm)[0] < 1e-12 and S.col_scaled(ref["rvar"], rv)[0] < 1e-12, S.describe(c)
+        # the stored (masked) gradient: the reference's own decisions here, the kernel's in the GPU test
+        dym = inp["dy"] * (ref["y"] > 0).float() if c.relu != "none" else inp["dy"]
+        F.batch_norm(z, None, None, g, b, True, 0.0, S.BN_EPS).backward(S._seen(None, dym, c.planes, F64))
+        acc = (inp["dgamma0"].double(), inp["dbeta0"].double()) if c.accumulate else (0, 0)
+        assert S.col_scaled(ref["dgamma"] - acc[0], g.grad)[0] < 1e-7 and S.col_scaled(ref["dbeta"] - acc[1], b.grad)[0] < 1e-12, S.describe(c)
+        if c.rows > 3:      # with two or three rows dz is what is left of a cancellation: nothing to compare beyond its smallness
+            assert S.col_scaled(ref["dz"], z.grad)[0] < 1e-6, S.describe(c)
+        dz = ref["A"] * S._seen(None, dym, c.planes, F64) + ref["B"] + ref["Cc"] * z.detach()
+        assert float((dz - ref["dz"]).abs().max()) <= 1e-9 * float(dz.abs().max() + (ref["B"].abs() + (ref["Cc"] * z.detach()).abs()).max()), S.describe(c)
+
+
+def test_decision_bits_cap():
+    """the GPU test compares the ReLU decisions of bn_apply wherever |pre-activation| exceeds y's own bound; on the float64 reference
+    alone, that leaves out less than 1 % of the elements of every case (max-pool's relu_mask decides on its exact inputs: nothing
+    is left out there)"""
+    worst = 0.0
+    for c in S.cases("F"):
+        if c.op != "bn_train" or c.relu == "none" or c.rows == 1:
+            continue
+        ref = S.reference(c, S.build(c))
+        share = float((ref["aux:pre"].abs() <= S.decision_threshold(c, ref, c.planes)).double().mean())
+        worst = max(worst, share)
+        assert share < 0.01, f"{S.describe(c)}: {share:.3%} of the decisions are within the bound of zero"
+        assert 0.3 < float((ref["aux:pre"] > 0).double().mean()) < 0.7, S.describe(c)
+    print(f"largest share left out: {worst:.3%}")
+
+
 # ---------------------------------------------------------------------------------------------------------------- E32
 def test_e32_table():
-    """every entry of E32 is at least what this machine measures and at most twice that: it can neither go stale nor be padded"""
+    """every entry of E32 is at least what this machine measures and at most twice that: it can neither go stale nor be padded.  Where
+    the float32 matrix products of two hosts differ (E32_HOST_RATIO) the entry is the larger host's figure and the upper limit is wider
+    by exactly the measured ratio between them."""
     measured = {}
-    for family in ("A", "C", "D"):
+    for family in ("A", "C", "D", "E", "F"):
         measured.update(S.measure_e32(family))
     print("\n".join(f"{k}: measured {v:.3g}, table {S.E32.get(k)}" for k, v in sorted(measured.items())))
     assert set(measured) == set(S.E32), set(measured) ^ set(S.E32)
-    for k, v in measured.items():
-        assert v <= S.E32[k] <= 2 * v, f"E32[{k}] = {S.E32[k]:.3g}, measured {v:.3g}"
+    assert set(S.E32_HOST_RATIO) <= set(S.E32) and all(1.0 < r < 5.0 for r in S.E32_HOST_RATIO.values())
+    # E and F: a figure below one float32 ulp (2^-23) is a count of ulps over a few values -- 0 on one host, 1 on the next -- and cannot
+    # move a bound (8 x 2^-22 is far below every floor): the table holds no E or F entry below 1.2e-7, and such an entry is held under
+    # 2^-22 instead of under twice the measurement
+    limit = lambda k, v: max(2 * S.E32_HOST_RATIO.get(k, 1.0) * v, 2.0 ** -22 if k[0][0] in "EF" else 0.0)      # noqa: E731
+    assert all(v >= 1.2e-7 for k, v in S.E32.items() if k[0][0] in "EF")
+    bad = [f"E32[{k}] = {S.E32[k]:.3g}, measured {v:.3g}" for k, v in measured.items() if not v <= S.E32[k] <= limit(k, v)]
+    assert not bad, "\n".join(bad)
 
 
 # ---------------------------------------------------------------------------------------------------------------- power of the sweep
@@ -298,7 +583,7 @@ def _sweep(family, kernel, pred=lambda c: True, split=False):
 
 def _correct32(c, inp):
     out = S.evaluate(c, inp, F32)
-    return {k: v for k, v in out.items() if not k.startswith("mag:")}
+    return {k: v for k, v in out.items() if not k.startswith(("mag:", "aux:"))}
 
 
 @pytest.mark.parametrize("family", FAMILIES)
@@ -412,3 +697,158 @@ def test_fake_cosine_backward_is_caught():
     caught = {c.index for c, _ in _sweep("D", _fake_cosine_overwrites_dx, lambda c: c.op == "cosine")}
     multi = {c.index for c in S.cases("D") if c.op == "cosine" and c.flag_b and S.cosine_chunks(c) > 1}
     assert caught and caught <= multi and len(caught) >= 0.5 * len(multi), (caught, multi)
+
+
+# ---------------------------------------------------------------------------------------------------------------- fakes of E and F
+def _only(op):
+    return lambda c: c.op == op
+
+
+def _fake_ln_naive_variance(c, inp):
+    out = _correct32(c, inp)
+    if c.op == "ln_fwd":
+        x = inp["x"] + (inp["res"] if c.res else 0.0)
+    else:
+        x = inp["word"][inp["ids"]] + inp["pos"][torch.arange(c.rows) % c.L] + inp["type"]
+    mean = x.mean(1, keepdim=True)
+    rstd = 1.0 / torch.sqrt((x * x).mean(1, keepdim=True) - mean * mean + c.eps)
+    xhat = (x - mean) * rstd
+    return dict(out, xhat=xhat, rstd=rstd, y=xhat * inp["gamma"] + inp["beta"])
+
+
+def test_fake_layernorm_kernels_are_caught():
+    caught = _sweep("E", _fake_ln_naive_variance, lambda c: c.op in ("ln_fwd", "embed_ln_fwd"))
+    profiles = {c.profile for c, _ in caught}
+    assert {"row_offset", "near_constant"} <= profiles and "randn" not in profiles and "base" not in profiles, profiles
+    hard = {c.index for c in S.cases("E") if c.op == "ln_fwd" and c.profile in ("row_offset", "near_constant")}
+    assert len(hard & {c.index for c, _ in caught}) >= 0.8 * len(hard)      # a row whose offset happens to be small may pass
+    # the rows of the last block, lost when rows % rows_per != 0
+    lost = lambda c, inp: S._eval_e(c, inp, F32, rows_used=c.rows - c.rows % S.ln_bwd_launch(c.rows)[1])      # noqa: E731
+    caught = {c.index for c, _ in _sweep("E", lost, _only("ln_bwd"))}
+    expect = {c.index for c in S.cases("E") if c.op == "ln_bwd" and c.rows % S.ln_bwd_launch(c.rows)[1]}
+    assert caught and caught <= expect and len(caught) >= 0.9 * len(expect), (sorted(caught), sorted(expect))
+
+    def no_add(c, inp):      # the column sums of the gradient without dx_add
+        out = _correct32(c, inp)
+        if c.dxsum != "none" and c.res:
+            out["dxsum"] = out["dxsum"] - inp["dx_add"].sum(0)
+        return out
+    caught = {c.index for c, _ in _sweep("E", no_add, _only("ln_bwd"))}
+    assert caught and caught == {c.index for c in S.cases("E") if c.op == "ln_bwd" and c.dxsum != "none" and c.res}
+
+
+def _embed_chunked32(c, inp, lose=False):
+    """csrc/embed.hip in float32 on the CPU: chunks of 32 sorted entries, interior runs added directly, boundary runs from the head /
+    tail partials.  lose: the boundary pass stops in front of a chunk with two runs instead of behind it."""
+    ids, dx, out = inp["ids"].tolist(), inp["dx"], inp["dword0"].clone()
+    order = sorted(range(c.rows), key=lambda t: (ids[t], t))
+    meta, head, tail = [], [], []
+    for p in range(0, c.rows, S.EMBED_CH):
+        runs = []
+        for t in order[p:p + S.EMBED_CH]:
+            if runs and runs[-1][0] == ids[t]:
+                runs[-1][1].append(t)
+            else:
+                runs.append((ids[t], [t]))
+        sums = []
+        for _, ts in runs:
+            acc = torch.zeros(c.H)
+            for t in ts:
+                acc = acc + dx[t]
+            sums.append(acc)
+        for (v, _), acc in zip(runs[1:-1], sums[1:-1]):
+            out[v] += acc
+        meta.append((len(runs), runs[0][0], runs[-1][0]))
+        head.append(sums[0])
+        tail.append(sums[-1])
+    for k, (nruns, head_id, tail_id) in enumerate(meta):
+        for which in (0, 1):
+            if which == 0:
+                if k > 0 and meta[k - 1][2] == head_id:
+                    continue
+                v, acc, reaches_end = head_id, head[k], nruns == 1
+            else:
+                if nruns < 2:
+                    continue
+                v, acc, reaches_end = tail_id, tail[k], True
+            last = k
+            while reaches_end and last + 1 < len(meta) and meta[last + 1][1] == v:
+                if lose and meta[last + 1][0] > 1:
+                    break
+                last += 1
+                if meta[last][0] > 1:
+                    break
+            for kk in range(k + 1, last + 1):
+                acc = acc + head[kk]
+            out[v] += acc
+    return {"dword": out}
+
+
+def test_fake_embedding_gradient_is_caught():
+    assert not _sweep("E", _embed_chunked32, _only("embed_bwd")), "the chunked float32 form the fake is a variation of must pass"
+    caught = {c.index: c for c, _ in _sweep("E", lambda c, i: _embed_chunked32(c, i, lose=True), _only("embed_bwd"))}
+    assert {c.index for c in S.cases("E") if c.op == "embed_bwd" and c.pattern == "long_then_split"} <= set(caught)
+    assert all(c.pattern in ("zipf", "long_then_split") for c in caught.values()), {c.pattern for c in caught.values()}
+
+
+def test_fake_pool_kernels_are_caught():
+    pool = _only("maxpool")
+    caught = {c.index: c for c, _ in _sweep("F", lambda c, i: dict(_correct32(c, i), idx=_pool_scan(i["x"], last=True)[0]), pool)}
+    assert {"relu", "constant"} == {c.profile for c in caught.values()}, "the last maximum instead of the first shows under ties only"
+    assert {c.index for c in S.cases("F") if c.op == "maxpool" and c.profile == "constant" and c.H * c.W > 1} <= set(caught)
+
+    def skips_last(c, inp):      # a 2 x 2-pixel thread map over H / 2 x W / 2 instead of (H + 1) / 2 x (W + 1) / 2
+        out = _correct32(c, inp)
+        dx = out["dx_pl"].clone()
+        dx[:, 2 * (c.H // 2):], dx[:, :, 2 * (c.W // 2):] = 0.0, 0.0
+        return dict(out, dx_pl=dx)
+    caught = {c.index for c, _ in _sweep("F", skips_last, pool)}
+    odd = {c.index for c in S.cases("F") if c.op == "maxpool" and (c.H % 2 or c.W % 2)}
+    assert caught and caught <= odd and any(c.index in caught and c.H % 2 == 0 for c in S.cases("F")) and any(c.index in caught and c.W % 2 == 0 for c in S.cases("F"))
+
+    def mask_ge(c, inp):
+        out = _correct32(c, inp)
+        ind, _ = S.pool_winners(inp["x"])
+        return dict(out, dx_pl=S.pool_backward(c, ind, inp["dy"], F32, mask_out=out["y"] >= 0)[0])
+    caught = {c.index: c for c, _ in _sweep("F", mask_ge, pool)}
+    assert caught and {c.profile for c in caught.values()} <= {"relu", "constant"} and "relu" in {c.profile for c in caught.values()}
+
+
+def test_fake_batchnorm_and_layout_kernels_are_caught():
+    bn = _only("bn_train")
+
+    def biased_running_var(c, inp):
+        out = _correct32(c, inp)
+        if c.running:
+            out["rvar"] = (1.0 - c.momentum) * inp["rvar0"] + c.momentum * out["var"]
+        return out
+    caught = {c.index: c for c, _ in _sweep("F", biased_running_var, bn)}
+    assert caught and all(c.running and c.momentum > 0 and c.rows > 1 for c in caught.values())
+    assert {c.index for c in S.cases("F") if c.op == "bn_train" and c.running and c.momentum > 0 and 1 < c.rows <= 257} <= set(caught)
+
+    def uncentred_dot(c, inp):      # coldot without its shift: sum dy z where sum dy (z - mean) belongs
+        out = _correct32(c, inp)
+        if c.rows == 1:
+            return out
+        z = S._seen(None, inp["z"], c.planes, F32)
+        dy = S._seen(None, inp["dy"] * (out["y"] > 0).float() if c.relu != "none" else inp["dy"], c.planes, F32)
+        dg = out["rstd"] * (dy * z).sum(0)
+        return dict(out, dz=out["A"] * (dy - out["sumdy"] / c.rows - (z - out["mean"]) * out["rstd"] * dg / c.rows))
+    caught = {c.index: c for c, _ in _sweep("F", uncentred_dot, bn)}
+    assert {c.index for c in S.cases("F") if c.op == "bn_train" and c.rows > 2 and int(c.profile[6:]) >= 30} <= set(caught), sorted(caught)
+
+    def drops_shift(c, inp):      # dz = A dy without B + Cc z: caught at every row count, the two-row cases (judged by the kernel's form) included
+        out = _correct32(c, inp)
+        if c.rows > 1:
+            out["dz"] = out["A"] * S._seen(None, inp["dy"] * (out["y"] > 0).float() if c.relu != "none" else inp["dy"], c.planes, F32)
+        return out
+    caught = {c.index for c, _ in _sweep("F", drops_shift, bn)}
+    assert caught == {c.index for c in S.cases("F") if c.op == "bn_train" and c.rows > 1} and any(c.rows == 2 and c.index in caught for c in S.cases("F"))
+
+    def padding_unwritten(c, inp):
+        out = _correct32(c, inp)
+        y = torch.full_like(out["nhwc"], float("nan"))
+        y[..., :c.C] = out["nhwc"][..., :c.C]
+        return dict(out, nhwc=y)
+    caught = {c.index for c, _ in _sweep("F", padding_unwritten, _only("layout"))}
+    assert caught and caught == {c.index for c in S.cases("F") if c.op == "layout" and c.Cpad > c.C}
