@@ -693,11 +693,7 @@ class JointContrastiveTrainer:
         if self.loss == "sigmoid":
             theta, b = (self.logit_scale, self.logit_bias) if self.logit_scale is not None else self._sigmoid_consts
             return Fh.sigmoid_pairs_loss(img, txt, theta, b, self.group, keys=keys)
-        if self.logit_scale is not None:
-            return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys, log_scale=self.logit_scale)
-        if keys is None:
-            return Fh.infonce_loss(img, txt, self.temperature, self.group)
-        return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys)
+        return Fh.infonce_loss(img, txt, self.temperature, self.group, keys=keys, log_scale=self.logit_scale)
 
     def _gradient(self, images, input_ids, attention_mask, labels, keys) -> torch.Tensor:
         """Everything of a step up to and including the gradient all-reduce -> the loss; afterwards the flat gradient buffer holds the

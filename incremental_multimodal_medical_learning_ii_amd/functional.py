@@ -192,7 +192,8 @@ def posneg_bce_loss(cosv: torch.Tensor, labels: torch.Tensor, diff: bool = True,
 
 
 # --------------------------------------------------------------------------------------------------------------
-# InfoNCE (north star)
+# The global-batch loss heads: InfoNCE (north star), pairwise sigmoid, similarity distillation.
+# One protocol (`_shard` .. `_backward_tail`), then the three heads with what is their own.
 # --------------------------------------------------------------------------------------------------------------
 
 def _all_gather_rows(t: torch.Tensor, group) -> torch.Tensor:
@@ -211,22 +212,161 @@ def _all_gather_rows(t: torch.Tensor, group) -> torch.Tensor:
     return out
 
 
+def _shard(group) -> Tuple[bool, int, int]:
+    """(data parallel?, this rank, number of ranks).  A step is data parallel with an explicit `group`, or with an initialised
+    default group of more than one rank; otherwise it is the single process (False, 0, 1) and reaches no collective."""
+    import torch.distributed as dist
+    if group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1):
+        return True, dist.get_rank(group), dist.get_world_size(group)
+    return False, 0, 1
+
+
+# Every check of a head's inputs runs BEFORE its first collective: a rank that raised inside loss.backward(), or after its peers
+# had entered a gather, would leave them waiting in the collective.
+
+def _check_pairs(what: str, img: torch.Tensor, txt: torch.Tensor, world: int) -> Tuple[int, int]:
+    """(B, D) of this rank's [B, D] image and text embeddings; `what` is the public function the message names"""
+    if img.dim() != 2 or tuple(txt.shape) != tuple(img.shape):
+        raise ValueError(f"{what}: image embeddings are {tuple(img.shape)} but text embeddings {tuple(txt.shape)}")
+    B, D = img.shape
+    if (B * world) % 4 != 0 or D % 4 != 0:
+        # the backward GEMMs contract over the global batch with 16-byte row accesses
+        raise ValueError(f"{what}: global batch {B * world} (= {B} rows x {world} ranks) and embedding size {D} must be "
+                         f"multiples of 4 (drop or pad the ragged last batch)")
+    return B, D
+
+
+def _check_keys(what: str, keys, B: int, device) -> Optional[torch.Tensor]:
+    if keys is None:
+        return None
+    if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
+        raise ValueError(f"{what}: keys must be an int64 tensor, got {getattr(keys, 'dtype', type(keys).__name__)}")
+    if tuple(keys.shape) != (B,):
+        raise ValueError(f"{what}: keys must have shape ({B},), one per local row, got {tuple(keys.shape)}")
+    if keys.device != device:
+        raise ValueError(f"{what}: keys are on {keys.device} but the embeddings on {device}")
+    return keys.detach().contiguous()
+
+
+def _device_scalar(what: str, t, name: str, device) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be an fp32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
+    if t.numel() != 1 or t.dim() > 1:
+        raise ValueError(f"{what}: {name} must be 0-d or have shape (1,), got {tuple(t.shape)}")
+    if t.device != device:
+        raise ValueError(f"{what}: {name} is on {t.device} but the embeddings on {device}")
+    return t.detach()
+
+
+def _gather_normalised(embs, keys, group, shard):
+    """The data-parallel form of every head (one process per GPU): rank r owns B rows of each [B, D] tensor of `embs` (image and
+    text embeddings; the distillation head adds the teacher's two).  They are L2-normalised into the column slices of ONE [B, n D]
+    send buffer, written in place by the normalisation kernels, and ONE all-gather makes it the [Bg, n D] buffer of the global
+    batch, which the GEMMs read through its column slices (row stride n D): no cat / contiguous copies.  With the per-row statistics
+    a head exchanges on top (none, or a few floats per row), every rank then holds what it needs to form the exact gradient of the
+    global-mean loss w.r.t. its own rows: no reduce-scatter of embedding gradients and no second matmul exchange.
+    `keys` (int64 [B] or None) are gathered next to the embeddings, one more all-gather: row keys of a block are the local slice,
+    column keys the gathered vector.  In a single process the local tensors stand in for the gathered ones.
+
+    -> ([(xhat, norm, xhat_all) per tensor of `embs`], keys_all, the offset rank * B of this rank's rows in the global batch, Bg);
+    the order is: every normalisation, the embedding gather, the keys gather."""
+    on, rank, world = shard
+    B, D = embs[0].shape
+    cols = [slice(q * D, (q + 1) * D) for q in range(len(embs))]
+    send = torch.empty(B, len(embs) * D, dtype=torch.float32, device=embs[0].device) if on else None
+    local = [K.l2norm_fwd(e, out=send[:, c] if on else None) for e, c in zip(embs, cols)]
+    if on:
+        every = _all_gather_rows(send, group)                                        # [Bg, n D]
+        keys_all = _all_gather_rows(keys, group) if keys is not None else None      # [Bg] int64
+        gathered = [every[:, c] for c in cols]
+    else:
+        keys_all, gathered = keys, [xhat for xhat, _ in local]
+    return [(xhat, norm, xhat_all) for (xhat, norm), xhat_all in zip(local, gathered)], keys_all, rank * B, B * world
+
+
+def _logit_blocks(im, tx, alpha: float):
+    """The two [B, Bg] logits blocks of a rank, from the (xhat, norm, xhat_all) triples of the image and the text side:
+    S1 = alpha * local images x all texts, S2 = alpha * local texts x all images.  Row i of S1 is row `off + i` of the global
+    S = I_hat T_hat^T, row i of S2 the same row of S^T: column j of S1 is text j over all images, so its statistics are row j's of
+    the global S2, and the other way round."""
+    (ih, _, ih_all), (th, _, th_all) = im, tx
+    B, D = ih.shape
+    Bg = ih_all.shape[0]
+    S1 = torch.empty(B, Bg, dtype=torch.float32, device=ih.device)
+    S2 = torch.empty(B, Bg, dtype=torch.float32, device=ih.device)
+    K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=alpha)
+    K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=alpha)
+    return S1, S2
+
+
+def _scalar_grad(p, part1, part2, upstream, scale: float):
+    """d p = upstream * scale * (sum part1 + sum part2) for a one-element parameter, straight into a leaf's `.grad` (the flat
+    gradient buffer's slot) when it has one of its own layout: autograd then adds nothing and gets None.  Any other `p` gets a
+    fresh tensor, returned to autograd."""
+    sink = GradSink([p])
+    dst, accumulate = sink.dst(0, force_fresh=not p.is_leaf)
+    K.logit_scale_grad(part1, part2, upstream, scale, dst, accumulate)
+    return sink.result()[0]
+
+
+def _backward_tail(S1, S2, im, tx, alpha: float, gloss, scalars=()):
+    """From the gradient blocks a head left in S1 / S2 to the gradients of this rank's unnormalised embeddings:
+    d I_hat = alpha * S1 @ T_hat_all and d T_hat = alpha * S2 @ I_hat_all (the GEMMs contract over the global batch), back through
+    the normalisation, times the upstream scalar, which is read on the device.  `scalars`: the head's one-element parameters, each
+    as (p, part1, part2, scale) for `_scalar_grad` or None for no gradient; they are formed between the two.
+    -> (d img, d txt, [d p per entry of `scalars`])"""
+    (ih, inorm, ih_all), (th, tnorm, th_all) = im, tx
+    B, D = ih.shape
+    Bg = S1.shape[1]
+    dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
+    dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
+    K.gemm(S1, th_all, dih, B, D, Bg, False, False, alpha=alpha)
+    K.gemm(S2, ih_all, dth, B, D, Bg, False, False, alpha=alpha)
+    di, dt = (K.l2norm_bwd(d, xhat, norm) for d, xhat, norm in ((dih, ih, inorm), (dth, th, tnorm)))
+    g = gloss.reshape(()).contiguous()
+    dscalars = [None if s is None else _scalar_grad(s[0], s[1], s[2], g, s[3]) for s in scalars]
+    return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), dscalars
+
+
+def _infonce_stats(S, off, keys, keys_all, theta, loss, loss_scale: float):
+    """(row log-sum-exp, positives per row or None) of one logits block; its share of the loss is added into `loss`.  The four
+    kernels: plain or keyed targets, S as it stands or, with a learnable temperature, exp(theta) * S."""
+    kw = dict(loss_out=loss, loss_scale=loss_scale, loss_accumulate=True)
+    if keys is None:
+        lse, _ = K.infonce_row_lse(S, off, **kw) if theta is None else K.infonce_row_lse_scaled(S, off, theta, **kw)
+        return lse, None
+    lse, _, npos = (K.multipos_row_stats(S, keys, keys_all, **kw) if theta is None else
+                    K.multipos_row_stats_scaled(S, keys, keys_all, theta, **kw))
+    return lse, npos
+
+
+def _infonce_grad(S, off, keyed, theta, lse_row, lse_col):
+    """S <- G = softmax_row + softmax_col - 2 * targets in place (`keyed`: None, or (keys, keys_all, positives per row)).  With a
+    learnable temperature the block is left as exp(theta) * G and the partial sums of G o S are returned; otherwise None."""
+    if theta is None:
+        if keyed is None:
+            K.infonce_grad_inplace(S, off, lse_row, lse_col)
+        else:
+            K.multipos_grad_inplace(S, *keyed, lse_row, lse_col)
+        return None
+    if keyed is None:
+        return K.infonce_grad_scaled_inplace(S, off, lse_row, lse_col, theta)[1]
+    return K.multipos_grad_scaled_inplace(S, *keyed, lse_row, lse_col, theta)[1]
+
+
 class _InfoNCE(torch.autograd.Function):
     """loss = ( CE(S, diag) + CE(S^T, diag) ) / 2 with S = I_hat T_hat^T / tau over the GLOBAL batch.
 
-    Data-parallel form (one process per GPU): rank r owns B rows of I and T.  One all-gather of the normalised
-    [B, 2D] embeddings and one of the [B, 2] log-sum-exps is all the communication: every rank then holds what it
-    needs to form the exact gradient of the global-mean loss w.r.t. its own rows — no reduce-scatter of embedding
-    gradients and no second matmul exchange.
+    Data-parallel form: `_gather_normalised`, plus one all-gather each of the two [B] row log-sum-exps (the column statistics of
+    the other block) and the scalar all-reduce of the reported loss.
 
     With `keys` (int64 [B], one per local pair; image i and text i share it) the targets are multi-positive: the positives of
     row i are the columns j of the global batch with k_j = k_i (n_i of them, i itself included), and
         loss = 1/(2 Bg) sum_i [ lse_row_i - 1/n_i sum_{j in P(i)} S_ij ]  +  the same over the columns,
         dL/dS_ij = ( softmax_row_ij + softmax_col_ij - 2 [k_i = k_j] / n_i ) / (2 Bg).
-    Data-parallel: one more all-gather, of the [B] keys, issued next to the embedding gather.  The row keys of S1 and S2 are the
-    local slice, the column keys the gathered vector, and n_i comes from the stats kernel (it counts against the global columns).
-    Because a key belongs to a PAIR, entry (i, j) matches exactly when (j, i) does, so the column count of a matching entry equals
-    its row count (n_j = n_i): the column term needs no exchange of counts.  With all keys distinct this is the plain loss.
+    n_i comes from the stats kernel (it counts against the global columns).  Because a key belongs to a PAIR, entry (i, j) matches
+    exactly when (j, i) does, so the column count of a matching entry equals its row count (n_j = n_i): the column term needs no
+    exchange of counts.  With all keys distinct this is the plain loss.
 
     With `log_scale` (theta = log(1/tau), a one-element fp32 device tensor, differentiable) the temperature is LEARNED
     (DESIGN.md §5.3): `temperature` is ignored, the logits GEMMs run with alpha = 1 and the *_scaled kernels form
@@ -242,129 +382,41 @@ class _InfoNCE(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, txt, temperature, group, keys=None, log_scale=None):
         import torch.distributed as dist
-        dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         img, txt = img.detach().contiguous(), txt.detach().contiguous()
-        B, D = img.shape
-        if tuple(txt.shape) != (B, D):
-            raise ValueError(f"infonce_loss: image embeddings are {tuple(img.shape)} but text embeddings {tuple(txt.shape)}")
-        world_ = dist.get_world_size(group) if dist_on else 1
-        if (B * world_) % 4 != 0 or D % 4 != 0:
-            # the backward GEMMs contract over the global batch with 16-byte row accesses; fail HERE, before any collective
-            # is issued, not inside loss.backward() with the other ranks already waiting in the gradient all-reduce
-            raise ValueError(f"infonce_loss: global batch {B * world_} (= {B} rows x {world_} ranks) and embedding size {D} must be "
-                             f"multiples of 4 (drop or pad the ragged last batch)")
-        if keys is not None:
-            # the same rule: a bad `keys` fails on this rank before any collective is issued
-            if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
-                raise ValueError(f"infonce_loss: keys must be an int64 tensor, got {getattr(keys, 'dtype', type(keys).__name__)}")
-            if tuple(keys.shape) != (B,):
-                raise ValueError(f"infonce_loss: keys must have shape ({B},), one per local row, got {tuple(keys.shape)}")
-            if keys.device != img.device:
-                raise ValueError(f"infonce_loss: keys are on {keys.device} but the embeddings on {img.device}")
-            keys = keys.detach().contiguous()
-        theta = None
-        if log_scale is not None:
-            # and again: a bad `log_scale` fails on this rank before any collective is issued
-            if not isinstance(log_scale, torch.Tensor) or log_scale.dtype != torch.float32:
-                raise ValueError(f"infonce_loss: log_scale must be an fp32 tensor, got {getattr(log_scale, 'dtype', type(log_scale).__name__)}")
-            if log_scale.numel() != 1 or log_scale.dim() > 1:
-                raise ValueError(f"infonce_loss: log_scale must be 0-d or have shape (1,), got {tuple(log_scale.shape)}")
-            if log_scale.device != img.device:
-                raise ValueError(f"infonce_loss: log_scale is on {log_scale.device} but the embeddings on {img.device}")
-            theta = log_scale.detach()
-        if dist_on:
-            # image and text halves of ONE [B, 2D] send buffer, written in place by the normalisation kernels; the gathered
-            # [Bg, 2D] buffer is read by the GEMMs through its column halves (row stride 2D): no cat / contiguous copies
-            rank, world = dist.get_rank(group), dist.get_world_size(group)
-            send = torch.empty(B, 2 * D, dtype=torch.float32, device=img.device)
-            ih, inorm = K.l2norm_fwd(img, out=send[:, :D])
-            th, tnorm = K.l2norm_fwd(txt, out=send[:, D:])
-            both = _all_gather_rows(send, group)                           # [Bg, 2D]
-            keys_all = _all_gather_rows(keys, group) if keys is not None else None      # [Bg] int64
-            ih_all, th_all = both[:, :D], both[:, D:]
-        else:
-            rank, world = 0, 1
-            ih, inorm = K.l2norm_fwd(img)
-            th, tnorm = K.l2norm_fwd(txt)
-            ih_all, th_all = ih, th
-            keys_all = keys
-        Bg = B * world
-        off = rank * B
+        shard = _shard(group)
+        B, D = _check_pairs("infonce_loss", img, txt, shard[2])
+        keys = _check_keys("infonce_loss", keys, B, img.device)
+        theta = None if log_scale is None else _device_scalar("infonce_loss", log_scale, "log_scale", img.device)
+        (im, tx), keys_all, off, Bg = _gather_normalised((img, txt), keys, group, shard)
         inv_tau = 1.0 if theta is not None else 1.0 / float(temperature)    # learnable: the kernels scale by exp(theta)
-        S1 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local images x all texts
-        S2 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local texts  x all images
-        K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=inv_tau)
-        K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=inv_tau)
+        S1, S2 = _logit_blocks(im, tx, inv_tau)
         loss = torch.zeros((), dtype=torch.float32, device=img.device)
-        if theta is not None and keys is None:
-            lse1, _ = K.infonce_row_lse_scaled(S1, off, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-            lse2, _ = K.infonce_row_lse_scaled(S2, off, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-            npos = None
-        elif theta is not None:
-            lse1, _, npos = K.multipos_row_stats_scaled(S1, keys, keys_all, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-            lse2, _, _ = K.multipos_row_stats_scaled(S2, keys, keys_all, theta, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-        elif keys is None:
-            lse1, _ = K.infonce_row_lse(S1, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-            lse2, _ = K.infonce_row_lse(S2, off, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-            npos = None
-        else:
-            lse1, _, npos = K.multipos_row_stats(S1, keys, keys_all, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-            lse2, _, _ = K.multipos_row_stats(S2, keys, keys_all, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-        if dist_on:
+        lse1, npos = _infonce_stats(S1, off, keys, keys_all, theta, loss, 0.5 / Bg)
+        lse2, _ = _infonce_stats(S2, off, keys, keys_all, theta, loss, 0.5 / Bg)
+        if shard[0]:
             dist.all_reduce(loss, group=group)
             lse1_all, lse2_all = _all_gather_rows(lse1, group), _all_gather_rows(lse2, group)   # [Bg] each (4 KiB per rank)
         else:
             lse1_all, lse2_all = lse1, lse2
         # theta is saved as the parameter itself, not a copy: the backward reads it again and writes into its `.grad`, and autograd's
         # version check refuses a theta that was updated in place between forward and backward
-        ctx.save_for_backward(S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm, log_scale)
+        ctx.save_for_backward(S1, S2, lse1, lse2, lse1_all, lse2_all, *im, *tx, log_scale)
         ctx.meta = (off, inv_tau, Bg)
         ctx.keys = None if keys is None else (keys, keys_all, npos)   # integer / count tensors: not autograd inputs or outputs
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        S1, S2, lse1, lse2, lse1_all, lse2_all, ih, th, ih_all, th_all, inorm, tnorm, log_scale = ctx.saved_tensors
+        S1, S2, lse1, lse2, lse1_all, lse2_all, ih, inorm, ih_all, th, tnorm, th_all, log_scale = ctx.saved_tensors
         off, inv_tau, Bg = ctx.meta
-        B, D = ih.shape
-        # dL/dS_ij = (softmax_row + softmax_col - 2*delta) / (2 Bg); fold 1/tau and the upstream scalar into alpha
-        parts = None
-        if log_scale is not None and ctx.keys is None:
-            theta = log_scale.detach()
-            parts = (K.infonce_grad_scaled_inplace(S1, off, lse1, lse2_all, theta)[1], K.infonce_grad_scaled_inplace(S2, off, lse2, lse1_all, theta)[1])
-        elif log_scale is not None:
-            theta = log_scale.detach()
-            keys, keys_all, npos = ctx.keys
-            parts = (K.multipos_grad_scaled_inplace(S1, keys, keys_all, npos, lse1, lse2_all, theta)[1],
-                     K.multipos_grad_scaled_inplace(S2, keys, keys_all, npos, lse2, lse1_all, theta)[1])
-        elif ctx.keys is None:
-            K.infonce_grad_inplace(S1, off, lse1, lse2_all)
-            K.infonce_grad_inplace(S2, off, lse2, lse1_all)
-        else:
-            keys, keys_all, npos = ctx.keys
-            K.multipos_grad_inplace(S1, keys, keys_all, npos, lse1, lse2_all)
-            K.multipos_grad_inplace(S2, keys, keys_all, npos, lse2, lse1_all)
-        c = inv_tau * 0.5 / Bg
-        dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
-        dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
-        K.gemm(S1, th_all, dih, B, D, Bg, False, False, alpha=c)
-        K.gemm(S2, ih_all, dth, B, D, Bg, False, False, alpha=c)
-        di = K.l2norm_bwd(dih, ih, inorm)
-        dt = K.l2norm_bwd(dth, th, tnorm)
-        g = gloss.reshape(()).contiguous()
-        dtheta = None
-        if parts is not None and ctx.needs_input_grad[5]:
-            # straight into theta's `.grad` (the flat gradient buffer's slot) when it is a leaf that has one: autograd then adds
-            # nothing.  A non-leaf theta gets a fresh tensor, returned to autograd
-            if log_scale.is_leaf:
-                sink = GradSink([log_scale])
-                dst, accumulate = sink.dst(0)
-                K.logit_scale_grad(parts[0], parts[1], g, 0.25 / Bg, dst, accumulate)
-                dtheta = sink.result()[0]
-            else:
-                dtheta = torch.empty_like(log_scale)
-                K.logit_scale_grad(parts[0], parts[1], g, 0.25 / Bg, dtheta, False)
-        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None, None, dtheta
+        theta = None if log_scale is None else log_scale.detach()
+        # dL/dS_ij = (softmax_row + softmax_col - 2*delta) / (2 Bg); fold 1/tau into alpha
+        part1 = _infonce_grad(S1, off, ctx.keys, theta, lse1, lse2_all)
+        part2 = _infonce_grad(S2, off, ctx.keys, theta, lse2, lse1_all)
+        want_theta = theta is not None and ctx.needs_input_grad[5]
+        di, dt, (dtheta,) = _backward_tail(S1, S2, (ih, inorm, ih_all), (th, tnorm, th_all), inv_tau * 0.5 / Bg, gloss,
+                                           [(log_scale, part1, part2, 0.25 / Bg) if want_theta else None])
+        return di, dt, None, None, None, dtheta
 
 
 def infonce_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: float = 0.07, group=None,
@@ -380,19 +432,7 @@ def infonce_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: floa
     device; `log_scale=None` is the fixed-temperature path, unchanged.  A leaf `log_scale` with a `.grad` of its own layout (a
     parameter of the flat optimiser) has its gradient added there directly; any other gets it through autograd.  It must not be
     updated in place between forward and backward (autograd's version check raises)."""
-    if log_scale is None:
-        return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys)
     return _InfoNCE.apply(img_emb, txt_emb, temperature, group, keys, log_scale)
-
-
-def _device_scalar(t, name: str, device) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"sigmoid_pairs_loss: {name} must be an fp32 tensor, got {getattr(t, 'dtype', type(t).__name__)}")
-    if t.numel() != 1 or t.dim() > 1:
-        raise ValueError(f"sigmoid_pairs_loss: {name} must be 0-d or have shape (1,), got {tuple(t.shape)}")
-    if t.device != device:
-        raise ValueError(f"sigmoid_pairs_loss: {name} is on {t.device} but the embeddings on {device}")
-    return t.detach()
 
 
 class _SigmoidPairs(torch.autograd.Function):
@@ -400,8 +440,8 @@ class _SigmoidPairs(torch.autograd.Function):
         L = 1/Bg sum_ij softplus(-x_ij) [pair (i,j) positive] + softplus(x_ij) [negative],      g = dl/dx,
         dL/dC = t g / Bg,    dL/dtheta = 1/Bg sum g (x - b),    dL/db = 1/Bg sum g.
     Positives: j is i's pair, or, with `keys`, every pair of equal keys.  Nothing is normalised over the batch, so there is no
-    log-sum-exp to exchange: the data-parallel step issues the embedding all-gather (plus the keys'), and the scalar all-reduce
-    of the reported loss.  One fused kernel per block does forward and backward: S1 = local images x all texts carries the
+    log-sum-exp to exchange: the data-parallel step issues `_gather_normalised`'s collectives and the scalar all-reduce of the
+    reported loss.  One fused kernel per block does forward and backward: S1 = local images x all texts carries the
     complete rows of g, so it also yields the loss and the d theta / d b partial sums; S2 = local texts x all images is the
     transpose coverage that the text gradient needs and yields no sums.  A key belongs to a pair, so S2 uses the same row and
     column keys.  Summed over the ranks the S1 blocks cover every (i, j) once: the sum all-reduce of the flat gradient buffer
@@ -410,84 +450,34 @@ class _SigmoidPairs(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, txt, log_scale, logit_bias, group, keys=None):
         import torch.distributed as dist
-        dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         img, txt = img.detach().contiguous(), txt.detach().contiguous()
-        if img.dim() != 2 or tuple(txt.shape) != tuple(img.shape):
-            raise ValueError(f"sigmoid_pairs_loss: image embeddings are {tuple(img.shape)} but text embeddings {tuple(txt.shape)}")
-        B, D = img.shape
-        world_ = dist.get_world_size(group) if dist_on else 1
-        # every check runs HERE, before any collective is issued (see _InfoNCE.forward)
-        if (B * world_) % 4 != 0 or D % 4 != 0:
-            raise ValueError(f"sigmoid_pairs_loss: global batch {B * world_} (= {B} rows x {world_} ranks) and embedding size {D} must "
-                             f"be multiples of 4 (drop or pad the ragged last batch)")
-        if keys is not None:
-            if not isinstance(keys, torch.Tensor) or keys.dtype != torch.int64:
-                raise ValueError(f"sigmoid_pairs_loss: keys must be an int64 tensor, got {getattr(keys, 'dtype', type(keys).__name__)}")
-            if tuple(keys.shape) != (B,):
-                raise ValueError(f"sigmoid_pairs_loss: keys must have shape ({B},), one per local row, got {tuple(keys.shape)}")
-            if keys.device != img.device:
-                raise ValueError(f"sigmoid_pairs_loss: keys are on {keys.device} but the embeddings on {img.device}")
-            keys = keys.detach().contiguous()
-        theta = _device_scalar(log_scale, "log_scale", img.device)
-        bias = _device_scalar(logit_bias, "logit_bias", img.device)
-        if dist_on:
-            rank, world = dist.get_rank(group), dist.get_world_size(group)
-            send = torch.empty(B, 2 * D, dtype=torch.float32, device=img.device)
-            ih, inorm = K.l2norm_fwd(img, out=send[:, :D])
-            th, tnorm = K.l2norm_fwd(txt, out=send[:, D:])
-            both = _all_gather_rows(send, group)                           # [Bg, 2D]
-            keys_all = _all_gather_rows(keys, group) if keys is not None else None      # [Bg] int64
-            ih_all, th_all = both[:, :D], both[:, D:]
-        else:
-            rank, world = 0, 1
-            ih, inorm = K.l2norm_fwd(img)
-            th, tnorm = K.l2norm_fwd(txt)
-            ih_all, th_all = ih, th
-            keys_all = keys
-        Bg = B * world
-        off = rank * B
-        S1 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local images x all texts
-        S2 = torch.empty(B, Bg, dtype=torch.float32, device=img.device)     # local texts  x all images
-        K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=1.0)
-        K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=1.0)
+        shard = _shard(group)
+        B, D = _check_pairs("sigmoid_pairs_loss", img, txt, shard[2])
+        keys = _check_keys("sigmoid_pairs_loss", keys, B, img.device)
+        theta = _device_scalar("sigmoid_pairs_loss", log_scale, "log_scale", img.device)
+        bias = _device_scalar("sigmoid_pairs_loss", logit_bias, "logit_bias", img.device)
+        (im, tx), keys_all, off, Bg = _gather_normalised((img, txt), keys, group, shard)
+        S1, S2 = _logit_blocks(im, tx, 1.0)
         # forward and backward of the head in one pass per block: S <- t * g
         _, parts = K.sigmoid_pairs_fwd_bwd_inplace(S1, off, keys, keys_all, theta, bias)
         K.sigmoid_pairs_fwd_bwd_inplace(S2, off, keys, keys_all, theta, bias, partials=False)
         loss = K.sigmoid_pairs_loss(parts[0], 1.0 / Bg)
-        if dist_on:
+        if shard[0]:
             dist.all_reduce(loss, group=group)
         # the two scalars are saved as the inputs themselves (their `.grad` is written in backward; autograd's version check
         # refuses one that was updated in place in between)
-        ctx.save_for_backward(S1, S2, parts, ih, th, ih_all, th_all, inorm, tnorm, log_scale, logit_bias)
+        ctx.save_for_backward(S1, S2, parts, *im, *tx, log_scale, logit_bias)
         ctx.Bg = Bg
         return loss
 
     @staticmethod
     def backward(ctx, gloss):
-        S1, S2, parts, ih, th, ih_all, th_all, inorm, tnorm, log_scale, logit_bias = ctx.saved_tensors
+        S1, S2, parts, ih, inorm, ih_all, th, tnorm, th_all, log_scale, logit_bias = ctx.saved_tensors
         Bg = ctx.Bg
-        B, D = ih.shape
-        dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
-        dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
-        K.gemm(S1, th_all, dih, B, D, Bg, False, False, alpha=1.0 / Bg)
-        K.gemm(S2, ih_all, dth, B, D, Bg, False, False, alpha=1.0 / Bg)
-        di = K.l2norm_bwd(dih, ih, inorm)
-        dt = K.l2norm_bwd(dth, th, tnorm)
-        g = gloss.reshape(()).contiguous()
-        grads = [None, None]
-        for k, (p, plane) in enumerate(((log_scale, parts[1]), (logit_bias, parts[2]))):
-            if not ctx.needs_input_grad[2 + k]:
-                continue
-            # straight into a leaf parameter's `.grad` (the flat gradient buffer's slot); a non-leaf gets a fresh tensor
-            if p.is_leaf:
-                sink = GradSink([p])
-                dst, accumulate = sink.dst(0)
-                K.logit_scale_grad(plane, None, g, 1.0 / Bg, dst, accumulate)
-                grads[k] = sink.result()[0]
-            else:
-                grads[k] = torch.empty_like(p)
-                K.logit_scale_grad(plane, None, g, 1.0 / Bg, grads[k], False)
-        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), grads[0], grads[1], None, None
+        scalars = [(p, plane, None, 1.0 / Bg) if ctx.needs_input_grad[2 + k] else None
+                   for k, (p, plane) in enumerate(((log_scale, parts[1]), (logit_bias, parts[2])))]
+        di, dt, (dtheta, dbias) = _backward_tail(S1, S2, (ih, inorm, ih_all), (th, tnorm, th_all), 1.0 / Bg, gloss, scalars)
+        return di, dt, dtheta, dbias, None, None
 
 
 def sigmoid_pairs_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, log_scale: torch.Tensor, logit_bias: torch.Tensor, group=None,
@@ -509,87 +499,47 @@ class _Distill(torch.autograd.Function):
         L_d = 1/(2 Bg) [ sum_i KL(pt_i || p_i) + sum_j KL(qt_j || q_j) ],      dL_d/dS_ij = (p_ij - pt_ij + q_ij - qt_ij) / (2 Bg).
     Returns (weight * L_d, L_d); only the first is differentiable, and only with respect to the student's embeddings.
 
-    Data-parallel form, `_InfoNCE`'s protocol with the teacher riding along: ONE all-gather of a [B, 4D] send buffer whose quarters
-    the four normalisations write in place, ONE all-gather of the [B, 4] log-sum-exps (student rows, student columns, teacher rows,
-    teacher columns) and the scalar all-reduce of the loss; every rank then forms the exact gradient for its own rows."""
+    Data-parallel form: `_gather_normalised` with the teacher riding along (a [B, 4D] send buffer), ONE all-gather of the [B, 4]
+    log-sum-exps (student rows, student columns, teacher rows, teacher columns) and the scalar all-reduce of the loss."""
 
     @staticmethod
     def forward(ctx, img, txt, img_t, txt_t, temperature, weight, group):
         import torch.distributed as dist
-        dist_on = group is not None or (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
         img, txt = img.detach().contiguous(), txt.detach().contiguous()
         img_t, txt_t = img_t.detach().contiguous(), txt_t.detach().contiguous()
-        if img.dim() != 2 or tuple(txt.shape) != tuple(img.shape):
-            raise ValueError(f"distill_loss: image embeddings are {tuple(img.shape)} but text embeddings {tuple(txt.shape)}")
-        B, D = img.shape
+        shard = _shard(group)
+        B, D = _check_pairs("distill_loss", img, txt, shard[2])
         if tuple(img_t.shape) != (B, D) or tuple(txt_t.shape) != (B, D):
             raise ValueError(f"distill_loss: the student's embeddings are {(B, D)} but the teacher's {tuple(img_t.shape)} and "
                              f"{tuple(txt_t.shape)}")
-        world_ = dist.get_world_size(group) if dist_on else 1
-        if (B * world_) % 4 != 0 or D % 4 != 0:
-            # as in _InfoNCE: fail HERE, before any collective is issued
-            raise ValueError(f"distill_loss: global batch {B * world_} (= {B} rows x {world_} ranks) and embedding size {D} must be "
-                             f"multiples of 4 (drop or pad the ragged last batch)")
-        dev = img.device
-        if dist_on:
-            rank, world = dist.get_rank(group), dist.get_world_size(group)
-            send = torch.empty(B, 4 * D, dtype=torch.float32, device=dev)
-            ih, inorm = K.l2norm_fwd(img, out=send[:, :D])
-            th, tnorm = K.l2norm_fwd(txt, out=send[:, D:2 * D])
-            iht, _ = K.l2norm_fwd(img_t, out=send[:, 2 * D:3 * D])
-            tht, _ = K.l2norm_fwd(txt_t, out=send[:, 3 * D:])
-            every = _all_gather_rows(send, group)                                                  # [Bg, 4D]
-            ih_all, th_all, iht_all, tht_all = (every[:, q * D:(q + 1) * D] for q in range(4))
-        else:
-            rank, world = 0, 1
-            ih, inorm = K.l2norm_fwd(img)
-            th, tnorm = K.l2norm_fwd(txt)
-            iht, _ = K.l2norm_fwd(img_t)
-            tht, _ = K.l2norm_fwd(txt_t)
-            ih_all, th_all, iht_all, tht_all = ih, th, iht, tht
-        Bg = B * world
+        (im, tx, im_t, tx_t), _, _, Bg = _gather_normalised((img, txt, img_t, txt_t), None, group, shard)
         inv_tau = 1.0 / float(temperature)
-        S1 = torch.empty(B, Bg, dtype=torch.float32, device=dev)      # local images x all texts
-        S2 = torch.empty(B, Bg, dtype=torch.float32, device=dev)      # local texts  x all images
-        T1 = torch.empty(B, Bg, dtype=torch.float32, device=dev)      # the teacher's two blocks
-        T2 = torch.empty(B, Bg, dtype=torch.float32, device=dev)
-        K.gemm(ih, th_all, S1, B, Bg, D, False, True, alpha=inv_tau)
-        K.gemm(th, ih_all, S2, B, Bg, D, False, True, alpha=inv_tau)
-        K.gemm(iht, tht_all, T1, B, Bg, D, False, True, alpha=inv_tau)
-        K.gemm(tht, iht_all, T2, B, Bg, D, False, True, alpha=inv_tau)
-        loss = torch.zeros((), dtype=torch.float32, device=dev)
+        S1, S2 = _logit_blocks(im, tx, inv_tau)
+        T1, T2 = _logit_blocks(im_t, tx_t, inv_tau)                   # the teacher's two blocks
+        loss = torch.zeros((), dtype=torch.float32, device=img.device)
         lse1, lt1, _ = K.distill_row_stats(S1, T1, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
         lse2, lt2, _ = K.distill_row_stats(S2, T2, loss_out=loss, loss_scale=0.5 / Bg, loss_accumulate=True)
-        if dist_on:
+        if shard[0]:
             dist.all_reduce(loss, group=group)
             lse_all = _all_gather_rows(torch.stack((lse1, lse2, lt1, lt2), dim=1), group).t().contiguous()    # [4, Bg]
             lse1_all, lse2_all, lt1_all, lt2_all = lse_all[0], lse_all[1], lse_all[2], lse_all[3]
         else:
             lse1_all, lse2_all, lt1_all, lt2_all = lse1, lse2, lt1, lt2
-        ctx.save_for_backward(S1, S2, T1, T2, lse1, lse2, lt1, lt2, lse1_all, lse2_all, lt1_all, lt2_all, ih, th, ih_all, th_all,
-                              inorm, tnorm)
-        ctx.meta = (float(weight) * inv_tau * 0.5 / Bg, Bg)
+        ctx.save_for_backward(S1, S2, T1, T2, lse1, lse2, lt1, lt2, lse1_all, lse2_all, lt1_all, lt2_all, *im, *tx)
+        ctx.alpha = float(weight) * inv_tau * 0.5 / Bg
         weighted = K.scale_mask(loss.reshape(1), alpha=float(weight)).reshape(())
         ctx.mark_non_differentiable(loss)
         return weighted, loss
 
     @staticmethod
     def backward(ctx, gloss, _gunweighted):
-        (S1, S2, T1, T2, lse1, lse2, lt1, lt2, lse1_all, lse2_all, lt1_all, lt2_all, ih, th, ih_all, th_all, inorm,
-         tnorm) = ctx.saved_tensors
-        c, Bg = ctx.meta
-        B, D = ih.shape
+        (S1, S2, T1, T2, lse1, lse2, lt1, lt2, lse1_all, lse2_all, lt1_all, lt2_all, ih, inorm, ih_all, th, tnorm,
+         th_all) = ctx.saved_tensors
         # column j of S1 is text j over all images: its log-sum-exp is row j's of the global S2, and the other way round
         K.distill_grad_inplace(S1, T1, lse1, lse2_all, lt1, lt2_all)
         K.distill_grad_inplace(S2, T2, lse2, lse1_all, lt2, lt1_all)
-        dih = torch.empty(B, D, dtype=torch.float32, device=ih.device)
-        dth = torch.empty(B, D, dtype=torch.float32, device=ih.device)
-        K.gemm(S1, th_all, dih, B, D, Bg, False, False, alpha=c)
-        K.gemm(S2, ih_all, dth, B, D, Bg, False, False, alpha=c)
-        di = K.l2norm_bwd(dih, ih, inorm)
-        dt = K.l2norm_bwd(dth, th, tnorm)
-        g = gloss.reshape(()).contiguous()
-        return K.scale_mask(di, alpha_dev=g, out=di), K.scale_mask(dt, alpha_dev=g, out=dt), None, None, None, None, None
+        di, dt, _ = _backward_tail(S1, S2, (ih, inorm, ih_all), (th, tnorm, th_all), ctx.alpha, gloss)
+        return di, dt, None, None, None, None, None
 
 
 def _distill_pair(img_emb, txt_emb, img_teacher, txt_teacher, temperature, weight=1.0, group=None):
