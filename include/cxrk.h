@@ -489,6 +489,59 @@ int cxrk_scale_mask(const float* x, const float* mask_src, const float* alpha_de
                     hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * mlm — the masked-language-modelling auxiliary loss of the joint step (csrc/mlm.hip): HF BertForMaskedLM's loss
+ * (the head the reference computes and discards, modelling_cxrbert.py:87-95) on tokens masked on the device by the rule of HF
+ * DataCollatorForLanguageModeling.  No entry point takes scratch memory, none uses an atomic, none synchronises: the number of rows
+ * that count travels in device memory (`stats`), and two runs on the same inputs give the same bits.
+ * mask_tokens:  ids / mask [N][L] int64 (mask may be NULL = all attended).  Token (n, t) is a CANDIDATE iff its mask is non-zero and
+ *              its id is none of special[0..nspecial) (a HOST array of at most 8 ids, copied into the launch).  Draw:
+ *                Philox4x32-10 (csrc/dropout.h), key = (seed & 0xffffffff, seed >> 32), ONE block per token with
+ *                counter = (0, row_offset + n, t, (counter & 0xffffff) << 8 | 0xF4)   (low byte 0xF4 = layer 61, site 0: no dropout
+ *                word and not the augmentation's 0xF0), output words w0..w3;
+ *                selected iff candidate and w0 < floor(p * 2^32 + 0.5);
+ *                a selected token becomes mask_id if w1 < 3435973837 (= ceil(0.8 * 2^32)), the id (w2 * V) >> 32 if
+ *                w1 < 3865470567 (= ceil(0.9 * 2^32)), and keeps its id otherwise; w3 is reserved.
+ *              The draw is a function of (seed, counter, global sequence index, token, the token's id and mask) and of nothing else: a
+ *              batch cut anywhere and masked with the matching row_offset gives the ids of the whole-batch call.
+ *              Outputs: ids_out [N][L]; the compact list in ASCENDING token order, sel[k] = index n * L + t (within the call) of the
+ *              k-th selected token and tgt[k] = its original id, for k < kept = min(selected, cap); sel[k] = tgt[k] = -1 for
+ *              kept <= k < cap; stats = {kept, selected} (selected > kept reports an overflow: the tokens past the cap stay corrupted
+ *              in ids_out and carry no loss); count_f[0] = float(kept).  block_counts: ceil(N L / 256) ints, an output of the caller
+ *              (the selected tokens per block of 256, from which every block derives its offset in a fixed order), not scratch memory.
+ *              -1 for p outside [0, 1], V outside [1, 2^31), mask_id outside [0, V), nspecial > 8, N L >= 2^31, cap outside [1, N L].
+ * gather_rows: out[r] = last[sel[r]] for r < kept, zero rows for kept <= r < cap; last [T][H] fp32; out fp32 [cap][H] (plane = 0,
+ *              H % 4 == 0) or planes (plane > 0, H % 8 == 0).  scatter_rows: dlast[sel[r]] = dx[r] for r < kept by plain stores (the
+ *              caller zeroes dlast [T][H]; sel lists no token twice).  An index outside [0, T) is skipped.
+ * xent_stats:  S [rows][ld] holds the logits WITHOUT the decoder bias of vocabulary columns [v0, v0 + cols); x = S + bias[column]
+ *              (bias = the whole [V] vector).  For every row r < kept the call folds columns [v0 + skip, v0 + cols) into
+ *              state [4][rows][64] (running maximum, sum of exp(x - maximum), best value, best column as int bits; `first` != 0: the
+ *              state is started, not read) and writes x of column tgt[r] to target_logit[r] when the chunk holds it.  Lane l of the
+ *              row's wave takes, in ascending order, the groups of four columns with (column / 4) mod 64 == l: chunk boundaries at
+ *              multiples of 4 change nothing of what a lane adds up, so the statistics do not depend on the chunk size (exact fp32
+ *              logits).  skip != 0, or v0 / cols / ld not multiples of 4: column by column, lane = column mod 64.
+ * xent_finish: per row r < kept the 64 lanes merged in a fixed order: lse[r], rowloss[r] = lse[r] - target_logit[r], hit[r] = [first
+ *              maximum of the row == tgt[r]] (a NaN is the maximum, as torch.argmax); zeros for r >= kept.  Then from one block in a
+ *              fixed order loss_out[0] = scale[0] * sum_{r < kept} rowloss[r] and correct_out[0] = sum hit.  kept = 0 gives exactly 0.
+ *              A NaN logit of a row r < kept reaches the loss; rows >= kept are never read.
+ * xent_grad:   the recomputed chunk S -> g = (exp(x - lse[r]) - [column == tgt[r]]) * upstream[0] * scale[0] * alpha for r < kept and
+ *              column >= v0 + skip, exactly 0 elsewhere (whatever S holds there); in place (G == NULL) or as planes G (row stride ldg,
+ *              lo plane gplane elements behind).  cols % 8 == 0, ld % 4 == 0 (ldg, gplane % 8 == 0), 16-byte aligned bases, else -1.
+ * stats / tgt / sel are int32; scale and upstream one fp32 each, read on the device. */
+int cxrk_mlm_mask_tokens(const long* ids, const long* mask, int N, int L, long row_offset, unsigned long long seed, unsigned counter,
+                         double p, long V, long mask_id, const long* special, int nspecial, int cap, long* ids_out, int* sel,
+                         int* tgt, int* stats, float* count_f, int* block_counts, hipStream_t stream);
+int cxrk_mlm_gather_rows(const float* last, long T, int H, const int* sel, const int* stats, int cap, void* out, long plane,
+                         hipStream_t stream);
+int cxrk_mlm_scatter_rows(const float* dx, const int* sel, const int* stats, int cap, long T, int H, float* dlast, hipStream_t stream);
+int cxrk_mlm_xent_stats(const float* S, long ld, int rows, int cols, int skip, int v0, const float* bias, const int* tgt,
+                        const int* stats, float* state, float* target_logit, int first, hipStream_t stream);
+int cxrk_mlm_xent_finish(const float* state, const float* target_logit, const int* tgt, const int* stats, int rows, const float* scale,
+                         float* lse, float* rowloss, int* hit, float* loss_out, int* correct_out, hipStream_t stream);
+int cxrk_mlm_xent_grad(float* S, long ld, void* G, long ldg, long gplane, int rows, int cols, int skip, int v0, const float* bias,
+                       const int* tgt, const int* stats, const float* lse, const float* upstream, const float* scale, float alpha,
+                       hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Optimiser / continual learning.
  * adam_fused:   torch.optim.Adam defaults (Trainer.py:172-175), one launch over a flat parameter buffer.
  * sgd:          optim.SGD (Trainer.py:176-178).

@@ -50,6 +50,10 @@ Two extensions behind the same entry points (both off unless asked for):
     a task keeps M of its rows per rank in an episodic memory; later steps take a reference gradient on rows drawn from it and project
     the step's gradient when the two conflict; `train` logs `train/agem_projected` (the fraction of the epoch's steps projected) and
     `train/agem_dot` once per epoch while active, `save` / `load` carry the memory and the sampler's step counter as `agem.pt`.
+    `"mlm_weight": w` (optionally `"mlm_probability"`, `"mlm_seed"`, `"mlm_mask_token_id"`, `"mlm_special_ids"`) adds the masked-
+    language-modelling loss of CXR-BERT's own head: every step masks its token ids on the device and trains
+    contrastive + w * L_mlm; `train` logs `train/mlm_loss` and `train/mlm_acc` once per epoch, `save` / `load` carry the (seed, step
+    counter) of the masking stream as `mlm.pt`.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -774,7 +778,10 @@ class Trainer:
 
     def _log_optimiser(self, epoch):
         """with "optim": "adamw" or a learning-rate schedule: the learning rate of the epoch's last step, and with "max_grad_norm" that
-        step's gradient norm before clipping (the one read-back of the norm), once per epoch"""
+        step's gradient norm before clipping (the one read-back of the norm), once per epoch; with "mlm_weight" the masked-language-
+        modelling loss and accuracy of the epoch's last step"""
+        # None without "mlm_weight" and before the first masked step; data parallel it all-reduces, so every rank asks, writer or not
+        mlm = self._joint.current_mlm() if self._joint is not None else None
         if self._joint is None or self.writer is None:
             return
         opt = self._joint.optimizer
@@ -789,6 +796,9 @@ class Trainer:
         distill = self._joint.current_distill()     # None without a teacher and before the first distilled step
         if distill is not None:
             self.writer.add_scalar('train/distill', distill, epoch)
+        if mlm is not None:
+            self.writer.add_scalar('train/mlm_loss', mlm["loss"], epoch)
+            self.writer.add_scalar('train/mlm_acc', mlm["accuracy"], epoch)
         agem = self._joint.current_interference()   # None without "agem_memory" and before the first step with a reference
         if agem is not None:
             proj, applied = agem["projected"] - self._agem_logged[0], agem["applied"] - self._agem_logged[1]
@@ -1030,6 +1040,9 @@ class Trainer:
                 torch.save(self._joint.ewc.state_dict(), os.path.join(self.writer.log_dir, 'ewc.pt'))
             if self._joint.teacher is not None:
                 torch.save(self._joint.teacher.state_dict(), os.path.join(self.writer.log_dir, 'teacher.pt'))
+            if self._joint.mlm_state is not None:   # plain numbers: the masking stream resumes where it stopped
+                seed, counter = self._joint.mlm_state
+                torch.save({"seed": int(seed), "counter": int(counter)}, os.path.join(self.writer.log_dir, 'mlm.pt'))
         if self._joint is not None and self._joint.memory is not None:   # every rank holds rows of its own shards
             torch.save({"memory": self._joint.memory.state_dict(), "agem": self._joint.agem.state_dict(),
                         "steps": int(self._joint.agem_steps)}, os.path.join(self.writer.log_dir, self._agem_file()))
@@ -1079,6 +1092,12 @@ class Trainer:
                 # just loaded, then take the saved tensors; size and keys are checked by `FrozenTeacher.load_state_dict`
                 self._joint.snapshot_teacher()
                 self._joint.teacher.load_state_dict(torch.load(tpath, map_location="cpu", weights_only=True))
+            if self._joint.mlm_state is not None:
+                path = os.path.join(self.writer.log_dir, 'mlm.pt')
+                sd = torch.load(path, map_location="cpu", weights_only=True)
+                if not isinstance(sd, dict) or set(sd) != {"seed", "counter"} or int(sd["counter"]) < 0 or int(sd["seed"]) < 0:
+                    raise ValueError(f"{path}: expected the keys ['counter', 'seed'] with both >= 0")
+                self._joint.mlm_state = (int(sd["seed"]), int(sd["counter"]))
             if self._joint.memory is not None:   # the memory, the projection's counters and the sampler's step counter
                 path = os.path.join(self.writer.log_dir, self._agem_file())
                 sd = torch.load(path, map_location="cpu", weights_only=True)

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_long, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_long, c_size_t, c_uint32, c_uint64, c_void_p
 from typing import Dict, List, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -105,6 +105,12 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_group_mean_bwd": (I, [P, I, I, I, P, P]),
     "cxrk_retrieval_ranks": (I, [P, L, I, P, L, I, I, I, P, P, P, P, P, P]),
     "cxrk_scale_mask": (I, [P, P, P, F, L, P, P]),
+    "cxrk_mlm_mask_tokens": (I, [P, P, I, I, L, c_uint64, c_uint32, c_double, L, L, P, I, I, P, P, P, P, P, P, P]),
+    "cxrk_mlm_gather_rows": (I, [P, L, I, P, P, I, P, L, P]),
+    "cxrk_mlm_scatter_rows": (I, [P, P, P, I, L, I, P, P]),
+    "cxrk_mlm_xent_stats": (I, [P, L, I, I, I, I, P, P, P, P, P, I, P]),
+    "cxrk_mlm_xent_finish": (I, [P, P, P, P, I, P, P, P, P, P, P, P]),
+    "cxrk_mlm_xent_grad": (I, [P, L, P, L, L, I, I, I, I, P, P, P, P, P, P, F, P]),
     "cxrk_adam_fused": (I, [P, P, P, P, L, F, F, F, F, F, I, F, P]),
     "cxrk_sgd": (I, [P, P, L, F, F, F, P]),
     "cxrk_grad_sqnorm_partials_bytes": (Z, [L]),

@@ -45,6 +45,13 @@ parameters, +4 B per parameter); from then on every step also runs the teacher's
 beta * L_d (`functional.distill_loss`) to the objective: two more collectives than the plain step's (the [B, 4D] embedding gather and
 the [B, 4] log-sum-exp gather) and one scalar all-reduce.  Before the first snapshot, and with `distill_weight=None` (the default),
 a step issues exactly the calls it always did.
+
+`mlm_weight=w`: the masked-language-modelling auxiliary loss CXR-BERT was trained with.  Every step masks its token
+ids on the device (`kernels.mlm_mask_tokens`: HF DataCollatorForLanguageModeling's rule, keyed by the global sequence index, so a
+sharded step masks as the single-process step does), runs the text encoder once on the masked ids through the full-sequence path, feeds
+the projected CLS embedding to the contrastive head and the last hidden state to `functional.mlm_loss`, and adds w * L_mlm to the
+objective as a second root of the step's one backward: one more collective than the plain step's, the scalar all-reduce of the number
+of selected tokens.  With `mlm_weight=None` (the default) a step issues exactly the calls it always did.
 """
 from __future__ import annotations
 
@@ -341,6 +348,39 @@ def check_agem_options(memory, batch, every, seed) -> tuple:
     return memory, batch, 1 if every is None else every, 0 if seed is None else seed
 
 
+MLM_PROBABILITY = 0.15                        # HF DataCollatorForLanguageModeling's default
+MLM_MASK_TOKEN_ID = 4                         # CXR-BERT's vocabulary: [PAD] 0, [UNK] 1, [CLS] 2, [SEP] 3, [MASK] 4
+MLM_SPECIAL_IDS = (0, 1, 2, 3, 4)
+
+
+def check_mlm_options(weight, probability, seed, mask_token_id, special_ids, micro_batch=None) -> tuple:
+    """(mlm_weight, mlm_probability, mlm_seed, mlm_mask_token_id, mlm_special_ids) checked, the defaults filled in (the seed stays None:
+    the constructor draws one); options given without `mlm_weight` are refused, and so is `mlm_weight` with `micro_batch`"""
+    if weight is None:
+        if any(v is not None for v in (probability, seed, mask_token_id, special_ids)):
+            raise ValueError("mlm_probability / mlm_seed / mlm_mask_token_id / mlm_special_ids are options of the masked-language-"
+                             "modelling loss; they were given without mlm_weight")
+        return None, None, None, None, None
+    if isinstance(weight, bool) or not isinstance(weight, (int, float)) or not (math.isfinite(weight) and weight >= 0):
+        raise ValueError(f"mlm_weight must be finite and >= 0, got {weight!r}")
+    if micro_batch is not None:
+        raise ValueError("mlm_weight with micro_batch is out of scope of this step: the masked-language-modelling loss needs the last "
+                         "hidden state of every chunk, which the micro-batched step does not keep; construct the trainer with "
+                         "micro_batch=None or without mlm_weight")
+    probability = MLM_PROBABILITY if probability is None else probability
+    if isinstance(probability, bool) or not isinstance(probability, (int, float)) or not 0.0 <= probability <= 1.0:
+        raise ValueError(f"mlm_probability must lie in [0, 1], got {probability!r}")
+    if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int) or seed < 0):
+        raise ValueError(f"mlm_seed must be an integer >= 0, got {seed!r}")
+    mask_token_id = MLM_MASK_TOKEN_ID if mask_token_id is None else mask_token_id
+    if isinstance(mask_token_id, bool) or not isinstance(mask_token_id, int) or mask_token_id < 0:
+        raise ValueError(f"mlm_mask_token_id must be an integer >= 0, got {mask_token_id!r}")
+    special_ids = MLM_SPECIAL_IDS if special_ids is None else tuple(special_ids)
+    if len(special_ids) > 8 or any(isinstance(s, bool) or not isinstance(s, int) or s < 0 for s in special_ids):
+        raise ValueError(f"mlm_special_ids must be at most 8 integers >= 0 (they are passed to the kernel by value), got {special_ids!r}")
+    return float(weight), float(probability), seed, mask_token_id, special_ids
+
+
 def _host_collective_device(group) -> str:
     """where the tensor of a collective on host integers has to live: RCCL moves device memory, gloo host memory"""
     import torch.distributed as dist
@@ -368,7 +408,9 @@ class JointContrastiveTrainer:
                  min_lr_ratio: Optional[float] = None, ewc_lambda: Optional[float] = None, ewc_gamma: Optional[float] = None,
                  ewc_fisher: Optional[str] = None, distill_weight: Optional[float] = None,
                  distill_temperature: Optional[float] = None, agem_memory: Optional[int] = None,
-                 agem_batch: Optional[int] = None, agem_every: Optional[int] = None, agem_seed: Optional[int] = None):
+                 agem_batch: Optional[int] = None, agem_every: Optional[int] = None, agem_seed: Optional[int] = None,
+                 mlm_weight: Optional[float] = None, mlm_probability: Optional[float] = None, mlm_seed: Optional[int] = None,
+                 mlm_mask_token_id: Optional[int] = None, mlm_special_ids: Optional[Tuple[int, ...]] = None):
         """`optim="adamw"`: `optim.AdamW` with decoupled `weight_decay` (default 0.01; parameters with ndim <= 1 do
         not decay) and, with `max_grad_norm`, clipping of the global gradient norm (`inf`: the norm is taken and reported, nothing
         is clipped).  `warmup_steps` / `total_steps` / `lr_decay` ("constant" | "linear" | "cosine") / `min_lr_ratio`: an
@@ -384,10 +426,34 @@ class JointContrastiveTrainer:
         `memory.EpisodicMemory` (seeded by `agem_seed`, default 0); once it holds rows, every `agem_every`-th step (default 1) first
         takes the gradient of `agem_batch` memory rows (default: as many as the step's shard has, at most all stored) as the
         reference, and every step projects its gradient against the stored reference (`optim.AGEM`).  Until the first `remember()`
-        a step is bit for bit the step without it."""
+        a step is bit for bit the step without it.
+        `mlm_weight` = w: the masked-language-modelling auxiliary loss.  Every step masks its token ids on the
+        device (HF DataCollatorForLanguageModeling's rule with `mlm_probability`, default 0.15, `mlm_mask_token_id`, default 4, never
+        touching `mlm_special_ids`, default (0, 1, 2, 3, 4), nor padding), runs the text encoder ONCE on the masked ids and trains
+        contrastive + w * L_mlm, L_mlm the mean cross-entropy of HF's MLM head over the selected tokens of the global batch.  It
+        implies that the head (`cls.predictions.*`) is trained.  `mlm_seed` (default: drawn from torch's CPU generator) seeds the
+        draws; `mlm_state` is the (seed, step counter) pair.  Not with `micro_batch`.  `mlm_weight=None` (the default) issues exactly
+        the calls it always did."""
         self.agem_memory, self.agem_batch, self.agem_every, self.agem_seed = check_agem_options(agem_memory, agem_batch, agem_every,
                                                                                                 agem_seed)
         self.micro_batch = check_micro_batch(micro_batch)
+        (self.mlm_weight, self.mlm_probability, mlm_seed, self.mlm_mask_token_id,
+         self.mlm_special_ids) = check_mlm_options(mlm_weight, mlm_probability, mlm_seed, mlm_mask_token_id, mlm_special_ids, self.micro_batch)
+        self._mlm, self._mlm_version, self._mlm_synced = None, 0, None      # [seed, counter] as `_augment`
+        self._mlm_off = False                # `_contrastive_only`: no masking, the counter stays
+        self._mlm_call = None                # the `kernels.MlmMask` of the forward that is running
+        self._pending_mlm = None             # w * L_mlm of the forward whose backward has not run yet
+        self._last_mlm = None                # (L_mlm share of this rank, correct, stats, 1 / M_global) of the last step, on the device
+        self.mlm_chunk_bytes = Fh.MLM_CHUNK_BYTES
+        if self.mlm_weight is not None:
+            train_mlm_head = True
+            self._mlm_vocab = int(text_model.config.vocab_size)
+            if self.mlm_mask_token_id >= self._mlm_vocab:
+                raise ValueError(f"mlm_mask_token_id {self.mlm_mask_token_id} is outside the vocabulary of {self._mlm_vocab} ids")
+            if mlm_seed is None:
+                w = torch.randint(0, 2 ** 32, (2,), dtype=torch.int64)
+                mlm_seed = (int(w[0]) << 32) | int(w[1])
+            self.mlm_state = (mlm_seed, 0)
         self.distill_weight, self.distill_temperature = check_distill_options(distill_weight, distill_temperature)
         self.teacher: Optional[FrozenTeacher] = None
         self._distill_off = False            # `consolidate` estimates the Fisher diagonal of the contrastive loss alone
@@ -491,6 +557,7 @@ class JointContrastiveTrainer:
         self._dropout_synced = None
         self.sync_dropout_state()
         self.sync_augment_state()
+        self.sync_mlm_state()
         self._spans = self.reduce_spans(inamed, tparams) if self.world > 1 else {}
 
     def current_temperature(self) -> float:
@@ -544,9 +611,93 @@ class JointContrastiveTrainer:
         self._augment = list(_broadcast_state(*self._augment, self.group))
         self._augment_synced = self._augment_version
 
+    # ------------------------------------------------------------------ masked-language-modelling loss
+    @property
+    def mlm_state(self) -> Optional[Tuple[int, int]]:
+        """(seed, step counter) of the next masked `step`; None without `mlm_weight`.  Assign a pair to resume or repeat a stream.  The
+        kernel keys the draws by the low 24 bits of the counter."""
+        return None if self._mlm is None else (self._mlm[0], self._mlm[1])
+
+    @mlm_state.setter
+    def mlm_state(self, state: Tuple[int, int]) -> None:
+        if self.mlm_weight is None:
+            raise RuntimeError("mlm_state: this trainer was constructed without mlm_weight")
+        seed, counter = state
+        if int(counter) < 0:
+            raise ValueError("mlm_state: the step counter must be >= 0")
+        self._mlm = [int(seed) & (2 ** 64 - 1), int(counter)]
+        self._mlm_version += 1
+
+    def sync_mlm_state(self) -> None:
+        """Token masking under data parallelism: every rank takes rank 0's (seed, counter), exactly as `sync_augment_state` does; with
+        the row offset of `step` the draws of a sharded step are those of the single-process step on the global batch.  It
+        communicates only when `mlm_state` was assigned since the last time (on every rank, in the same program order)."""
+        if self.world == 1 or self._mlm is None or self._mlm_version == self._mlm_synced:
+            return
+        self._mlm = list(_broadcast_state(*self._mlm, self.group))
+        self._mlm_synced = self._mlm_version
+
+    def _masking(self) -> bool:
+        return self._mlm is not None and not self._mlm_off
+
+    def _mask_tokens(self, input_ids, attention_mask) -> K.MlmMask:
+        """this step's draw, once, before the encoders: row offset = this rank's first global row, the counter advances once"""
+        seed, counter = self._mlm
+        self._mlm[1] = counter + 1
+        input_ids = input_ids if input_ids.dtype == torch.int64 else input_ids.to(torch.int64)
+        if attention_mask is not None and attention_mask.dtype != torch.int64:
+            attention_mask = attention_mask.to(torch.int64)
+        return K.mlm_mask_tokens(input_ids, attention_mask, seed, counter, self.mlm_probability, self._mlm_vocab, self.mlm_mask_token_id,
+                                 self.mlm_special_ids, row_offset=self.rank * int(input_ids.shape[0]))
+
+    def _mlm_head(self, last: torch.Tensor, m: K.MlmMask) -> None:
+        """w * L_mlm on the last hidden state of the masked ids (on the stream the text encoder ran on): it waits in `_pending_mlm` for
+        the step's one backward.  The mean runs over the selected tokens of the GLOBAL batch: one scalar all-reduce of the count."""
+        count = m.count
+        if self.world > 1:
+            import torch.distributed as dist
+            count = count.clone()
+            if count.is_cuda and dist.get_backend(self.group) == "gloo":      # rehearsals of the N > 1 path (see `_all_gather_rows`)
+                host = count.cpu()
+                dist.all_reduce(host, group=self.group)
+                count.copy_(host)
+            else:
+                dist.all_reduce(count, group=self.group)
+        scale = torch.reciprocal(torch.clamp(count, min=1.0))                  # 1 / max(M_global, 1), never read on the host
+        weighted, loss, correct = Fh._mlm_triple(last, m.sel, m.tgt, m.stats, self.text_model.mlm_head_params(), scale,
+                                                 self.mlm_chunk_bytes, self.mlm_weight, self.text_model.config.layer_norm_eps)
+        self._pending_mlm = weighted if (self.mlm_weight > 0 and weighted.requires_grad) else None
+        self._last_mlm = (loss, correct, m.stats, count)
+
+    def current_mlm(self) -> Optional[dict]:
+        """{"loss", "accuracy", "masked", "overflowed"} of the last masked step as host numbers (None without `mlm_weight` or before the
+        first such step): L_mlm, the fraction of the counted tokens whose arg-max is the original id, the tokens counted and the
+        selected tokens that found no slot, all over the global batch.  A host sync -- and, data parallel, one all-reduce of four
+        numbers, so every rank has to call it -- and only when called."""
+        if self._last_mlm is None:
+            return None
+        loss, correct, stats, _ = self._last_mlm
+        t = torch.stack((loss.double().reshape(()), correct[0].double(), stats[0].double(), (stats[1] - stats[0]).double()))
+        if self.world > 1:
+            import torch.distributed as dist
+            t = t.to(_host_collective_device(self.group))
+            dist.all_reduce(t, group=self.group)
+        loss, correct, kept, over = (float(v) for v in t.cpu())
+        return {"loss": loss, "accuracy": correct / kept if kept > 0 else float("nan"), "masked": int(kept), "overflowed": int(over)}
+
     def _step_forward_loss(self, images, input_ids, attention_mask, labels, keys) -> torch.Tensor:
         """`forward_loss` of one `step`: with an augment spec the image model carries this step's call descriptor while its forward
-        runs (row offset = this rank's first global row; the shards are equal and contiguous), and the counter advances once."""
+        runs (row offset = this rank's first global row; the shards are equal and contiguous), and the counter advances once.  With
+        `mlm_weight` the token ids are masked first, once (`forward_loss` finds the draw in `_mlm_call`)."""
+        if self._masking():
+            self._mlm_call = self._mask_tokens(input_ids, attention_mask)
+            try:
+                return self._augmented_forward_loss(images, input_ids, attention_mask, labels, keys)
+            finally:
+                self._mlm_call = None
+        return self._augmented_forward_loss(images, input_ids, attention_mask, labels, keys)
+
+    def _augmented_forward_loss(self, images, input_ids, attention_mask, labels, keys) -> torch.Tensor:
         if self._augment is None:
             return self.forward_loss(images, input_ids, attention_mask, labels, keys)
         seed, counter = self._augment
@@ -621,16 +772,28 @@ class JointContrastiveTrainer:
         """both encoders (`models`: another pair, the teacher's) on the same rows -> (image embeddings, text embeddings), the text
         encoder on the second stream"""
         im, tm = (self.image_model, self.text_model) if models is None else models
+        m = self._mlm_call
+
+        def text():
+            if m is None:
+                return tm.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
+            # a masked step: every text call reads the masked ids through the full-sequence path (a teacher then gives the student's
+            # bits at equal parameters); the student's last hidden state feeds the MLM head, on this stream
+            txt, last = tm.get_projected_text_embeddings_and_hidden(m.ids, attention_mask, want_hidden=models is None)
+            if models is None:
+                self._mlm_head(last, m)
+            return txt
+
         if not (self.two_streams and images.is_cuda):
             img = im(images)
-            txt = tm.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
+            txt = text()
             return img, txt
         if self._text_stream is None:
             self._text_stream = torch.cuda.Stream(device=images.device)
         cur = torch.cuda.current_stream(images.device)
         self._text_stream.wait_stream(cur)                     # inputs, weights and the zeroed gradients are ready
         with torch.cuda.stream(self._text_stream):
-            txt = tm.get_projected_text_embeddings(input_ids, attention_mask, normalize_embeddings=False)
+            txt = text()
         img = im(images)
         cur.wait_stream(self._text_stream)
         txt.record_stream(cur)
@@ -684,10 +847,11 @@ class JointContrastiveTrainer:
         """the step's one backward: the contrastive loss and, when a forward left one, beta * L_d, as two roots of one graph walk (each
         encoder's backward runs once, on the sum of both gradients of its embeddings)"""
         d, self._pending_distill = self._pending_distill, None
-        if d is None:
+        m, self._pending_mlm = self._pending_mlm, None
+        if d is None and m is None:
             loss.backward()
         else:
-            torch.autograd.backward([loss, d])
+            torch.autograd.backward([loss] + [r for r in (d, m) if r is not None])
 
     def _loss(self, img, txt, keys):
         if self.loss == "sigmoid":
@@ -701,11 +865,13 @@ class JointContrastiveTrainer:
         slices = ((0, int(images.shape[0])),) if self.micro_batch is None else micro_slices(int(images.shape[0]), self.micro_batch)
         chunked = len(slices) > 1
         self._pending_distill = None
+        self._pending_mlm = None
         if chunked:
             self._require_eval_batchnorm()
         self.optimizer.zero_grad()
         self.sync_dropout_state()
         self.sync_augment_state()
+        self.sync_mlm_state()
         works, fired = [], []      # without spans both stay empty: the final reduce then takes the whole buffer and waits for nothing
         on_ready = None
 
@@ -740,12 +906,12 @@ class JointContrastiveTrainer:
         """While it is open `_gradient` is that of the contrastive loss alone, on the images as they are: no augmentation (its counter
         does not move) and no teacher.  What `consolidate` estimates and what the A-GEM reference is taken from."""
         augment, self._augment = self._augment, None
-        self._distill_off = True
+        self._distill_off = self._mlm_off = True
         try:
             yield
         finally:
             self._augment = augment
-            self._distill_off = False
+            self._distill_off = self._mlm_off = False
 
     def _stored_gradient(self, batch) -> torch.Tensor:
         """`_gradient` of a stored batch `(images, input_ids, attention_mask[, labels | keys])`: a fourth tensor of more than one

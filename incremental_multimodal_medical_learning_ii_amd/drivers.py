@@ -140,8 +140,17 @@ def joint_encoders_from_args(args, image_model, kind=None, train_loader=None) ->
             "micro_batch": getattr(args, "micro_batch", None),
             **optimiser_from_args(args, kind, train_loader),
             **continual_from_args(args),
+            **mlm_from_args(args),
             "augment": augment_from_args(args),
             "retrieval": retrieval_from_args(args)}
+
+
+def mlm_from_args(args) -> dict:
+    """`--mlm-weight W [--mlm-probability P] [--mlm-seed S]` -> the `joint_encoders` keys of the masked-language-modelling loss
+    (DESIGN.md 5.13); without `--mlm-weight` an empty dict: the keys exist only when their flag is given"""
+    if getattr(args, "mlm_weight", None) is None:
+        return {}
+    return {k: getattr(args, k) for k in ("mlm_weight", "mlm_probability", "mlm_seed") if getattr(args, k, None) is not None}
 
 
 def retrieval_from_args(args):
@@ -384,6 +393,13 @@ def make_parser():
                          "all that are stored)")
     ap.add_argument("--agem-every", type=int, default=None, metavar="K",
                     help="--cl agem: recompute the reference gradient every K-th step and reuse it in between (default 1)")
+    ap.add_argument("--mlm-weight", type=float, default=None, metavar="W",
+                    help="--joint: add W times the masked-language-modelling loss of CXR-BERT's own head to the step's objective; the "
+                         "token ids are masked on the device every step and the head is trained (DESIGN.md 5.13)")
+    ap.add_argument("--mlm-probability", type=float, default=None, metavar="P",
+                    help="--mlm-weight: the fraction of the non-special tokens selected per step (default 0.15)")
+    ap.add_argument("--mlm-seed", type=int, default=None, metavar="S",
+                    help="--mlm-weight: seed of the masking draws (default: drawn from torch's CPU generator)")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
@@ -432,6 +448,21 @@ def parse_args(argv=None):
         for f in given:
             if getattr(args, f) < 1:
                 ap.error(f"--{f.replace('_', '-')} must be >= 1, got {getattr(args, f)}")
+    given = [f for f in ("mlm_probability", "mlm_seed") if getattr(args, f) is not None]
+    if given and args.mlm_weight is None:
+        ap.error("--" + given[0].replace("_", "-") + " configures the masked-language-modelling loss and needs --mlm-weight")
+    if args.mlm_weight is not None:
+        if not args.joint:
+            ap.error("--mlm-weight adds a loss to the north-star step and needs --joint (the adapter schedules use frozen "
+                     "pre-computed text embeddings)")
+        if not (args.mlm_weight >= 0 and args.mlm_weight != float("inf")):
+            ap.error(f"--mlm-weight must be finite and >= 0, got {args.mlm_weight}")
+        if args.mlm_probability is not None and not 0.0 <= args.mlm_probability <= 1.0:
+            ap.error(f"--mlm-probability must be in [0, 1], got {args.mlm_probability}")
+        if args.mlm_seed is not None and args.mlm_seed < 0:
+            ap.error(f"--mlm-seed must be >= 0, got {args.mlm_seed}")
+        if getattr(args, "micro_batch", None) is not None:
+            ap.error("--mlm-weight with --micro-batch is out of scope: the micro-batched step keeps no last hidden state")
     return args
 
 

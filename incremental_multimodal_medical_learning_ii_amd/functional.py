@@ -567,6 +567,154 @@ def distill_loss(img_emb: torch.Tensor, txt_emb: torch.Tensor, img_teacher: torc
     return _distill_pair(img_emb, txt_emb, img_teacher, txt_teacher, temperature, weight, group)[0]
 
 
+# --------------------------------------------------------------------------------------------------------------
+# The masked-language-modelling head: HF BertOnlyMLMHead + cross-entropy on the selected tokens, with the
+# vocabulary swept in chunks so that the [tokens, V] logits never exist.
+# --------------------------------------------------------------------------------------------------------------
+MLM_CHUNK_BYTES = 128 << 20
+
+
+def mlm_vocab_chunks(vocab_size: int, rows: int, chunk_bytes: int = MLM_CHUNK_BYTES, planes: bool = False):
+    """The (first column, columns, leading columns not counted) triples of one vocabulary sweep over `rows` logits rows with a
+    workspace of at most `chunk_bytes` (split-bf16 mode keeps the fp32 logits AND their gradient planes: half the columns).  Chunks
+    hold a multiple of 128 columns (at least 128, whatever the budget) and tile [0, V - V % 8); every GEMM of the sweep then has
+    sizes and offsets that are multiples of 8.  The V % 8 columns left are taken by one more chunk of 8 columns, [V - 8, V), whose
+    first 8 - V % 8 columns overlap the chunk before: they are not counted and get a zero gradient."""
+    V = int(vocab_size)
+    if V < 8:
+        raise ValueError(f"mlm_loss: the vocabulary must hold at least 8 ids, got {V}")
+    if int(chunk_bytes) < 1 or int(rows) < 1:
+        raise ValueError(f"mlm_loss: chunk_bytes and the number of rows must be positive, got {chunk_bytes!r} and {rows!r}")
+    vc = max(128, int(chunk_bytes) // (int(rows) * (8 if planes else 4)) // 128 * 128)
+    V8 = V // 8 * 8
+    chunks = [(v0, min(vc, V8 - v0), 0) for v0 in range(0, V8, vc)]
+    if V8 != V:
+        chunks.append((V - 8, 8, 8 - (V - V8)))
+    return chunks
+
+
+class _MLMLoss(torch.autograd.Function):
+    """(weight * L, L, correct) with L = scale * sum over the kept selected tokens of -log softmax(logits)[original id], logits those of
+    HF BertOnlyMLMHead (dense + erf-GELU + LayerNorm, decoder tied to the word embeddings + bias) on the selected rows of the last
+    hidden state.  Only the first output is differentiable: with respect to the last hidden state and the six head parameters.
+
+    Forward: gather -> transform -> for every vocabulary chunk (logits GEMM into the workspace, `mlm_xent_stats`) -> `mlm_xent_finish`.
+    Backward: for every chunk the same logits GEMM again (the same bits), `mlm_xent_grad`, then the data gradient accumulated into
+    d[cap, H], the chunk's rows of the decoder weight gradient and its slice of the decoder bias gradient; LayerNorm, GELU and dense
+    backward; scatter into a zeroed gradient of the last hidden state.  Parameter gradients go through `GradSink`: a parameter of the
+    flat optimiser gets them accumulated in place (the tied word embeddings receive the encoder's share later, in the same way)."""
+
+    @staticmethod
+    def forward(ctx, last, sel, tgt, stats, scale, weight, eps, chunk_bytes, wd, bd, gamma, beta, wdec, bdec):
+        from . import _lib
+        ctx.set_materialize_grads(False)
+        pl = _lib.get_precision() == "split_bf16"
+        H = last.shape[-1]
+        flat = last.detach().reshape(-1, H).contiguous()
+        cap = sel.shape[0]
+        V = wdec.shape[0]
+        if tuple(wd.shape) != (H, H) or wdec.shape[1] != H or bdec.numel() != V or tgt.shape[0] != cap:
+            raise ValueError(f"mlm_loss: hidden size {H}, transform {tuple(wd.shape)}, decoder {tuple(wdec.shape)}, bias {tuple(bdec.shape)}, "
+                             f"{cap} slots and {tgt.shape[0]} targets do not fit together")
+        p = [t.detach() for t in (wd, bd, gamma, beta, wdec, bdec)]
+        wd_w, wdec_w = (K.split_planes(p[0]), K.split_planes(p[4])) if pl else (p[0], p[4])
+        lin = K.linear_fwd_pl if pl else K.linear_fwd
+        x = K.mlm_gather_rows(flat, sel, stats, out_planes=pl)
+        h1_pre = torch.empty(cap, H, dtype=torch.float32, device=flat.device)
+        h1 = lin(x, wd_w, p[1], act=K.ACT_GELU, preact_out=h1_pre)
+        h2, xhat, rstd = K.residual_ln_fwd(h1, None, p[2], p[3], eps, out_planes=pl)
+        chunks = mlm_vocab_chunks(V, cap, chunk_bytes, pl)
+        ws = torch.empty(cap, max(c for _, c, _ in chunks), dtype=torch.float32, device=flat.device)
+        state, tl = K.mlm_xent_state(cap, flat.device)
+        for k, (v0, cols, skip) in enumerate(chunks):
+            S = lin(h2, _rows(wdec_w, v0, cols), None, out=ws[:, :cols])
+            K.mlm_xent_stats(S, v0, skip, p[5], tgt, stats, state, tl, first=k == 0)
+        lse, loss, correct = K.mlm_xent_finish(state, tl, tgt, stats, scale)
+        ctx.save_for_backward(sel, tgt, stats, scale, h1_pre, xhat, rstd, lse, *p)
+        ctx.ops = (x, h2, wd_w, wdec_w)            # GEMM operands in the storage format of the mode (Planes are no autograd tensors)
+        ctx.meta = (pl, float(weight), chunks, tuple(last.shape))
+        ctx.params = (wd, bd, gamma, beta, wdec, bdec)
+        weighted = K.scale_mask(loss.reshape(1), alpha=float(weight)).reshape(())
+        ctx.mark_non_differentiable(loss, correct)
+        return weighted, loss, correct
+
+    @staticmethod
+    def backward(ctx, gloss, _gl, _gc):
+        sel, tgt, stats, scale, h1_pre, xhat, rstd, lse, wd, bd, gamma, beta, wdec, bdec = ctx.saved_tensors
+        x, h2, wd_w, wdec_w = ctx.ops
+        pl, weight, chunks, shape = ctx.meta
+        ctx.ops = None
+        cap, H = h1_pre.shape
+        dev = h1_pre.device
+        lin, dgrad, wgrad = ((K.linear_fwd_pl, K.linear_bwd_data_pl, K.linear_bwd_weight_pl) if pl else
+                             (K.linear_fwd, K.linear_bwd_data, K.linear_bwd_weight))
+        sink = GradSink(ctx.params, ctx.needs_input_grad[8:])
+        up = gloss.reshape(()).contiguous()
+        width = max(c for _, c, _ in chunks)
+        ws = torch.empty(cap, width, dtype=torch.float32, device=dev)
+        gpl = K.Planes.empty(cap, width, device=dev) if pl else None
+        d = torch.empty(cap, H, dtype=torch.float32, device=dev)
+        dwdec, _ = sink.dst(4, zero=True)           # both accumulate: the chunks write row ranges, the last one overlapping
+        dbdec, _ = sink.dst(5, zero=True)
+        for k, (v0, cols, skip) in enumerate(chunks):
+            S = lin(h2, _rows(wdec_w, v0, cols), None, out=ws[:, :cols])                 # the forward's call: the same bits
+            G = K.mlm_xent_grad(S, v0, skip, bdec, tgt, stats, lse, up, scale, alpha=weight,
+                                out=K.Planes(gpl.t[:, :, :cols]) if pl else None)
+            dgrad(G, _rows(wdec_w, v0, cols), out=d, accumulate=k > 0)
+            wgrad(G, h2, dwdec[v0:v0 + cols], accumulate=True)
+            K.colsum(G, dbdec[v0:v0 + cols], accumulate=True)
+        (dg, db), acc = sink.dst_group(2, 3)
+        dh1 = K.residual_ln_bwd(d, xhat, rstd, gamma, dg, db, accumulate=acc)
+        dpre = K.gelu_bwd(dh1, h1_pre)
+        dpo = K.split_planes(dpre) if pl else dpre
+        g, acc = sink.dst(0)
+        wgrad(dpo, x, g, accumulate=acc)
+        g, acc = sink.dst(1)
+        K.colsum(dpre, g, accumulate=acc)
+        dlast = None
+        if ctx.needs_input_grad[0]:
+            T = 1
+            for s in shape[:-1]:
+                T *= s
+            dlast = K.mlm_scatter_rows(dgrad(dpo, wd_w), sel, stats, T).view(shape)
+        return (dlast, None, None, None, None, None, None, None) + sink.result()
+
+
+def _rows(w, v0: int, n: int):
+    """rows v0 .. v0 + n of a weight matrix in either storage format"""
+    return w.rows(slice(v0, v0 + n)) if isinstance(w, K.Planes) else w[v0:v0 + n]
+
+
+def _mlm_triple(last_hidden, sel, tgt, stats, model_params, scale, chunk_bytes=MLM_CHUNK_BYTES, weight=1.0, eps=1e-12):
+    """(weight * L, L, correct) of `mlm_loss`; the last two carry no graph (the joint trainer reports them)"""
+    weight = float(weight)
+    if not (math.isfinite(weight) and weight >= 0.0):
+        raise ValueError(f"mlm_loss: weight must be finite and >= 0, got {weight!r}")
+    params = tuple(model_params)
+    if len(params) != 6:
+        raise ValueError("mlm_loss: model_params are (transform.dense.weight, transform.dense.bias, transform.LayerNorm.weight, "
+                         f"transform.LayerNorm.bias, decoder.weight, decoder bias); got {len(params)} tensors")
+    if last_hidden.dim() not in (2, 3):
+        raise ValueError(f"mlm_loss: the last hidden state must be [T, H] or [N, L, H], got {tuple(last_hidden.shape)}")
+    scale = _device_scalar("mlm_loss", scale, "scale", last_hidden.device)
+    return _MLMLoss.apply(last_hidden, sel, tgt, stats, scale, weight, float(eps), int(chunk_bytes), *params)
+
+
+def mlm_loss(last_hidden: torch.Tensor, sel: torch.Tensor, tgt: torch.Tensor, stats: torch.Tensor, model_params, scale: torch.Tensor,
+             chunk_bytes: int = MLM_CHUNK_BYTES, weight: float = 1.0, eps: float = 1e-12) -> torch.Tensor:
+    """weight * scale * sum over the kept selected tokens of -log softmax(MLM logits)[original id] (see `_MLMLoss`) as
+    a device scalar: HF `BertForMaskedLM.forward(labels=)`'s loss when `scale` holds 1 / (number of selected tokens).
+
+    `last_hidden` [N, L, H] (or [T, H]) is the encoder's last hidden state ON THE MASKED IDS and receives a gradient; `sel` / `tgt` /
+    `stats` are the compact list of `kernels.mlm_mask_tokens` (int32 token indices and original ids in `cap` slots, stats[0] = the
+    slots that count, read on the device); `model_params` = the head's six parameters, `cls.predictions.transform.dense.weight /
+    .bias`, `.transform.LayerNorm.weight / .bias`, `.decoder.weight` (tied to the word embeddings) and the decoder bias; `scale` a
+    0-d or [1] fp32 device tensor (the data-parallel step puts 1 / max(selected tokens of the global batch, 1) there).  The
+    vocabulary runs in chunks whose logits workspace follows `chunk_bytes`, never the vocabulary size.  With no slot counting, the
+    loss and every gradient are exactly zero.  No atomics: two runs give the same bits."""
+    return _mlm_triple(last_hidden, sel, tgt, stats, model_params, scale, chunk_bytes, weight, eps)[0]
+
+
 @torch.no_grad()
 def similarity_logits(img_emb: torch.Tensor, txt_emb: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
     """normalize(img) @ normalize(txt).T / tau — the zero-shot score matrix (trash/lower_bound_mcs.py:79-117)."""

@@ -183,6 +183,23 @@ class CXRBertModel(BertForMaskedLM):
         bias = self.cls.predictions.bias if getattr(dec, "bias", None) is None else dec.bias
         return K.linear_fwd(h, dec.weight, bias).view(N, L, -1)
 
+    def mlm_head_params(self) -> Tuple[nn.Parameter, ...]:
+        """the six parameters of HF `BertOnlyMLMHead` in the order `functional.mlm_loss` takes them: transform dense weight / bias,
+        transform LayerNorm weight / bias, decoder weight (the word embeddings when tied) and the decoder bias"""
+        tr = self.cls.predictions.transform
+        dec = self.cls.predictions.decoder
+        bias = self.cls.predictions.bias if getattr(dec, "bias", None) is None else dec.bias
+        return (tr.dense.weight, tr.dense.bias, tr.LayerNorm.weight, tr.LayerNorm.bias, dec.weight, bias)
+
+    def get_projected_text_embeddings_and_hidden(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+                                                 want_hidden: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(unnormalised projected CLS embeddings [batch, projection_size], last hidden state [batch, L, hidden]) of ONE encoder pass
+        on the full-sequence path, both differentiable: what the joint step's masked-language-modelling loss reads
+        (`functional.mlm_loss`).  `want_hidden=False` runs the same path (the same bits of the embeddings) and returns None for the
+        hidden state."""
+        proj, last = self._encode(input_ids, attention_mask, cls_only=False, want_last=want_hidden)
+        return proj, (last if want_hidden else None)
+
     # ------------------------------------------------------------------ reference API
     def forward(
         self,

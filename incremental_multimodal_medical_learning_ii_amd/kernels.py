@@ -1353,6 +1353,158 @@ def distill_grad_inplace(S, St, lse_row, lse_col, lse_t_row, lse_t_col):
     return S
 
 
+# ---- masked-language-modelling head (include/cxrk.h, "mlm"; csrc/mlm.hip) ---------------------------------------------------------
+
+def mlm_capacity(T: int, p: float) -> int:
+    """slots of the compact list of selected tokens for T tokens masked with probability p:
+    min(T, roundup128(ceil(p T + 8 sqrt(p (1 - p) T)))), at least 1.  The selected count is at most Binomial(T, p) (pads and special
+    tokens are never drawn), so the list overflows only beyond eight standard deviations."""
+    import math
+    if isinstance(T, bool) or not isinstance(T, int) or T < 1:
+        raise ValueError(f"mlm_capacity: the number of tokens must be an integer >= 1, got {T!r}")
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"mlm_capacity: the masking probability must lie in [0, 1], got {p!r}")
+    need = math.ceil(p * T + 8.0 * math.sqrt(p * (1.0 - p) * T))
+    return max(1, min(T, (need + 127) // 128 * 128))
+
+
+class MlmMask(NamedTuple):
+    """what `mlm_mask_tokens` returns: the ids the encoder reads, the compact list of the selected tokens (`sel` int32 token indices in
+    ascending order, `tgt` int32 original ids; -1 behind the kept ones), `stats` = int32 {kept, selected} and `count` = fp32 [1] kept"""
+    ids: torch.Tensor
+    sel: torch.Tensor
+    tgt: torch.Tensor
+    stats: torch.Tensor
+    count: torch.Tensor
+
+
+def mlm_mask_tokens(ids, mask, seed: int, counter: int, p: float, vocab_size: int, mask_id: int, special_ids=(), row_offset: int = 0,
+                    cap: Optional[int] = None) -> MlmMask:
+    """HF DataCollatorForLanguageModeling's masking on the device (include/cxrk.h, "mask_tokens"): one Philox block per token, keyed by
+    (seed, counter, row_offset + sequence, token); the selected tokens compacted in token order into `cap` slots (default
+    `mlm_capacity`).  Nothing is read back: the counts stay in `stats` on the device."""
+    import ctypes
+    lib = _lib.load()
+    _chk(ids, "mlm_mask.ids", torch.int64)
+    if ids.dim() != 2:
+        raise ValueError(f"mlm_mask.ids: expected [N, L], got {tuple(ids.shape)}")
+    ids = ids.contiguous()
+    N, L = ids.shape
+    if mask is not None:
+        _chk(mask, "mlm_mask.mask", torch.int64)
+        if tuple(mask.shape) != (N, L):
+            raise ValueError(f"mlm_mask.mask: expected {(N, L)}, got {tuple(mask.shape)}")
+        mask = mask.contiguous()
+    special = tuple(int(s) for s in special_ids)
+    if len(special) > 8:
+        raise ValueError(f"mlm_mask: at most 8 special ids, got {len(special)}")
+    T = N * L
+    cap = mlm_capacity(T, p) if cap is None else int(cap)
+    dev = ids.device
+    out = MlmMask(torch.empty_like(ids), torch.empty(cap, dtype=torch.int32, device=dev), torch.empty(cap, dtype=torch.int32, device=dev),
+                  torch.empty(2, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.float32, device=dev))
+    counts = torch.empty((T + 255) // 256, dtype=torch.int32, device=dev)
+    sp = (ctypes.c_long * 8)(*(special + (-1,) * (8 - len(special))))
+    check(lib.cxrk_mlm_mask_tokens(_p(ids), _p(mask), N, L, int(row_offset), int(seed) & (2 ** 64 - 1), int(counter) & 0xFFFFFFFF, float(p),
+                                   int(vocab_size), int(mask_id), ctypes.cast(sp, ctypes.c_void_p), len(special), cap, _p(out.ids),
+                                   _p(out.sel), _p(out.tgt), _p(out.stats), _p(out.count), _p(counts), _stream()), "cxrk_mlm_mask_tokens")
+    return out
+
+
+def _mlm_list(sel, stats, what):
+    _chk(sel, f"{what}.sel", torch.int32)
+    _chk(stats, f"{what}.stats", torch.int32)
+    if sel.dim() != 1 or not sel.is_contiguous() or stats.numel() < 1 or not stats.is_contiguous():
+        raise ValueError(f"{what}: sel must be a contiguous int32 vector and stats hold the kept count")
+    return sel.shape[0]
+
+
+def mlm_gather_rows(last, sel, stats, out_planes: bool = False):
+    """[cap, H] rows last[sel[r]] for r < kept = stats[0], zero rows behind them; fp32 or Planes."""
+    lib = _lib.load()
+    cap = _mlm_list(sel, stats, "mlm_gather")
+    _chk(last, "mlm_gather.last")
+    if last.dim() != 2 or not last.is_contiguous():
+        raise ValueError(f"mlm_gather.last: expected a contiguous [T, H] tensor, got {tuple(last.shape)}")
+    T, H = last.shape
+    out, op, opl = _new_out(cap, H, last.device, out_planes)
+    check(lib.cxrk_mlm_gather_rows(_p(last), T, H, _p(sel), _p(stats), cap, op, opl, _stream()), "cxrk_mlm_gather_rows")
+    return out
+
+
+def mlm_scatter_rows(dx, sel, stats, T: int):
+    """zeroed [T, H] with row sel[r] = dx[r] for r < kept (plain stores: `sel` lists no token twice)"""
+    lib = _lib.load()
+    cap = _mlm_list(sel, stats, "mlm_scatter")
+    _chk(dx, "mlm_scatter.dx")
+    if dx.dim() != 2 or dx.shape[0] != cap or not dx.is_contiguous():
+        raise ValueError(f"mlm_scatter.dx: expected a contiguous [{cap}, H] tensor, got {tuple(dx.shape)}")
+    H = dx.shape[1]
+    dlast = torch.zeros(int(T), H, dtype=torch.float32, device=dx.device)
+    check(lib.cxrk_mlm_scatter_rows(_p(dx), _p(sel), _p(stats), cap, int(T), H, _p(dlast), _stream()), "cxrk_mlm_scatter_rows")
+    return dlast
+
+
+def mlm_xent_state(rows: int, device):
+    """(state [4, rows, 64], target_logit [rows]) of one vocabulary sweep of `mlm_xent_stats`"""
+    return (torch.empty(4, rows, 64, dtype=torch.float32, device=device), torch.zeros(rows, dtype=torch.float32, device=device))
+
+
+def _mlm_block(S, what):
+    _chk(S, f"{what}.S")
+    if S.dim() != 2 or (S.shape[1] > 1 and S.stride(1) != 1):
+        raise ValueError(f"{what}.S must be a 2-d block with contiguous columns, got shape {tuple(S.shape)} strides {S.stride()}")
+    rows, cols = S.shape
+    return rows, cols, (S.stride(0) if rows > 1 else max(cols, S.stride(0)))
+
+
+def mlm_xent_stats(S, v0: int, skip: int, bias, tgt, stats, state, target_logit, first: bool) -> None:
+    """fold the logits chunk S [rows, cols] (vocabulary columns v0 .. v0 + cols, the first `skip` not counted; the decoder `bias` [V]
+    is added here) into the running per-(row, lane) statistics (include/cxrk.h, "xent_stats")"""
+    lib = _lib.load()
+    rows, cols, ld = _mlm_block(S, "mlm_xent_stats")
+    _chk(bias, "mlm_xent_stats.bias")
+    _chk(tgt, "mlm_xent_stats.tgt", torch.int32)
+    if not bias.is_contiguous() or bias.numel() < v0 + cols or tgt.numel() != rows or tuple(state.shape) != (4, rows, 64):
+        raise ValueError(f"mlm_xent_stats: bias must cover columns {v0}..{v0 + cols}, tgt hold {rows} ids and state be [4, {rows}, 64]")
+    check(lib.cxrk_mlm_xent_stats(_p(S), ld, rows, cols, int(skip), int(v0), _p(bias), _p(tgt), _p(stats), _p(_chk(state, "mlm.state")),
+                                  _p(_rowvec(target_logit, rows, "mlm.target_logit")), int(bool(first)), _stream()), "cxrk_mlm_xent_stats")
+
+
+def mlm_xent_finish(state, target_logit, tgt, stats, scale):
+    """-> (lse [rows], loss = scale * sum_{r < kept} (lse - target logit) as a 0-d tensor, correct = int32 [1] rows whose argmax is the
+    target)"""
+    lib = _lib.load()
+    rows = state.shape[1]
+    dev = state.device
+    lse = torch.empty(rows, dtype=torch.float32, device=dev)
+    rowloss = torch.empty(rows, dtype=torch.float32, device=dev)
+    hit = torch.empty(rows, dtype=torch.int32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    correct = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.cxrk_mlm_xent_finish(_p(state), _p(target_logit), _p(tgt), _p(stats), rows, _p(_scalar(scale, "mlm_xent_finish.scale")),
+                                   _p(lse), _p(rowloss), _p(hit), _p(loss), _p(correct), _stream()), "cxrk_mlm_xent_finish")
+    return lse, loss, correct
+
+
+def mlm_xent_grad(S, v0: int, skip: int, bias, tgt, stats, lse, upstream, scale, alpha: float = 1.0, out: Optional[Planes] = None):
+    """the recomputed logits chunk S -> its gradient (include/cxrk.h, "xent_grad"), in place, or as Planes into `out` ([rows, cols]
+    view of a planes buffer); rows >= kept and the `skip` columns come out exactly zero"""
+    lib = _lib.load()
+    rows, cols, ld = _mlm_block(S, "mlm_xent_grad")
+    gp, ldg, gpl = (None, 0, 0)
+    if out is not None:
+        if tuple(out.shape) != (rows, cols):
+            raise ValueError(f"mlm_xent_grad.out: expected Planes {(rows, cols)}, got {tuple(out.shape)}")
+        gp, ldg, gpl = _pl2d(out, "mlm_xent_grad.out")
+    check(lib.cxrk_mlm_xent_grad(_p(S), ld, gp, ldg, gpl, rows, cols, int(skip), int(v0), _p(_chk(bias, "mlm_xent_grad.bias")),
+                                 _p(_chk(tgt, "mlm_xent_grad.tgt", torch.int32)), _p(stats), _p(_rowvec(lse, rows, "mlm_xent_grad.lse")),
+                                 _p(_scalar(upstream, "mlm_xent_grad.upstream")), _p(_scalar(scale, "mlm_xent_grad.scale")), float(alpha),
+                                 _stream()), "cxrk_mlm_xent_grad")
+    return S if out is None else out
+
+
 def clamp_inplace(x, lo: float, hi: float):
     """x <- min(max(x, lo), hi) in place on a dense tensor; a NaN stays a NaN."""
     lib = _lib.load()
