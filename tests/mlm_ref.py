@@ -56,11 +56,18 @@ def mask_tokens(ids, mask, seed, counter, p, vocab, mask_id, special=(), row_off
     return dict(ids_out=out, sel=sel, tgt=tgt, kept=kept, selected=len(where), kind=kind)
 
 
-def head_logits(x, wd, bd, gamma, beta, wdec, bdec, eps=1e-12):
+def linear_wide(x, w, b):
+    """F.linear whose three matrix products (forward, data and weight gradient) accumulate in float64 and round once to the operands'
+    dtype.  A float32 product of the CPU BLAS sums in an order that follows the processor model; this one gives every host the same
+    float32 figures (float64 operands: F.linear itself)."""
+    return F.linear(x.double(), w.double(), b.double()).to(x.dtype)
+
+
+def head_logits(x, wd, bd, gamma, beta, wdec, bdec, eps=1e-12, linear=F.linear):
     """HF BertOnlyMLMHead on rows x [R, H] (any float dtype)"""
-    h = F.gelu(F.linear(x, wd, bd))
+    h = F.gelu(linear(x, wd, bd))
     h = F.layer_norm(h, (h.shape[-1],), gamma, beta, eps)
-    return F.linear(h, wdec, bdec)
+    return linear(h, wdec, bdec)
 
 
 def correct_range(logits, targets, tol):
@@ -74,16 +81,18 @@ def correct_range(logits, targets, tol):
     return int((hit & sure).sum()), int((hit & sure).sum() + near.sum())
 
 
-def head_loss(last, sel, tgt, kept, params, scale, weight=1.0, eps=1e-12, tol=0.0):
+def head_loss(last, sel, tgt, kept, params, scale, weight=1.0, eps=1e-12, tol=0.0, dtype=torch.float64):
     """float64 autograd reference of `functional.mlm_loss`: last [T, H] and the six head parameters (cpu tensors) ->
-    dict(loss (unweighted), correct = `correct_range` at `tol`, dlast, dparams) of weight * scale * sum CE over the first `kept` slots"""
-    last = last.detach().double().clone().requires_grad_(True)
-    ps = [p.detach().double().clone().requires_grad_(True) for p in params]
+    dict(loss (unweighted), correct = `correct_range` at `tol`, dlast, dparams) of weight * scale * sum CE over the first `kept` slots.
+    `dtype`: the same formula in another precision (the differential sweep measures its float32 error, tests/sweep_cases.py), with
+    the matrix products of `linear_wide`: that figure must not depend on the host's BLAS"""
+    last = last.detach().to(dtype).clone().requires_grad_(True)
+    ps = [p.detach().to(dtype).clone().requires_grad_(True) for p in params]
     rows = torch.as_tensor(np.asarray(sel[:kept]), dtype=torch.int64)
     t = torch.as_tensor(np.asarray(tgt[:kept]), dtype=torch.int64)
     if kept == 0:
         return dict(loss=0.0, correct=(0, 0), dlast=torch.zeros_like(last), dparams=[torch.zeros_like(p) for p in ps])
-    logits = head_logits(last[rows], *ps, eps=eps)
+    logits = head_logits(last[rows], *ps, eps=eps, linear=F.linear if dtype == torch.float64 else linear_wide)
     loss = F.cross_entropy(logits, t, reduction="sum") * float(scale)
     (loss * weight).backward()
     return dict(loss=float(loss.detach()), correct=correct_range(logits, t, tol), dlast=last.grad,

@@ -1,14 +1,18 @@
 """Seeded differential sweep of the attention, GEMM, column-reduction and head kernels, the BERT row kernels (LayerNorm, embedding,
-gelu', planes_add_rows) and the image-side non-GEMM kernels (max-pool, layout transforms, spatial mean, BatchNorm folding and the
-train-mode BatchNorm chain) (cases, float64 references, comparators and bounds: tests/sweep_cases.py; what the sweep can see:
-tests/test_sweep_host.py).  Families A to D run in both contraction precisions; the kernels of E and F neither dispatch nor store
-by that mode (kernels.py: only the GEMM and convolution launches read it), so they run once.
+gelu', planes_add_rows), the image-side non-GEMM kernels (max-pool, layout transforms, spatial mean, BatchNorm folding and the
+train-mode BatchNorm chain) and the masked-language-modelling kernels (token masking, gather / scatter of the selected rows, the
+chunked vocabulary cross-entropy and its gradient, the whole head) (cases, float64 references, comparators and bounds:
+tests/sweep_cases.py; what the sweep can see: tests/test_sweep_host.py).  Families A to D run in both contraction precisions; the
+kernels of E, F and G neither dispatch nor store by that mode (kernels.py: only the GEMM and convolution launches read it; the
+masked-LM kernels take their storage form from their arguments), so they run once -- but for G's head cases, whose GEMMs do.
 
 Every input sits in a `memguard.Guarded` allocation and every output goes through `memguard.run_contract` (guards and pitch padding
 intact, every element written, bit-identical over an ordinary and a NaN-poisoned exact-size workspace, and a +-1e30 one where the
 call takes a workspace), so a stray access lands in memory the test owns.  Every generated case is legal under include/cxrk.h:
 nothing is skipped, and a refusal by a wrapper fails the test.  Each test id is a chunk of at most 16 cases and prints its worst
 error / bound per output before it asserts."""
+import ctypes
+
 import pytest
 import torch
 
@@ -19,6 +23,7 @@ pytestmark = [pytest.mark.gpu]
 both_precisions = pytest.mark.usefixtures("precision")
 
 from incremental_multimodal_medical_learning_ii_amd import _lib as _cxr_lib  # noqa: E402
+from incremental_multimodal_medical_learning_ii_amd import functional as Fh  # noqa: E402
 from incremental_multimodal_medical_learning_ii_amd import kernels as K  # noqa: E402
 
 DEV = "cuda"
@@ -486,6 +491,145 @@ def test_image_side(chunk):
     rep = Report("image side " + chunk, mode=False)
     for c in chunk_cases("F", chunk):
         _image_side(c, rep)
+    rep.finish()
+
+
+# ================================================================================================================ G: masked-LM kernels
+def _mlm_mask(c, inp, ref, G, rep):
+    N, L, cap = c.N, c.L, int(inp["cap"])
+    ids, mask = G.put(inp["ids"], "ids"), (G.put(inp["mask"], "mask") if c.given_mask else None)
+    special = S.mask_special(c)
+    sp = (ctypes.c_long * 8)(*(special + (-1,) * (8 - len(special))))
+    outs = {"ids": Out((N, L), I64), "sel": Out((cap,), I32), "tgt": Out((cap,), I32), "stats": Out((2,), I32), "count": Out((1,)),
+            "blocks": Out(((N * L + 255) // 256,), I32)}
+    o = run(lambda o: cabi("cxrk_mlm_mask_tokens", P(ids), P(mask), N, L, c.row_offset, int(inp["seed"]), int(inp["counter"]) & 0xFFFFFFFF, c.p,
+                           S.MLM_VOCAB, S.MLM_MASK_ID, ctypes.cast(sp, ctypes.c_void_p), len(special), cap,
+                           *(P(o[k]) for k in ("ids", "sel", "tgt", "stats", "count", "blocks"))), outs, False)
+    rep.add(c, S.check(c, ref, {k: g.t.cpu() for k, g in o.items()}))
+
+
+def _mlm_rows(c, inp, ref, G, rep):
+    cap, H = c.cap, c.H
+    sel, stats = G.put(inp["sel"], "sel"), G.put(inp["stats"], "stats")
+    if c.op == "gather":
+        last = G.put(inp["last"], "last")
+        T = last.shape[0]
+        spec = {"out": Out((2, cap, H), BF, gap=c.gap) if c.planes else Out((cap, H))}
+        o = run(lambda o: cabi("cxrk_mlm_gather_rows", P(last), T, H, P(sel), P(stats), cap, P(o["out"]), o["out"].stride(0) if c.planes else 0), spec, False)
+        rep.add(c, S.check(c, ref, {"out": o["out"].t.cpu()}), "->planes" if c.planes else "")      # the planes: bit for bit the canonical split
+    else:
+        dx, T = G.put(inp["dx"], "dx"), int(inp["T"])
+        o = run(lambda o: cabi("cxrk_mlm_scatter_rows", P(dx), P(sel), P(stats), cap, T, H, P(o["dlast"])), {"dlast": Out((T, H), init=torch.zeros(T, H))}, False)
+        rep.add(c, S.check(c, ref, {"dlast": o["dlast"].t.cpu()}))
+
+
+def _mlm_xent(c, inp, ref, G, rep):
+    """one vocabulary sweep at kernel level: stats chunk by chunk through one shared workspace, finish, then the gradient of every chunk
+    from the float32 rounding of the reference's log-sum-exp, in place and as planes"""
+    rows, V = c.cap, c.V
+    chunks = S.xent_chunks(V, c.width)
+    width = max(n for _, n, _ in chunks)
+    ld = width + c.pad
+    bias, tgt, stats, scale, up, lse_in = (G.put(inp[k], k) for k in ("bias", "tgt", "stats", "scale", "upstream", "lse_in"))
+    logits = inp["S"].to(DEV)
+    spec = {"state": Out((4, rows, 64), written=False), "tl": Out((rows,), written=False), "lse": Out((rows,)), "rowloss": Out((rows,)),
+            "hit": Out((rows,), I32), "loss": Out(()), "correct": Out((1,), I32)}
+    # the workspace of _MLMLoss (ws[:, :cols] of one block for every chunk); then with ld % 4 != 0 and from a base 4 bytes off a
+    # 16-byte boundary: the column-by-column kernel takes every chunk, not only the tail
+    for form, ldw, off in (("", ld, 0), ("[ld % 4]", ld + 1, 0), ("[base + 4]", ld, 1)):
+        if off:
+            ws = MG.Guarded(((rows - 1) * ldw + width + off,), device=DEV, name="logits workspace " + form)
+            block = ws.t[off:].as_strided((rows, width), (ldw, 1))
+        else:
+            ws = MG.Guarded((rows, width), ld=ldw, device=DEV, name="logits workspace " + form)
+            block = ws.t
+        ws.must_write = False
+
+        def sweep(o):
+            for k, (v0, n, skip) in enumerate(chunks):
+                block[:, :n].copy_(logits[:, v0:v0 + n])
+                cabi("cxrk_mlm_xent_stats", P(block), ldw, rows, n, skip, v0, P(bias), P(tgt), P(stats), P(o["state"]), P(o["tl"]), int(k == 0))
+            cabi("cxrk_mlm_xent_finish", P(o["state"]), P(o["tl"]), P(tgt), P(stats), rows, P(scale), P(o["lse"]), P(o["rowloss"]), P(o["hit"]),
+                 P(o["loss"]), P(o["correct"]))
+
+        o = run(sweep, spec, False)
+        ws.check()
+        got = {k: o[k].value() for k in ("lse", "rowloss", "loss")}
+        got.update(hit=o["hit"].t.cpu(), correct=o["correct"].t.cpu())
+        rep.add(c, S.check(c, ref, got), form)
+    alpha = float(torch.tensor(c.alpha, dtype=torch.float32))
+    ldg = (ld + 7) // 8 * 8 + 8
+    for form in ("", "->planes"):
+        grad, skipped = torch.zeros(rows, V, dtype=torch.float64), []
+        for v0, n, skip in chunks:
+            if form:
+                src = G.put(inp["S"][:, v0:v0 + n], "logits", ld)
+                o = run(lambda o: cabi("cxrk_mlm_xent_grad", P(src), ld, P(o["g"]), ldg, o["g"].stride(0), rows, n, skip, v0, P(bias), P(tgt), P(stats),
+                                       P(lse_in), P(up), P(scale), alpha), {"g": Out((2, rows, n), BF, ld=ldg, gap=8)}, False)
+            else:
+                o = run(lambda o: cabi("cxrk_mlm_xent_grad", P(o["g"]), ld, None, 0, 0, rows, n, skip, v0, P(bias), P(tgt), P(stats), P(lse_in), P(up),
+                                       P(scale), alpha), {"g": Out((rows, n), ld=ld, init=inp["S"][:, v0:v0 + n])}, False)
+            g = o["g"].value()
+            grad[:, v0 + skip:v0 + n] = g[:, skip:]
+            skipped.append(g[:, :skip])
+        rep.add(c, S.check(c, ref, {"grad": grad, "grad_skip": skipped[-1]}, planes_out=("grad",) if form else ()), form)
+
+
+def _mlm_head(c, rep):
+    inp = S.build(c)
+    ref = S.reference(c, inp)
+    G = Inputs()
+    names = ("wd", "bd", "gamma", "beta", "wdec", "bdec")
+    last, params = G.put(inp["last"], "last"), [G.put(inp[k], k) for k in names]
+    sel, tgt, stats, scale, up = (G.put(inp[k], k) for k in ("sel", "tgt", "stats", "scale", "upstream"))
+    T, H, V = last.shape[0], c.H, c.V
+    assert Fh.mlm_vocab_chunks(V, c.cap, S.head_chunk_bytes(c, _split()), _split()) == S.xent_chunks(V, c.width)
+    spec = {"loss": Out(()), "correct": Out((1,), I32), "dlast": Out((T, H)), "dwd": Out((H, H)), "dbd": Out((H,)), "dgamma": Out((H,)),
+            "dbeta": Out((H,)), "dwdec": Out((V, H)), "dbdec": Out((V,))}
+
+    def call(o):      # autograd allocates its results: copied into the guarded outputs, whose three runs must agree bit for bit
+        x = last.detach().requires_grad_(True)
+        leaves = [p.detach().requires_grad_(True) for p in params]
+        weighted, loss, correct = Fh._mlm_triple(x, sel, tgt, stats, leaves, scale, S.head_chunk_bytes(c, _split()), c.alpha)
+        (weighted * up[0]).backward()
+        o["loss"].copy_(loss)
+        o["correct"].copy_(correct)
+        o["dlast"].copy_(x.grad)
+        for k, p in zip(names, leaves):
+            o["d" + k].copy_(p.grad)
+
+    o = run(call, spec, True)
+    got = {k: g.value() for k, g in o.items() if k != "correct"}
+    got["correct"] = o["correct"].t.cpu()
+    rep.add(c, S.check(c, ref, got, _split()))
+    G.check()
+
+
+def _mlm(c, rep):
+    inp = S.build(c)
+    ref = S.reference(c, inp)
+    G = Inputs()
+    {"mask_tokens": _mlm_mask, "gather": _mlm_rows, "scatter": _mlm_rows, "xent": _mlm_xent}[c.op](c, inp, ref, G, rep)
+    G.check()
+
+
+@pytest.mark.parametrize("chunk", chunk_ids("G"))
+def test_mlm(chunk):
+    """mask, gather, scatter and the cross-entropy kernels take their storage form from their arguments: once (the head cases that fall
+    into the chunk run in test_mlm_head)"""
+    rep = Report("mlm " + chunk, mode=False)
+    for c in chunk_cases("G", chunk):
+        if c.op != "head":
+            _mlm(c, rep)
+    rep.finish()
+
+
+@both_precisions
+def test_mlm_head():
+    rep = Report("mlm head")
+    for c in [c for f, c in REGRESSIONS if f == "G"] + S.cases("G"):
+        if c.op == "head":
+            _mlm_head(c, rep)
     rep.finish()
 
 

@@ -1,8 +1,8 @@
 """The differential sweep without a GPU: the generators of tests/sweep_cases.py are deterministic, legal and cover their strata and the
 kernels' dispatch thresholds; the float64 references agree with independent formulations; the table E32 is what this machine
 measures; and -- as tests/test_memguard_host.py does for the memory contract -- deliberately wrong CPU "kernels" run through the
-same comparators and bounds as the GPU tests: each is caught on at least one generated case, the correct float32 evaluation passes
-on every case."""
+same comparators and bounds as the GPU tests: each is caught on at least one generated case (family G's: on exactly the cases that
+reach the path it breaks), the correct float32 evaluation passes on every case."""
 import math
 import os
 import sys
@@ -19,7 +19,8 @@ FAMILIES = tuple(S.NCASES)
 
 
 def _same(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a, b)
+    # bit for bit: the NaN poison of family G's inputs is the same poison
+    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))
 
 
 # ---------------------------------------------------------------------------------------------------------------- generators
@@ -553,16 +554,16 @@ def test_e32_table():
     the float32 matrix products of two hosts differ (E32_HOST_RATIO) the entry is the larger host's figure and the upper limit is wider
     by exactly the measured ratio between them."""
     measured = {}
-    for family in ("A", "C", "D", "E", "F"):
+    for family in ("A", "C", "D", "E", "F", "G"):
         measured.update(S.measure_e32(family))
     print("\n".join(f"{k}: measured {v:.3g}, table {S.E32.get(k)}" for k, v in sorted(measured.items())))
     assert set(measured) == set(S.E32), set(measured) ^ set(S.E32)
     assert set(S.E32_HOST_RATIO) <= set(S.E32) and all(1.0 < r < 5.0 for r in S.E32_HOST_RATIO.values())
-    # E and F: a figure below one float32 ulp (2^-23) is a count of ulps over a few values -- 0 on one host, 1 on the next -- and cannot
-    # move a bound (8 x 2^-22 is far below every floor): the table holds no E or F entry below 1.2e-7, and such an entry is held under
-    # 2^-22 instead of under twice the measurement
-    limit = lambda k, v: max(2 * S.E32_HOST_RATIO.get(k, 1.0) * v, 2.0 ** -22 if k[0][0] in "EF" else 0.0)      # noqa: E731
-    assert all(v >= 1.2e-7 for k, v in S.E32.items() if k[0][0] in "EF")
+    # E, F and G: a figure below one float32 ulp (2^-23) is a count of ulps over a few values -- 0 on one host, 1 on the next -- and
+    # cannot move a bound (8 x 2^-22 is far below every floor): the table holds no E, F or G entry below 1.2e-7, and such an entry is
+    # held under 2^-22 instead of under twice the measurement
+    limit = lambda k, v: max(2 * S.E32_HOST_RATIO.get(k, 1.0) * v, 2.0 ** -22 if k[0][0] in "EFG" else 0.0)      # noqa: E731
+    assert all(v >= 1.2e-7 for k, v in S.E32.items() if k[0][0] in "EFG")
     bad = [f"E32[{k}] = {S.E32[k]:.3g}, measured {v:.3g}" for k, v in measured.items() if not v <= S.E32[k] <= limit(k, v)]
     assert not bad, "\n".join(bad)
 
@@ -852,3 +853,307 @@ def test_fake_batchnorm_and_layout_kernels_are_caught():
         return dict(out, nhwc=y)
     caught = {c.index for c, _ in _sweep("F", padding_unwritten, _only("layout"))}
     assert caught and caught == {c.index for c in S.cases("F") if c.op == "layout" and c.Cpad > c.C}
+
+
+# ---------------------------------------------------------------------------------------------------------------- family G
+def test_mlm_strata_are_hit():
+    by = _by_op("G")
+    assert {op: len(v) for op, v in by.items()} == dict(S.G_COUNTS)
+    mk = by["mask_tokens"]
+    _covered(mk, {"NL": (S.G_MASK_NL, lambda c: (c.N, c.L)), "mask": ((True, False), lambda c: c.given_mask),
+                  "nspecial": (S.G_MASK_NSPECIAL, lambda c: c.nspecial), "row_offset": (S.G_MASK_OFFSET, lambda c: c.row_offset)})
+    big = lambda c: c.N * c.L > 65536      # noqa: E731
+    _covered_among(mk, lambda c: not big(c), "p", S.G_MASK_P, lambda c: c.p)
+    _covered_among(mk, big, "p", S.G_MASK_P[1:], lambda c: c.p)
+    narrow = lambda c: big(c) or c.p == 0.0 or c.N * c.L == 1      # noqa: E731
+    _covered_among(mk, lambda c: not narrow(c), "cap", S.G_MASK_CAP, lambda c: c.cap_mode)
+    _covered_among(mk, narrow, "cap", ("default", "T"), lambda c: c.cap_mode)
+    assert {c.N * c.L for c in mk} == {1, 255, 256, 257, 513, 8192, 66048}
+    for c in mk:      # a forced capacity overflows, the default one does not; special ids and pads exist where the case has them
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        kept, selected = ref["stats"].tolist()
+        assert (selected > kept) == (c.cap_mode == "below") and 1 <= int(inp["cap"]) <= c.N * c.L, S.describe(c)
+        assert int(ref["blocks"].sum()) == selected
+        if c.p == 1.0 and c.N * c.L >= 255:
+            assert (selected < c.N * c.L) == (c.given_mask or c.nspecial > 0), S.describe(c)
+    for op in ("gather", "scatter"):
+        _covered(by[op], {"cap": (S.G_CAP, lambda c: c.cap), "kept": (S.G_KEPT, lambda c: c.kept)})
+    ga = by["gather"]
+    _covered(ga, {"planes": ((True, False), lambda c: c.planes)})
+    _covered_among(ga, lambda c: c.planes, "H", [h for h in S.G_ROWS_H if h % 8 == 0], lambda c: c.H)
+    _covered_among(ga, lambda c: not c.planes, "H", S.G_ROWS_H, lambda c: c.H)
+    _covered_among(ga, lambda c: c.planes, "gap", S.G_GAP, lambda c: c.gap)
+    _covered(by["scatter"], {"H": (S.G_ROWS_H, lambda c: c.H)})
+    for c in ga + by["scatter"]:      # one -1 and one T among the kept slots (from two / three kept slots on); poison behind them
+        inp = S.build(c)
+        live, sel = S.mlm_live(c), inp["sel"].tolist()
+        T = inp["last"].shape[0] if c.op == "gather" else int(inp["T"])
+        assert sel[:live].count(-1) == (live >= 2) and sel[:live].count(T) == (live >= 3) and all(0 <= t < T for t in sel[live:])
+        assert len(set(sel)) == len(sel) and inp["stats"].tolist()[0] == S.mlm_kept(c)
+        poisoned = inp["last"][inp["sel"][live:].long()] if c.op == "gather" else inp["dx"][live:]
+        assert bool(torch.isnan(poisoned).all()) and int(torch.isnan(inp["last" if c.op == "gather" else "dx"]).any(1).sum()) == c.cap - live
+    xs = by["xent"]
+    _covered(xs, {"V": (S.G_V, lambda c: c.V), "rows": (S.G_CAP, lambda c: c.cap), "pad": (S.G_PAD, lambda c: c.pad),
+                  "alpha": ((1.0, 0.5), lambda c: c.alpha), "profile": (S.G_PROFILES, lambda c: c.profile)})
+    for widths in {S.xent_widths(v) for v in S.G_V}:      # vocabularies that allow the same widths share one covering sequence (Schedule)
+        _covered_among(xs, lambda c: S.xent_widths(c.V) == widths, "width", widths, lambda c: c.width)
+    needs = lambda c: S.xent_needs_rows(c.V, c.width, c.profile)      # noqa: E731
+    kept_of = lambda c: S.xent_kept(c.V, c.width, c.profile, c.cap)      # noqa: E731
+    assert {kept_of(c) for c in xs} == {S.G_KEPT, S.G_KEPT[2:], ("1", "cap", "cap+5")}
+    for strata in {kept_of(c) for c in xs}:
+        _covered_among(xs, lambda c: kept_of(c) == strata, "kept", strata, lambda c: c.kept)
+    assert all(S.mlm_live(c) > 0 for c in xs if needs(c)) and 4 <= sum(S.mlm_live(c) == 0 for c in xs) <= 8
+    tie_targets = set()
+    assert {w for v in S.G_V for w in S.xent_widths(v)} == set(S.G_WIDTH) | {0}
+    placed = set()
+    for c in xs:
+        inp = S.build(c)
+        live, chunks = S.mlm_live(c), S.xent_chunks(c.V, c.width)
+        tgt = inp["tgt"][:live].tolist()
+        assert all(0 <= t < c.V for t in tgt) and bool((inp["tgt"][live:] == -1).all()) and bool(torch.isnan(inp["S"][live:]).all())
+        x = (inp["S"].double() + inp["bias"].double())[:live]
+        p = torch.softmax(x, 1)[torch.arange(live), inp["tgt"][:live].long()]
+        if c.profile == "dominant":
+            assert bool((1 - p < 1e-6).all()) and bool((1 - p > 0.9e-6).all()), S.describe(c)
+        if c.profile == "pm80" and live:
+            assert float(x.max()) > 70 and float(x.min()) < -70
+        if c.profile == "ties":
+            ties = S.tie_columns(c)
+            assert len(ties) == (3 if c.V % 8 else 2) and len({(t // 4) % 64 for t in ties}) == len(ties) == len({t % 64 for t in ties})
+            owner = lambda col: max(k for k, (v0, n, skip) in enumerate(chunks) if v0 + skip <= col < v0 + n)      # noqa: E731
+            assert len({owner(t) for t in ties}) == min(len(ties), len(chunks)), S.describe(c)
+            assert bool((x[:, ties] == S.TIE_VALUE).all()) and all(float(x[i].max()) == S.TIE_VALUE for i in range(live))
+            assert bool((x.argmax(1) == ties[0]).all())
+            tie_targets |= {("tail" if t >= c.V // 8 * 8 else "later" if t != ties[0] else "first") for t in tgt if t in ties}
+        for v0, n, skip in chunks:
+            for t in tgt:
+                for tag, col in (("first", v0 + skip), ("last", v0 + n - 1), ("4095", v0 + 4095), ("4096", v0 + 4096), ("2047", v0 + 2047), ("2048", v0 + 2048)):
+                    if t == col and col < v0 + n:
+                        placed.add(tag)
+                if skip and v0 <= t < v0 + skip:
+                    placed.add("overlap")
+                if skip and t == v0 + skip:
+                    placed.add("tail first")
+    assert placed == {"first", "last", "4095", "4096", "2047", "2048", "overlap", "tail first"}, placed
+    # a target on the winning tie, on a later one in a whole chunk and on the one in the tail chunk's counted columns (hit = 0 there)
+    assert tie_targets == {"first", "later", "tail"}, tie_targets
+    hd = by["head"]
+    _covered(hd, {"cap": (S.G_HEAD_CAP, lambda c: c.cap), "width": (S.G_HEAD_WIDTH, lambda c: c.width), "kept": (S.G_HEAD_KEPT, lambda c: c.kept)})
+    assert all(c.H == 768 and c.V == 4366 for c in hd)
+    assert S.xent_chunks(4366, 0) == [(0, 4360, 0), (4358, 8, 2)] and S.xent_chunks(4366, 2176) == [(0, 2176, 0), (2176, 2176, 0), (4352, 8, 0), (4358, 8, 2)]
+
+
+def test_mlm_chunk_lists_are_the_library_s():
+    """the chunk list a case states from (V, columns per chunk) is what functional.mlm_vocab_chunks cuts, in both storage modes"""
+    from incremental_multimodal_medical_learning_ii_amd import functional as Fh
+    for c in S.cases("G"):
+        if c.op in ("xent", "head"):
+            for split in (False, True):
+                assert Fh.mlm_vocab_chunks(c.V, c.cap, S.head_chunk_bytes(c, split), split) == S.xent_chunks(c.V, c.width), S.describe(c)
+
+
+def _stats_vec(c, v0, cols, skip, ld, aligned=True):
+    return skip == 0 and ld % 4 == 0 and cols % 4 == 0 and v0 % 4 == 0 and aligned      # csrc/mlm.hip cxrk_mlm_xent_stats
+
+
+def test_mlm_dispatch_coverage():
+    """the host logic of csrc/mlm.hip restated: the trips, blocks and clamps no other test reaches are reached by a generated case"""
+    by = _by_op("G")
+    xs = [c for c in by["xent"] if S.mlm_live(c) > 0]
+    seen = set()
+    for c in xs:
+        chunks = S.xent_chunks(c.V, c.width)
+        ld = max(n for _, n, _ in chunks) + c.pad
+        for k, (v0, n, skip) in enumerate(chunks):
+            grid_y = -(-n // S.GRAD_TILE)
+            if grid_y >= 2:
+                seen.add("grid.y >= 2")
+                if min(n, grid_y * S.GRAD_TILE) % S.GRAD_STEP:
+                    seen.add("hi clipped off a multiple of 2048")
+            if min(n, S.GRAD_TILE) > S.GRAD_STEP:
+                seen.add("second trip of the gradient loop")
+            vec = _stats_vec(c, v0, n, skip, ld)
+            if vec and -(-n // S.STATS_STEP) >= 3:
+                seen.add("three trips of the vector stats loop")
+            if k > 0:
+                seen.add("first = 0, vector" if vec else "first = 0, scalar")
+            if k > 0 and not vec and any(_stats_vec(c, *ch, ld) for ch in chunks[:k]):
+                seen.add("a state from the vector path into the scalar tail")
+            assert not _stats_vec(c, v0, n, skip, ld + 1) and not _stats_vec(c, v0, n, skip, ld, aligned=False)      # the two all-scalar sweeps
+    assert seen == {"grid.y >= 2", "hi clipped off a multiple of 2048", "second trip of the gradient loop", "three trips of the vector stats loop",
+                    "first = 0, vector", "first = 0, scalar", "a state from the vector path into the scalar tail"}, seen
+    assert any(len(S.xent_chunks(c.V, c.width)) > 2 and c.V % 8 for c in xs)
+    live = lambda op, pred: any(pred(c) and S.mlm_live(c) > 0 for c in by[op])      # noqa: E731
+    assert live("gather", lambda c: not c.planes and c.H > 256) and live("gather", lambda c: not c.planes and c.H > 512)      # j += 256: 2, 3 trips
+    assert live("gather", lambda c: c.planes and 512 < c.H < 1024)      # j += 512: the second trip, by lanes below 32 only (H = 768) ...
+    assert live("gather", lambda c: c.planes and c.H == 1024)            # ... and by every lane
+    assert live("scatter", lambda c: c.H > 256) and live("scatter", lambda c: c.H > 512)
+    assert any(-(-c.N * c.L // 256) > 256 for c in by["mask_tokens"]) and any(2 < -(-c.N * c.L // 256) <= 256 for c in by["mask_tokens"])
+    for op in ("gather", "scatter", "xent"):
+        assert any(S.mlm_kept(c) < 0 for c in by[op]) and any(S.mlm_kept(c) > c.cap for c in by[op]), op
+        assert {(4 - c.cap % 4) % 4 for c in by[op]} >= {0, 1, 3}      # one wave per row, four rows per block: idle waves
+    hd = by["head"]
+    wide = [c for c in hd if c.width == 0]
+    assert wide and all(S.xent_chunks(c.V, c.width)[0][1] == 4360 for c in wide) and {c.width for c in hd} == {0, 2176}
+
+
+def test_mlm_references_against_independent_forms():
+    import numpy as np
+    for c in _by_op("G")["mask_tokens"]:      # the block-wise placement of the kernels is the token order of the reference
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        flags = (ref["ids"] != inp["ids"]).reshape(-1).numpy()
+        sel, tgt, counts = S.mask_place(np.isin(np.arange(c.N * c.L), _selected_tokens(c, inp)), inp["ids"].numpy(), int(inp["cap"]))
+        assert np.array_equal(sel, ref["sel"].numpy()) and np.array_equal(tgt, ref["tgt"].numpy()) and int(counts.sum()) == int(ref["stats"][1])
+        assert not flags[~np.isin(np.arange(c.N * c.L), _selected_tokens(c, inp))].any()
+        k = int(ref["stats"][0])
+        assert bool((ref["sel"][:k].diff() > 0).all()) and bool((ref["sel"][k:] == -1).all()) and float(ref["count"]) == k
+    for c in _pick("G", lambda c: c.op == "xent" and S.mlm_live(c) > 1 and c.V <= 4366, 8):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        live = S.mlm_live(c)
+        x = (inp["S"].double() + inp["bias"].double())[:live].requires_grad_(True)
+        ce = F.cross_entropy(x, inp["tgt"][:live].long(), reduction="sum") * inp["scale"].double()[0]
+        assert abs(float(ce) - float(ref["loss"])) <= 1e-12 * max(abs(float(ce)), float(ref["lse"].abs().max()))      # lse - target logit cancels
+        (ce * float(inp["upstream"][0]) * c.alpha).backward()
+        # the reference gradient is taken at the float32 rounding of the log-sum-exp the kernel is handed: equal to autograd up to that
+        assert float(((ref["grad"][:live] - x.grad).abs() / ref["mag:grad"][:live].clamp_min(1e-300)).max()) <= S.U24, S.describe(c)
+        assert int(ref["correct"]) == int((x.detach().argmax(1) == inp["tgt"][:live]).sum())
+        lo, hi = ref["aux:correct"][0].tolist()
+        assert lo <= int(ref["correct"]) <= hi and (lo == hi or c.profile != "ties")
+
+
+def _selected_tokens(c, inp):
+    import numpy as np
+    import mlm_ref
+    out = mlm_ref.mask_tokens(inp["ids"].numpy(), inp["mask"].numpy() if c.given_mask else None, int(inp["seed"]), int(inp["counter"]), c.p,
+                              S.MLM_VOCAB, S.MLM_MASK_ID, S.mask_special(c), c.row_offset, cap=c.N * c.L)
+    return np.asarray(out["sel"][:out["kept"]])
+
+
+def test_mlm_gradient_bound_leaves_no_element_out():
+    """on the float64 reference alone: the bound of every gradient element of a row that counts is positive, and its relative part is
+    below 1e-3 of the element's own scale |f| (p + [column == target]) -- a column of probability 1e-4 that is wrong by a thousandth
+    of itself fails, whatever the target's p - 1 is; only |f| 2^-126 is absolute (products that underflow in float32)"""
+    worst = 0.0
+    for c in _by_op("G")["xent"]:
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        live = S.mlm_live(c)
+        f = float(S.xent_factor(c, inp, F64).abs())
+        hot = torch.zeros(live, c.V, dtype=torch.bool)
+        hot[torch.arange(live), inp["tgt"][:live].long()] = True
+        own = f * (torch.softmax((inp["S"].double() + inp["bias"].double())[:live], 1) + hot.double())
+        bound = S.grad_c(c) * S.U24 * ref["mag:grad"] + S.grad_extra(ref, False)
+        assert bool((bound[:live] > 0).all()) and not bool(bound[live:].any()), S.describe(c)
+        if live:
+            rel = float(((bound[:live] - f * S.F32_TINY) / own).max())
+            worst = max(worst, rel)
+            assert rel < 1e-3, f"{S.describe(c)}: {rel:.3g}"
+    print(f"largest relative part of a gradient bound: {worst:.3g}")
+
+
+def _mlm32(c, inp, wrapped_bias=False, restart=False, last_tie=False, gather_cols=None, blocks_summed=None, dead=None):
+    """the correct float32 evaluation with one deliberate mistake of a kernel"""
+    out = _correct32(c, inp)
+    live = S.mlm_live(c)
+    if c.op == "mask_tokens" and blocks_summed is not None:
+        return {k: v for k, v in S._eval_g(c, inp, F32, blocks_summed=blocks_summed).items()}
+    if c.op == "gather" and gather_cols is not None:
+        out["out"] = out["out"].clone()
+        out["out"][..., gather_cols:] = 0
+    if c.op == "xent" and dead is not None:      # a row output that is not zeroed behind the kept rows
+        out[dead] = out[dead].clone()
+        out[dead][live:] = 7
+    if c.op != "xent" or not live:
+        return out
+    chunks = S.xent_chunks(c.V, c.width)
+    tgt = inp["tgt"][:live].long()
+    x = (inp["S"] + inp["bias"])[:live]
+    if wrapped_bias:      # bias[v0 + j % 4096] where bias[v0 + j] belongs
+        bias = inp["bias"].clone()
+        for v0, n, skip in chunks:
+            if skip == 0:
+                bias[v0:v0 + n] = inp["bias"][v0 + torch.arange(n) % S.GRAD_TILE]
+        hot = torch.zeros(live, c.V)
+        hot[torch.arange(live), tgt] = 1.0
+        out["grad"] = S._pad_rows((torch.exp(inp["S"][:live] + bias - inp["lse_in"][:live, None]) - hot) * S.xent_factor(c, inp, F32), c.cap)
+    if restart or last_tie:
+        if restart:      # the state is started on every chunk: only the last chunk's counted columns are left
+            v0, n, skip = chunks[-1]
+            seen, first = x[:, v0 + skip:v0 + n], v0 + skip
+        else:
+            seen, first = x, 0
+        arg = first + (seen.shape[1] - 1 - seen.flip(1).argmax(1) if last_tie else seen.argmax(1))
+        lse = torch.logsumexp(seen, 1)
+        rowloss = lse - x[torch.arange(live), tgt]
+        hit = (arg == tgt).int()
+        out.update(lse=S._pad_rows(lse, c.cap), rowloss=S._pad_rows(rowloss, c.cap), loss=rowloss.sum() * inp["scale"][0], hit=S._pad_rows(hit, c.cap),
+                   correct=hit.sum().reshape(1).int())
+    return out
+
+
+def test_fake_mlm_kernels_are_caught():
+    G = S.cases("G")
+    xent, live = _only("xent"), lambda c: S.mlm_live(c) > 0      # noqa: E731
+    multi = {c.index for c in G if c.op == "xent" and live(c) and len(S.xent_chunks(c.V, c.width)) > 1}
+    caught = {c.index for c, _ in _sweep("G", lambda c, i: _mlm32(c, i, restart=True), xent)}
+    assert caught and caught == multi, (sorted(caught ^ multi))
+    caught = {c.index: c for c, _ in _sweep("G", lambda c, i: _mlm32(c, i, last_tie=True), xent)}
+    assert {c.index for c in G if c.op == "xent" and live(c) and c.profile == "ties"} == set(caught), sorted(caught)
+    behind = {c.index for c in G if c.op == "xent" and S.mlm_live(c) < c.cap}
+    assert any(S.mlm_live(c) == 0 for c in G if c.index in behind) and any(S.mlm_kept(c) < 0 for c in G if c.index in behind)
+    for name in ("hit", "lse", "rowloss"):      # garbage behind the kept rows: caught on exactly the cases that have such rows
+        caught = {c.index for c, _ in _sweep("G", lambda c, i: _mlm32(c, i, dead=name), xent)}
+        assert caught and caught == behind, (name, sorted(caught ^ behind))
+    caught = {c.index for c, _ in _sweep("G", lambda c, i: _mlm32(c, i, gather_cols=256), _only("gather"))}
+    assert caught and caught == {c.index for c in G if c.op == "gather" and live(c) and c.H > 256}
+    assert {c.planes for c in G if c.index in caught} == {True, False}
+    caught = {c.index for c, _ in _sweep("G", lambda c, i: _mlm32(c, i, blocks_summed=256), _only("mask_tokens"))}
+    assert caught and caught == {c.index for c in G if c.op == "mask_tokens" and c.N * c.L > 65536}
+    assert not _sweep("G", lambda c, i: _mlm32(c, i, blocks_summed=1 << 30), _only("mask_tokens")), "the block-wise placement the fake is a variation of must pass"
+
+
+def _lowered(c, inp):
+    """the same inputs with the columns from 4096 of a chunk on lowered by 30 (they keep e^-30 of their probability) and the targets
+    that lay there moved 4096 columns forward; the log-sum-exp the gradient is handed is that of the new logits"""
+    live = S.mlm_live(c)
+    logits, tgt = inp["S"].clone(), inp["tgt"].clone()
+    for v0, n, _ in S.xent_chunks(c.V, c.width):
+        if n > S.GRAD_TILE:
+            logits[:, v0 + S.GRAD_TILE:v0 + n] -= 30.0
+            behind = (tgt >= v0 + S.GRAD_TILE) & (tgt < v0 + n)
+            tgt[behind] -= S.GRAD_TILE
+    lse = torch.zeros(c.cap)
+    lse[:live] = torch.logsumexp((logits.double() + inp["bias"].double())[:live], 1).float()
+    return dict(inp, S=logits, tgt=tgt, lse_in=lse)
+
+
+def test_wrapped_bias_passes_the_old_metric_and_fails_the_new():
+    """a gradient kernel that reads bias[v0 + j % 4096]: wrong from column 4096 of a chunk on, i.e. exactly in the cases with a chunk
+    wider than 4096.  The elementwise bound rejects every one of them, by five decades and more -- on most of them so does today's
+    metric (max |got - ref| / max |ref| < 2e-5, whose max |ref| is the p - 1 at the target), because a target or a column of weight
+    lies behind column 4095.  What today's metric cannot see is the same mistake in columns of little probability.  That is shown
+    with the same inputs, the columns behind 4095 lowered by 30 and the targets moved in front of them: the tensor-wide figure is
+    then far below 2e-5, the elementwise bound still rejects every case whose changed products are normal float32 numbers."""
+    xs = [c for c in S.cases("G") if c.op == "xent" and S.mlm_live(c) > 0]
+    wide = {c.index for c in xs if max(n for _, n, _ in S.xent_chunks(c.V, c.width)) > S.GRAD_TILE}
+    caught, old_pass_new_fail = set(), []
+    for c in xs:
+        inp = S.build(c)
+        ref, got = S.reference(c, inp), _mlm32(c, inp, wrapped_bias=True)
+        res = S.check(c, ref, got)
+        if any(not r <= 1.0 for _, r, _ in res):
+            caught.add(c.index)
+            assert [n for n, r, _ in res if not r <= 1.0] == ["grad"]
+        if c.index in wide:
+            inp = _lowered(c, inp)
+            ref, got = S.reference(c, inp), _mlm32(c, inp, wrapped_bias=True)
+            new = dict((n, r) for n, r, _ in S.check(c, ref, got))["grad"]
+            old = S.tensor_wide(got["grad"], ref["grad"])
+            print(f"case {c.index} ({c.profile}, V = {c.V}), columns behind 4095 lowered: tensor-wide {old:.2e}, elementwise {new:.3g} x bound")
+            if old < 2e-5 and new > 1.0:      # (a dominant logit that lay behind column 4095 still dominates when lowered: both reject)
+                old_pass_new_fail.append(c.index)
+    assert caught == wide and len(wide) >= 5, (sorted(caught), sorted(wide))
+    assert len(old_pass_new_fail) >= 5, "the wrapped bias index must pass today's metric and fail the elementwise bound"
