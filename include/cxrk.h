@@ -599,6 +599,21 @@ int cxrk_mlm_xent_grad(float* S, long ld, void* G, long ldg, long gplane, int ro
  *               the caller zeroes once).  gref and the partials are read only.
  *               Non-finite: a NaN anywhere in g or gref makes its block's partial NaN, hence dot NaN, the projection taken with
  *               coef = NaN and every element of g NaN; a bad reference gradient never silently disables the projection.
+ *
+ * Exponential moving average of the parameters over the same flat buffers.  Both calls follow grad_sqnorm's
+ * conventions (float4 accesses, 16-byte alignment or CXRK_ERR_ARG, a scalar n % 4 tail, grid-stride loops, n > 0, nothing launched
+ * and nothing written when a call is refused); neither takes scratch memory, uses an atomic or LDS, or synchronises.
+ * ema_update:   c = 1 - decay, formed once in fp32;  d = p[i] - avg[i];  avg[i] = fma(c, d, avg[i]): two roundings, nothing else
+ *               contracted.  8 B read + 4 B written per parameter; p is read only.  decay outside [0, 1] or NaN: CXRK_ERR_ARG.
+ *               The lerp form is the contract: p[i] == avg[i] leaves avg[i] as it is bit for bit (d = 0), so the average of a
+ *               parameter that never moved IS the parameter; decay == 1 (c = 0) leaves every avg[i] with a finite d as it is bit for
+ *               bit; decay == 0 gives avg[i] = p[i] up to the rounding of d.  Whenever the result equals avg[i] as a number, avg[i]
+ *               keeps its own bits: a negative zero stays a negative zero (the addition alone would make it +0).
+ *               Non-finite: as the torch expression avg + c * (p - avg).  A NaN or Inf in p[i] or avg[i] reaches avg[i] and no other
+ *               element; Inf - Inf and 0 * Inf give NaN, so at decay == 1 an infinite p[i] or avg[i] makes avg[i] NaN.
+ * flat_swap:    a[i] <-> b[i], moves only: every bit pattern (NaN payloads included) arrives as it left, and two swaps are the
+ *               identity.  8 B read + 8 B written per parameter, no temporary of the buffers' size.  a == b or overlapping ranges:
+ *               CXRK_ERR_ARG.
  */
 int cxrk_adam_fused(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,
                     float eps, float weight_decay, int step, float grad_scale, hipStream_t stream);
@@ -617,6 +632,8 @@ int cxrk_ewc_penalty(float* g, const float* p, const float* anchor, const float*
 size_t cxrk_agem_dots_partials_bytes(long n);
 int cxrk_agem_dots(const float* g, const float* gref, long n, float* partials, size_t ws_bytes, hipStream_t stream);
 int cxrk_agem_project(float* g, const float* gref, long n, const float* partials, float* stats, hipStream_t stream);
+int cxrk_ema_update(float* avg, const float* p, long n, float decay, hipStream_t stream);
+int cxrk_flat_swap(float* a, float* b, long n, hipStream_t stream);
 size_t cxrk_weight_reset_ws_bytes(void);
 int cxrk_weight_reset(float* pnew, const float* pold, long n, float threshold, unsigned long long* counters, float* ws,
                       size_t ws_bytes, hipStream_t stream);

@@ -54,6 +54,11 @@ Two extensions behind the same entry points (both off unless asked for):
     language-modelling loss of CXR-BERT's own head: every step masks its token ids on the device and trains
     contrastive + w * L_mlm; `train` logs `train/mlm_loss` and `train/mlm_acc` once per epoch, `save` / `load` carry the (seed, step
     counter) of the masking stream as `mlm.pt`.
+    `"ema_decay": d` (optionally `"ema_warmup"`, `"ema_eval"`, `"ema_teacher"`) keeps an exponential moving average of the trained
+    parameters, updated by one launch after every step.  With `"ema_eval": True` `val` / `test` (the retrieval
+    metrics included) evaluate the averaged weights under the same metric tags; with `"ema_teacher": True` (needs
+    `"distill_weight"`) the distillation teacher is the average itself, a momentum teacher.  `train` logs `train/ema_decay` once per
+    epoch, `save` / `load` carry the average as `ema.pt`; the saved model files stay the raw weights.
   * data parallelism: with `torch.distributed` initialised (one process per GPU) every rank draws the SAME global batch from its
     loader (same sampler seed) and trains on its contiguous row shard; adapter gradients (0.5 MB) are summed with one
     all-reduce of the flat gradient buffer, weighted by shard size, so the update equals the single-process global-batch one
@@ -61,6 +66,7 @@ Two extensions behind the same entry points (both off unless asked for):
 """
 from __future__ import annotations
 
+import contextlib
 import copy
 import inspect
 import math
@@ -75,8 +81,8 @@ from torch.utils.data import ConcatDataset, DataLoader, RandomSampler, Subset, T
 from . import functional as Fh
 from . import kernels as K
 from . import optim as cxr_optim
-from .contrastive import (RETRIEVAL_KS, JointContrastiveTrainer, check_agem_options, check_distill_options, check_ks,
-                          retrieval_metrics)
+from .contrastive import (RETRIEVAL_KS, JointContrastiveTrainer, check_agem_options, check_distill_options, check_ema_options,
+                          check_ks, retrieval_metrics)
 from .DataRetrieval import CHEXPERT_COMPETITION_CLASSES, basic_create_prompts, create_prompts
 from .health_multimodal.text import get_cxr_bert_inference
 from .models import myLinearModel, myMLP
@@ -179,6 +185,7 @@ def joint_options(joint_encoders):
     kw = {JOINT_STEP_KEYS[k]: v for k, v in je.items() if k in JOINT_STEP_KEYS and v is not None}
     check_distill_options(kw.get("distill_weight"), kw.get("distill_temperature"))
     check_agem_options(*(kw.get(k) for k in ("agem_memory", "agem_batch", "agem_every", "agem_seed")))
+    check_ema_options(*(kw.get(k) for k in ("ema_decay", "ema_warmup", "ema_eval", "ema_teacher", "distill_weight")))
     kw["temperature"] = float(kw.get("temperature", 0.07))
     kw.setdefault("optim", OPTIM)
     if kw.get("augment") in (None, False):
@@ -806,6 +813,9 @@ class Trainer:
             if applied > 0:                         # the fraction of this epoch's steps whose gradient was projected
                 self.writer.add_scalar('train/agem_projected', proj / applied, epoch)
                 self.writer.add_scalar('train/agem_dot', agem["dot"], epoch)
+        ema = self._joint.current_ema()             # None without "ema_decay"; host numbers, no read-back
+        if ema is not None and ema["last_decay"] is not None:
+            self.writer.add_scalar('train/ema_decay', ema["last_decay"], epoch)
 
     @staticmethod
     def _parse_retrieval(opt):
@@ -846,8 +856,28 @@ class Trainer:
                     self.writer.add_scalar(f"{val_test}/Retrieval/{direction} {k}", v, epoch)
         return m
 
+    @contextlib.contextmanager
+    def _eval_weights(self):
+        """the weights an evaluation reads: with `"ema_eval": True` the parameter average (`JointContrastiveTrainer.averaged()`,
+        DESIGN.md §5.14), else the parameters as they are.  The cached prompt embeddings belong to the weights they were made with:
+        the cache is emptied on entry and on exit."""
+        if self._joint is None or not getattr(self._joint, "ema_eval", False):
+            yield
+            return
+        self._bert_cache.clear()
+        try:
+            with self._joint.averaged():
+                yield
+        finally:
+            self._bert_cache.clear()
+
     @torch.no_grad()
     def _eval_loop(self, loader, criterion, epoch, log_tag):
+        with self._eval_weights():
+            return self._eval_batches(loader, criterion, epoch, log_tag)
+
+    def _eval_batches(self, loader, criterion, epoch, log_tag):
+        """the body of `_eval_loop` (the retrieval evaluation included), under no_grad and on the weights `_eval_weights` chose"""
         self._set_mode(False)
         y_true, y_pred, y_score = [], [], []
         batch_idx = 0
@@ -1043,6 +1073,8 @@ class Trainer:
             if self._joint.mlm_state is not None:   # plain numbers: the masking stream resumes where it stopped
                 seed, counter = self._joint.mlm_state
                 torch.save({"seed": int(seed), "counter": int(counter)}, os.path.join(self.writer.log_dir, 'mlm.pt'))
+            if self._joint.ema is not None:         # the model files above stay the raw weights; the average travels on its own
+                torch.save(self._joint.ema.state_dict(), os.path.join(self.writer.log_dir, 'ema.pt'))
         if self._joint is not None and self._joint.memory is not None:   # every rank holds rows of its own shards
             torch.save({"memory": self._joint.memory.state_dict(), "agem": self._joint.agem.state_dict(),
                         "steps": int(self._joint.agem_steps)}, os.path.join(self.writer.log_dir, self._agem_file()))
@@ -1092,6 +1124,9 @@ class Trainer:
                 # just loaded, then take the saved tensors; size and keys are checked by `FrozenTeacher.load_state_dict`
                 self._joint.snapshot_teacher()
                 self._joint.teacher.load_state_dict(torch.load(tpath, map_location="cpu", weights_only=True))
+            if self._joint.ema is not None:   # keys, decay, warmup and the size of avg are checked by `EMA.load_state_dict`; with
+                # "ema_teacher" the teacher's flat copy IS avg: this load and the one above land in the same storage
+                self._joint.ema.load_state_dict(torch.load(os.path.join(self.writer.log_dir, 'ema.pt'), map_location="cpu", weights_only=True))
             if self._joint.mlm_state is not None:
                 path = os.path.join(self.writer.log_dir, 'mlm.pt')
                 sd = torch.load(path, map_location="cpu", weights_only=True)

@@ -123,6 +123,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_agem_dots_partials_bytes": (Z, [L]),
     "cxrk_agem_dots": (I, [P, P, L, P, Z, P]),
     "cxrk_agem_project": (I, [P, P, L, P, P, P]),
+    "cxrk_ema_update": (I, [P, P, L, F, P]),
+    "cxrk_flat_swap": (I, [P, P, L, P]),
     "cxrk_weight_reset_ws_bytes": (Z, []),
     "cxrk_weight_reset": (I, [P, P, L, F, P, P, Z, P]),
     "cxrk_gemm_wgrad_splitk": (I, [I, I, I, I]),

@@ -52,6 +52,15 @@ sharded step masks as the single-process step does), runs the text encoder once 
 the projected CLS embedding to the contrastive head and the last hidden state to `functional.mlm_loss`, and adds w * L_mlm to the
 objective as a second root of the step's one backward: one more collective than the plain step's, the scalar all-reduce of the number
 of selected tokens.  With `mlm_weight=None` (the default) a step issues exactly the calls it always did.
+
+`ema_decay=d`: an exponential moving average of every trained parameter (`optim.EMA`, +4 B per parameter).  It starts
+as a copy of the parameters at the entry of the first `step` and takes one launch after each optimiser step (with `ema_warmup`, the
+default, at the decay min(d, (1 + t) / (10 + t))); the training itself is not touched.  `averaged()` is a context manager inside which
+the encoders read the averaged parameters (the two flat buffers are swapped, and swapped back on exit); `ema_eval=True` asks `Trainer`
+to evaluate inside it.  `ema_teacher=True` (with `distill_weight`) makes the teacher a momentum teacher: its parameters ARE the average,
+as of the end of the previous step.  BatchNorm running statistics are module buffers, not parameters, and are not averaged; the joint
+trainers run BatchNorm in eval mode.  No collective: the replicas' averages are bit-identical because their parameters are.  With
+`ema_decay=None` (the default) a step issues exactly the calls it always did.
 """
 from __future__ import annotations
 
@@ -275,9 +284,17 @@ class FrozenTeacher:
     tensors IN PLACE: every tensor the copies hold keeps its identity, and the encoders derive nothing from their parameters that
     outlives a forward (q/k/v are fused by adjacency, BatchNorm is folded and planes are split per call), so nothing is stale."""
 
-    def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, optimizer):
+    def __init__(self, image_model: torch.nn.Module, text_model: torch.nn.Module, optimizer, flat: Optional[torch.Tensor] = None):
+        """`flat`: a buffer laid out like `optimizer.flat_p` to use as the flat copy in place of a clone (the momentum teacher of
+        DESIGN.md §5.14 hands in the parameter average: the teacher's parameters are then views of it, no second copy exists, and
+        `refresh()` leaves it to its owner)"""
         import copy
-        self.flat = optimizer.flat_p.detach().clone()
+        if flat is not None and (flat.dtype != torch.float32 or tuple(flat.shape) != (int(optimizer.numel),) or not flat.is_contiguous()
+                                 or flat.device != optimizer.flat_p.device or flat.data_ptr() == optimizer.flat_p.data_ptr()):
+            raise ValueError(f"FrozenTeacher: flat must be a contiguous float32 buffer of {int(optimizer.numel)} elements on the "
+                             f"optimiser's device, other than its flat_p")
+        self._owns_flat = flat is None
+        self.flat = optimizer.flat_p.detach().clone() if flat is None else flat
         self.numel = int(optimizer.numel)
         base = optimizer.flat_p.data_ptr()
         memo = {}
@@ -304,8 +321,10 @@ class FrozenTeacher:
 
     @torch.no_grad()
     def refresh(self, optimizer) -> None:
-        """take the student's current parameters and buffers, in place"""
-        self.flat.copy_(optimizer.flat_p)
+        """take the student's current parameters and buffers, in place (a flat copy handed in at construction is its owner's: only
+        the cloned tensors are refreshed)"""
+        if self._owns_flat:
+            self.flat.copy_(optimizer.flat_p)
         for t, s in self._pairs:
             t.copy_(s)
 
@@ -346,6 +365,31 @@ def check_agem_options(memory, batch, every, seed) -> tuple:
         if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < lo):
             raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
     return memory, batch, 1 if every is None else every, 0 if seed is None else seed
+
+
+def check_ema_options(decay, warmup, ema_eval, teacher, distill_weight=None) -> tuple:
+    """(ema_decay, ema_warmup, ema_eval, ema_teacher) checked, the defaults (warmup on, the other two off) filled in; options given
+    without `ema_decay` are refused, and so is `ema_teacher` without `distill_weight`"""
+    if decay is None:
+        if warmup is not None or ema_eval is not None or teacher is not None:
+            raise ValueError("ema_warmup / ema_eval / ema_teacher are options of the parameter average; they were given without ema_decay")
+        return None, None, None, None
+    if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (math.isfinite(decay) and 0.0 <= decay <= 1.0):
+        raise ValueError(f"ema_decay must be a number in [0, 1], got {decay!r}")
+    for name, v in (("ema_warmup", warmup), ("ema_eval", ema_eval), ("ema_teacher", teacher)):
+        if v is not None and not isinstance(v, bool):
+            raise ValueError(f"{name} must be True or False, got {v!r}")
+    if teacher and distill_weight is None:
+        raise ValueError("ema_teacher makes the teacher of similarity distillation a momentum teacher; it was given without distill_weight")
+    return float(decay), True if warmup is None else warmup, bool(ema_eval), bool(teacher)
+
+
+def _refuse_averaged(trainer, what: str) -> None:
+    """inside `JointContrastiveTrainer.averaged()` the flat parameter buffer holds the average: whatever trains on it, anchors it or
+    copies it is refused (a trainer without the attribute was never inside)"""
+    if getattr(trainer, "_averaging", False):
+        raise RuntimeError(f"JointContrastiveTrainer.{what}: called inside averaged(); the flat parameter buffer holds the average "
+                           f"until the context exits")
 
 
 MLM_PROBABILITY = 0.15                        # HF DataCollatorForLanguageModeling's default
@@ -410,7 +454,9 @@ class JointContrastiveTrainer:
                  distill_temperature: Optional[float] = None, agem_memory: Optional[int] = None,
                  agem_batch: Optional[int] = None, agem_every: Optional[int] = None, agem_seed: Optional[int] = None,
                  mlm_weight: Optional[float] = None, mlm_probability: Optional[float] = None, mlm_seed: Optional[int] = None,
-                 mlm_mask_token_id: Optional[int] = None, mlm_special_ids: Optional[Tuple[int, ...]] = None):
+                 mlm_mask_token_id: Optional[int] = None, mlm_special_ids: Optional[Tuple[int, ...]] = None,
+                 ema_decay: Optional[float] = None, ema_warmup: Optional[bool] = None, ema_eval: Optional[bool] = None,
+                 ema_teacher: Optional[bool] = None):
         """`optim="adamw"`: `optim.AdamW` with decoupled `weight_decay` (default 0.01; parameters with ndim <= 1 do
         not decay) and, with `max_grad_norm`, clipping of the global gradient norm (`inf`: the norm is taken and reported, nothing
         is clipped).  `warmup_steps` / `total_steps` / `lr_decay` ("constant" | "linear" | "cosine") / `min_lr_ratio`: an
@@ -433,7 +479,18 @@ class JointContrastiveTrainer:
         contrastive + w * L_mlm, L_mlm the mean cross-entropy of HF's MLM head over the selected tokens of the global batch.  It
         implies that the head (`cls.predictions.*`) is trained.  `mlm_seed` (default: drawn from torch's CPU generator) seeds the
         draws; `mlm_state` is the (seed, step counter) pair.  Not with `micro_batch`.  `mlm_weight=None` (the default) issues exactly
-        the calls it always did."""
+        the calls it always did.
+        `ema_decay` = d in [0, 1]: `self.ema`, an `optim.EMA` of the flat parameter buffer.  It starts at the entry of
+        the first `step` (or of the first `snapshot_teacher()` with `ema_teacher`), not here: `Trainer` broadcasts the parameters
+        and loads checkpoints after construction, and the average has to start from those values.  `step` updates it after the
+        optimiser's step and the clamp of theta; `consolidate`, the A-GEM reference pass and `_gradient` never do.  `ema_warmup`
+        (default True): the decay of update t is min(d, (1 + t) / (10 + t)).  `averaged()`: the encoders read the average.
+        `ema_eval`: kept for `Trainer`, which then evaluates inside `averaged()`.  `ema_teacher` (needs `distill_weight`): the
+        teacher's flat copy is the average itself.  Losses and parameters of a run with `ema_decay` and no `ema_teacher` are bit for
+        bit those of the run without it."""
+        self.ema_decay, self.ema_warmup, self.ema_eval, self.ema_teacher = check_ema_options(ema_decay, ema_warmup, ema_eval, ema_teacher,
+                                                                                              distill_weight)
+        self.ema, self._averaging = None, False
         self.agem_memory, self.agem_batch, self.agem_every, self.agem_seed = check_agem_options(agem_memory, agem_batch, agem_every,
                                                                                                 agem_seed)
         self.micro_batch = check_micro_batch(micro_batch)
@@ -549,6 +606,8 @@ class JointContrastiveTrainer:
             from .memory import EpisodicMemory
             self.agem = cxr_optim.AGEM(self.optimizer)
             self.memory = EpisodicMemory(self.agem_memory, seed=self.agem_seed)
+        if self.ema_decay is not None:   # no buffer yet: `begin()` runs at the first step
+            self.ema = cxr_optim.EMA(self.optimizer, self.ema_decay, warmup=self.ema_warmup)
         self.world, self.rank = 1, 0
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
@@ -804,13 +863,47 @@ class JointContrastiveTrainer:
         """End of a task (needs `distill_weight`): freeze the current encoders as the teacher of the steps that follow.  The first
         call builds the copies (`FrozenTeacher`); a later one overwrites their flat parameter copy and buffers in place.  Under
         data parallelism every rank calls it at the same step: the replicas are identical, so are the teachers, and nothing is
-        communicated."""
+        communicated.  With `ema_teacher` the copies' parameters are views of the parameter average (`self.ema.avg`, started here if
+        no step has run yet): distillation begins at the first call as ever, the teacher then moves with every step's update of the
+        average, and a later call refreshes only the cloned tensors (module buffers)."""
         if self.distill_weight is None:
             raise ValueError("JointContrastiveTrainer.snapshot_teacher: this trainer was constructed without distill_weight")
+        _refuse_averaged(self, "snapshot_teacher")
         if self.teacher is None:
-            self.teacher = FrozenTeacher(self.image_model, self.text_model, self.optimizer)
+            flat = None
+            if self.ema_teacher:
+                self.ema.begin()
+                flat = self.ema.avg
+            self.teacher = FrozenTeacher(self.image_model, self.text_model, self.optimizer, flat=flat)
         else:
             self.teacher.refresh(self.optimizer)
+
+    # ------------------------------------------------------------------ parameter average (DESIGN.md §5.14)
+    @contextlib.contextmanager
+    def averaged(self):
+        """While it is open the two encoders (and `current_temperature()`) read the averaged parameters: one `flat_swap` launch on
+        entry exchanges the average and the flat parameter buffer that every trained parameter is a view of, one more on exit
+        (in `finally`) puts both back bit for bit.  No copy of the model is made.  Inside, `step`, `consolidate`, `remember`,
+        `snapshot_teacher` and a nested `averaged()` raise.  Module buffers (BatchNorm running statistics) are not averaged: the
+        averaged model runs on the raw model's statistics.  Under data parallelism every rank enters and leaves alike."""
+        if self.ema is None:
+            raise ValueError("JointContrastiveTrainer.averaged: this trainer was constructed without ema_decay")
+        _refuse_averaged(self, "averaged")
+        self.ema.begin()
+        self.ema.swap()
+        self._averaging = True
+        try:
+            yield self
+        finally:
+            self.ema.swap()
+            self._averaging = False
+
+    def current_ema(self) -> Optional[dict]:
+        """the parameter average as host numbers: "updates", "decay" and "last_decay" (the decay of the last update, None before it),
+        all from host state: no sync.  None without `ema_decay`."""
+        if self.ema is None:
+            return None
+        return {"updates": int(self.ema.updates), "decay": float(self.ema.decay), "last_decay": self.ema.last_decay}
 
     def current_distill(self) -> Optional[float]:
         """the unweighted L_d of the last distilled step as a host float (None without a teacher or before the first distilled step):
@@ -935,7 +1028,13 @@ class JointContrastiveTrainer:
         collective, as any failure of one data-parallel rank does: the job has to be torn down (torchrun / the RCCL watchdog).
 
         With `micro_batch` < this rank's rows the forward and backward run chunk by chunk (`_chunked_forward_backward`); the hook
-        is then handed only to the encoder calls of the step's LAST backward, after which every range is complete."""
+        is then handed only to the encoder calls of the step's LAST backward, after which every range is complete.
+
+        With `ema_decay` the parameter average starts here, at the entry of the first step (a copy of the parameters as they are
+        by then), and takes its one launch at the very end, after the optimiser's step and the clamp."""
+        if self.ema is not None:
+            _refuse_averaged(self, "step")
+            self.ema.begin()
         if self.agem is not None and len(self.memory) > 0:
             self._agem_reference(int(images.shape[0]))
         loss = self._gradient(images, input_ids, attention_mask, labels, keys)
@@ -948,6 +1047,8 @@ class JointContrastiveTrainer:
         self.optimizer.step()
         if self.logit_scale is not None:
             K.clamp_inplace(self.logit_scale.data, *self.log_scale_bounds)
+        if self.ema is not None:         # the decay is a host float argument of the one launch: no sync
+            self.ema.update()
         return loss.detach()
 
     # ------------------------------------------------------------------ episodic memory and A-GEM
@@ -972,6 +1073,7 @@ class JointContrastiveTrainer:
         all ranks hold the same number of rows (the sampler's indices are then the same everywhere), and raises if they do not."""
         if self.memory is None:
             raise ValueError("JointContrastiveTrainer.remember: this trainer was constructed without agem_memory")
+        _refuse_averaged(self, "remember")
         kept = self.memory.add_task(batches)
         if self.world > 1:
             import torch.distributed as dist
@@ -1002,6 +1104,7 @@ class JointContrastiveTrainer:
         own and is bit-identical on every rank."""
         if self.ewc is None:
             raise ValueError("JointContrastiveTrainer.consolidate: this trainer was constructed without ewc_lambda")
+        _refuse_averaged(self, "consolidate")
         used = 0
         if self.ewc.fisher == "empirical":
             self.ewc.begin_estimate()

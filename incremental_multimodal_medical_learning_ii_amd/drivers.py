@@ -9,6 +9,8 @@ and `DATA_INCREMENTAL.py:74-97` (hyper-parameters as arguments instead of litera
     python -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --joint --cl ewc --ewc-lambda 1e4 --ewc-batches 8
     python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --joint --cl lwf --distill-weight 1.0
     python -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --joint --cl agem --agem-memory 256
+    python -m incremental_multimodal_medical_learning_ii_amd.drivers zero-joint --joint --ema-decay 0.999 --ema-eval
+    python -m incremental_multimodal_medical_learning_ii_amd.drivers data-inc --joint --cl lwf --ema-decay 0.995 --ema-teacher
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29511 \
         -m incremental_multimodal_medical_learning_ii_amd.drivers class-inc --mode class-pos-neg --batch-size 2048
 
@@ -141,6 +143,7 @@ def joint_encoders_from_args(args, image_model, kind=None, train_loader=None) ->
             **optimiser_from_args(args, kind, train_loader),
             **continual_from_args(args),
             **mlm_from_args(args),
+            **ema_from_args(args),
             "augment": augment_from_args(args),
             "retrieval": retrieval_from_args(args)}
 
@@ -151,6 +154,20 @@ def mlm_from_args(args) -> dict:
     if getattr(args, "mlm_weight", None) is None:
         return {}
     return {k: getattr(args, k) for k in ("mlm_weight", "mlm_probability", "mlm_seed") if getattr(args, k, None) is not None}
+
+
+def ema_from_args(args) -> dict:
+    """`--ema-decay D [--ema-no-warmup] [--ema-eval] [--ema-teacher]` -> the `joint_encoders` keys of the parameter average
+    (DESIGN.md 5.14); without `--ema-decay` an empty dict: the keys exist only when their flag is given"""
+    if getattr(args, "ema_decay", None) is None:
+        return {}
+    out = {"ema_decay": args.ema_decay}
+    if getattr(args, "ema_no_warmup", False):
+        out["ema_warmup"] = False
+    for flag in ("ema_eval", "ema_teacher"):
+        if getattr(args, flag, False):
+            out[flag] = True
+    return out
 
 
 def retrieval_from_args(args):
@@ -400,12 +417,22 @@ def make_parser():
                     help="--mlm-weight: the fraction of the non-special tokens selected per step (default 0.15)")
     ap.add_argument("--mlm-seed", type=int, default=None, metavar="S",
                     help="--mlm-weight: seed of the masking draws (default: drawn from torch's CPU generator)")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="--joint: keep an exponential moving average of the trained parameters with decay D in [0, 1], one launch "
+                         "per step (DESIGN.md 5.14)")
+    ap.add_argument("--ema-no-warmup", action="store_true",
+                    help="--ema-decay: use D from the first update on (default: min(D, (1 + t) / (10 + t)) at update t)")
+    ap.add_argument("--ema-eval", action="store_true",
+                    help="--ema-decay: val / test (and --retrieval) evaluate the averaged weights")
+    ap.add_argument("--ema-teacher", action="store_true",
+                    help="--ema-decay with --cl lwf: the distillation teacher is the average itself (a momentum teacher)")
     ap.add_argument("--pretrained-image", default=None)
     return ap
 
 
 def parse_args(argv=None):
-    """`make_parser().parse_args` plus the refusals that concern `--cl ewc`, `--cl lwf` and `--cl agem` (parser errors: exit status 2)"""
+    """`make_parser().parse_args` plus the refusals that concern `--cl ewc`, `--cl lwf`, `--cl agem`, `--mlm-weight` and `--ema-decay`
+    (parser errors: exit status 2)"""
     ap = make_parser()
     args = ap.parse_args(argv)
     given = [f for f in ("ewc_lambda", "ewc_batches", "ewc_gamma", "ewc_fisher") if getattr(args, f) is not None]
@@ -463,6 +490,17 @@ def parse_args(argv=None):
             ap.error(f"--mlm-seed must be >= 0, got {args.mlm_seed}")
         if getattr(args, "micro_batch", None) is not None:
             ap.error("--mlm-weight with --micro-batch is out of scope: the micro-batched step keeps no last hidden state")
+    given = [f for f in ("ema_no_warmup", "ema_eval", "ema_teacher") if getattr(args, f)]
+    if given and args.ema_decay is None:
+        ap.error("--" + given[0].replace("_", "-") + " configures the parameter average and needs --ema-decay")
+    if args.ema_decay is not None:
+        if not args.joint:
+            ap.error("--ema-decay averages the encoders of the north-star step and needs --joint (the adapter schedules have no such "
+                     "average)")
+        if not 0.0 <= args.ema_decay <= 1.0:
+            ap.error(f"--ema-decay must be in [0, 1], got {args.ema_decay}")
+        if args.ema_teacher and args.cl != "lwf":
+            ap.error("--ema-teacher makes the teacher of similarity distillation a momentum teacher and needs --cl lwf")
     return args
 
 

@@ -1829,6 +1829,23 @@ def agem_project(g: torch.Tensor, gref: torch.Tensor, partials: torch.Tensor, st
     check(lib.cxrk_agem_project(_p(g), _p(gref), n, _p(partials), _p(stats), _stream()), "cxrk_agem_project")
 
 
+def ema_update(avg: torch.Tensor, p: torch.Tensor, decay: float) -> None:
+    """avg += (1 - decay) * (p - avg) over flat fp32 buffers, in place (include/cxrk.h, "ema_update"): p == avg and decay == 1 leave
+    avg as it is bit for bit; p is not modified.  `decay` in [0, 1] is a host float argument of the launch."""
+    lib = _lib.load()
+    n = _flat(avg, "ema_update.avg").numel()
+    _flat(p, "ema_update.p", n)
+    check(lib.cxrk_ema_update(_p(avg), _p(p), n, float(decay), _stream()), "cxrk_ema_update")
+
+
+def flat_swap(a: torch.Tensor, b: torch.Tensor) -> None:
+    """exchange two flat fp32 buffers exactly, in place and in one launch (include/cxrk.h, "flat_swap"); they must not overlap"""
+    lib = _lib.load()
+    n = _flat(a, "flat_swap.a").numel()
+    _flat(b, "flat_swap.b", n)
+    check(lib.cxrk_flat_swap(_p(a), _p(b), n, _stream()), "cxrk_flat_swap")
+
+
 def sgd(p, g, lr, weight_decay: float = 0.0, grad_scale: float = 1.0):
     lib = _lib.load()
     check(lib.cxrk_sgd(_p(_chk(p, "sgd.p")), _p(_chk(g, "sgd.g")), p.numel(), float(lr), float(weight_decay),

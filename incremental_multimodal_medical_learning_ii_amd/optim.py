@@ -9,7 +9,8 @@ conv filters) is preserved.
 
 `AdamW` (decoupled weight decay with a no-decay set, global-norm clipping) and `LRSchedule` (warmup / decay) are opt-in additions
 that the reference does not have; so is `EWC`, elastic weight consolidation over the same flat buffers (§5.10).  So is
-`AGEM`, A-GEM's projection of the step's gradient against an episodic-memory gradient (§5.12).
+`AGEM`, A-GEM's projection of the step's gradient against an episodic-memory gradient (§5.12), and `EMA`, the exponential moving
+average of the flat parameter buffer (§5.14).
 """
 from __future__ import annotations
 
@@ -485,3 +486,97 @@ class AGEM:
             raise ValueError(f"AGEM.load_state_dict: 'applied' must be >= 0, got {sd['applied']!r}")
         self._stats.copy_(st)
         self.applied, self.valid = int(sd["applied"]), False
+
+
+class EMA:
+    """Exponential moving average of the parameters over the flat buffer of any `_FlatOptimizer`:
+    avg <- avg + (1 - d_t) (flat_p - avg) after every optimiser step, in one launch (`kernels.ema_update`).
+
+    `begin()` allocates `avg` and sets it to `flat_p` (the one allocation, +4 B per parameter; a second call does nothing).
+    `update()` counts the update and passes the step's decay d_t -- `decay`, or with `warmup` min(decay, (1 + t) / (10 + t)) at
+    update t = 1, 2, ... -- as a host float argument of the launch, as the learning-rate schedule is passed: no launch and no sync
+    of its own.  `last_decay` keeps it.  `swap()` exchanges `avg` and `optimizer.flat_p` exactly, in one launch, so that the modules
+    (views of `flat_p`) read the averaged parameters until the next `swap()`; `swapped` says which state holds.  A parameter that
+    never moved is its own average bit for bit, and so is every parameter at decay 1 (include/cxrk.h, "ema_update")."""
+
+    def __init__(self, optimizer: _FlatOptimizer, decay: float, warmup: bool = True):
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not (math.isfinite(decay) and 0.0 <= decay <= 1.0):
+            raise ValueError(f"EMA: decay must be a number in [0, 1], got {decay!r}")
+        if not isinstance(warmup, bool):
+            raise ValueError(f"EMA: warmup must be True or False, got {warmup!r}")
+        self.optimizer, self.decay, self.warmup = optimizer, float(decay), warmup
+        self.avg: Optional[torch.Tensor] = None
+        self.updates, self.last_decay, self.swapped = 0, None, False
+
+    @torch.no_grad()
+    def begin(self) -> None:
+        """avg = a copy of `optimizer.flat_p`, once"""
+        if self.avg is None:
+            self.avg = self.optimizer.flat_p.detach().clone()
+
+    def decay_at(self, updates: int) -> float:
+        """d_t of update number `updates` (counted from 1), in double on the host"""
+        return min(self.decay, (1.0 + updates) / (10.0 + updates)) if self.warmup else self.decay
+
+    @torch.no_grad()
+    def update(self) -> None:
+        """avg += (1 - d_t) * (flat_p - avg): one launch"""
+        if self.avg is None:
+            raise ValueError("EMA.update: no average yet (call begin() first)")
+        if self.swapped:
+            raise ValueError("EMA.update: the buffers are swapped (flat_p holds the average); call swap() first")
+        self.updates += 1
+        self.last_decay = self.decay_at(self.updates)
+        K.ema_update(self.avg, self.optimizer.flat_p, self.last_decay)
+
+    @torch.no_grad()
+    def swap(self) -> None:
+        """avg <-> flat_p: one launch"""
+        if self.avg is None:
+            raise ValueError("EMA.swap: no average yet (call begin() first)")
+        K.flat_swap(self.avg, self.optimizer.flat_p)
+        self.swapped = not self.swapped
+
+    def state_dict(self) -> dict:
+        """tensors and plain numbers only (loadable with weights_only=True); refused while swapped: `avg` would hold the raw weights"""
+        if self.swapped:
+            raise ValueError("EMA.state_dict: the buffers are swapped (avg holds the raw parameters); call swap() first")
+        sd = {"numel": int(self.optimizer.numel), "decay": float(self.decay), "warmup": bool(self.warmup), "updates": int(self.updates)}
+        if self.avg is not None:
+            sd["avg"] = self.avg.detach().cpu()
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, sd: dict) -> None:
+        """strict: the keys of `state_dict()`, the same decay and warmup, and an `avg` of exactly `optimizer.numel` float32 elements;
+        a refused state changes nothing.  `avg` is filled in place when it exists (a momentum teacher's parameters are views of it)."""
+        if not isinstance(sd, dict):
+            raise ValueError(f"EMA.load_state_dict: expected a dict, got {type(sd).__name__}")
+        want = {"numel", "decay", "warmup", "updates"}
+        if not want <= set(sd) or set(sd) - want - {"avg"}:
+            raise ValueError(f"EMA.load_state_dict: keys {sorted(sd)} (expected {sorted(want)} and, once begun, 'avg')")
+        if self.swapped:
+            raise ValueError("EMA.load_state_dict: the buffers are swapped; call swap() first")
+        n = self.optimizer.numel
+        if isinstance(sd["numel"], bool) or not isinstance(sd["numel"], int) or sd["numel"] != n:
+            raise ValueError(f"EMA.load_state_dict: the state belongs to a flat buffer of {sd['numel']!r} elements, this one has {n}")
+        if isinstance(sd["decay"], bool) or not isinstance(sd["decay"], (int, float)) or float(sd["decay"]) != self.decay:
+            raise ValueError(f"EMA.load_state_dict: the state was written with decay={sd['decay']!r}, this object has {self.decay!r}")
+        if sd["warmup"] is not self.warmup:
+            raise ValueError(f"EMA.load_state_dict: the state was written with warmup={sd['warmup']!r}, this object has {self.warmup!r}")
+        updates = sd["updates"]
+        if isinstance(updates, bool) or not isinstance(updates, int) or updates < 0:
+            raise ValueError(f"EMA.load_state_dict: 'updates' must be an integer >= 0, got {updates!r}")
+        avg = sd.get("avg")
+        if avg is None:
+            if updates > 0:
+                raise ValueError(f"EMA.load_state_dict: {updates} update(s) need the tensor 'avg'")
+        elif not isinstance(avg, torch.Tensor) or avg.dtype != torch.float32 or tuple(avg.shape) != (n,):
+            raise ValueError(f"EMA.load_state_dict: 'avg' must be a float32 tensor of {n} elements (this optimiser's flat buffer), got "
+                             f"{(avg.dtype, tuple(avg.shape)) if isinstance(avg, torch.Tensor) else type(avg).__name__}")
+        if avg is not None:
+            if self.avg is None:
+                self.avg = torch.empty_like(self.optimizer.flat_p)
+            self.avg.copy_(avg)
+        self.updates = updates
+        self.last_decay = self.decay_at(updates) if updates > 0 else None
