@@ -483,6 +483,25 @@ int cxrk_group_mean_bwd(const float* dout, int G, int n, int D, float* din, hipS
  * -1 for N, M, D < 1, ld < D, exactly one key pointer NULL, or (pair form) diag_off outside [0, M - N]. */
 int cxrk_retrieval_ranks(const float* Q, long ldq, int N, const float* G, long ldg, int M, int D, int diag_off,
                          const long long* keys_q, const long long* keys_g, float* pos, int* greater, int* ties, hipStream_t stream);
+/* topk_neighbours — for every query row i the k best gallery rows j by s(i,j) = sum_d Q[i][d] G[j][d] (csrc/topk.hip), again WITHOUT
+ * the [N][M] block and with the scores of retrieval_ranks bit for bit (same tile code, both precision modes).  One total order:
+ * score descending, every NaN above every number, then gallery index ascending — the order of the signed 64-bit key
+ * (enc(s) << 32) | (0xFFFFFFFF - j).  score[N][k] fp32 / index[N][k] int32, each row sorted by it, no index twice; with fewer
+ * than k candidates the remaining slots are index -1, score -inf.  exclude_off >= 0: column i + exclude_off is no candidate of
+ * row i (leave-one-out of a bank against itself; the rank offset under data parallelism; exclude_off + N <= M); -1: none.
+ * Two launches, no atomics, no host sync: per-block sorted lists into `slab` as [N][split][k] keys, then a merge per row; the result
+ * does not depend on the split.  slab: the lists' memory, 256-byte aligned; exactly cxrk_topk_neighbours_slab_bytes(N, M, k) bytes
+ * are written (the query gives 0 for bad arguments; CXRK_ERR_WS when slab_bytes is below it).
+ * -1 for k outside [1, 64], N, M, D < 1, ld < D, exclude_off < -1 or exclude_off + N > M; nothing is launched then. */
+size_t cxrk_topk_neighbours_slab_bytes(int N, int M, int k);
+int cxrk_topk_neighbours(const float* Q, long ldq, int N, const float* G, long ldg, int M, int D, int k, int exclude_off,
+                         float* score, int* index, void* slab, size_t slab_bytes, hipStream_t stream);
+/* knn_vote — the weighted kNN vote (Wu et al. 2018) for multi-hot labels[M][C] (row pitch ldl >= C) on the lists above:
+ *   out[i][c] = sum_n w_n labels[index[i][n]][c] / sum_n w_n,  w_n = expf((score[i][n] - score[i][0]) * inv_temperature),
+ * n ascending in fp32 (one thread per output, no atomics).  Slots with index -1 have weight 0.  A row that holds a NaN score, an
+ * index outside [-1, M) (never read) or no neighbour at all gives NaN in all C outputs.  1 <= k <= 64. */
+int cxrk_knn_vote(const float* score, const int* index, int N, int k, const float* labels, long ldl, int M, int C,
+                  float inv_temperature, float* out, hipStream_t stream);
 /* out = alpha * (alpha_dev ? *alpha_dev : 1) * x * (mask_src > 0): nn.ReLU backward (models.py:10) and chain-rule scaling
  * by an upstream scalar gradient that lives on the device. */
 int cxrk_scale_mask(const float* x, const float* mask_src, const float* alpha_dev, float alpha, long n, float* out,

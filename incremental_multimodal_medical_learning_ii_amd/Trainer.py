@@ -31,6 +31,10 @@ Two extensions behind the same entry points (both off unless asked for):
     inside the training step; `val` / `test` never augment.  `"retrieval": True | (k, ...)` makes `val` / `test`
     also encode each batch's reports and add image<->text retrieval over the whole split (Recall@K, median / mean rank, both
     directions) to the returned dict and the writer as `Retrieval/i2t R@1`, ...; off by default.
+    `"knn": True | {"k": 20, "temperature": 0.07, "bank_batches": 8}` adds a kNN label probe of the image embeddings (DESIGN.md
+    §5.15): `knn_bank(loaders)` re-embeds up to "bank_batches" batches per loader into a bank of embeddings and labels, and from then
+    on `val` / `test` label every evaluation image by the weighted vote of its k nearest bank rows and add `kNN/Accuracy`,
+    `kNN/F1-macro`, `kNN/AUROC-macro`, `kNN/AUROC-weighted`; off by default, and nothing is added before `knn_bank`.
     `"micro_batch": n` runs the encoders on at most n of a rank's rows at a time (gradient cache): the same loss
     and update as the unchunked step up to fp32 summation order, at the peak memory of one chunk.
     `"optim": "adamw"` (overrides the module-level `OPTIM` for the joint trainer only) selects AdamW with decoupled
@@ -81,8 +85,8 @@ from torch.utils.data import ConcatDataset, DataLoader, RandomSampler, Subset, T
 from . import functional as Fh
 from . import kernels as K
 from . import optim as cxr_optim
-from .contrastive import (RETRIEVAL_KS, JointContrastiveTrainer, check_agem_options, check_distill_options, check_ema_options,
-                          check_ks, retrieval_metrics)
+from .contrastive import (KNN_K, KNN_TEMPERATURE, RETRIEVAL_KS, JointContrastiveTrainer, KNNBank, check_agem_options,
+                          check_distill_options, check_ema_options, check_knn_options, check_ks, retrieval_metrics)
 from .DataRetrieval import CHEXPERT_COMPETITION_CLASSES, basic_create_prompts, create_prompts
 from .health_multimodal.text import get_cxr_bert_inference
 from .models import myLinearModel, myMLP
@@ -150,6 +154,8 @@ def change_values(tensor):
 # step's options.  A key is the keyword of the same name, except:
 JOINT_RENAMED = {"contrastive_loss": "loss"}                      # key -> keyword, where the two differ
 JOINT_OWN_KEYS = ("image_model", "retrieval", "ewc_batches")      # read by `Trainer` itself
+JOINT_PROBE_KEYS = ("knn",)                                       # read by `Trainer` itself too, through `knn_options`
+KNN_BANK_BATCHES = 8
 # (master key, member keys, what the group configures, what the adapter schedules lack): a member needs its master, all need joint mode
 JOINT_GROUPS = (("ewc_lambda", ("ewc_gamma", "ewc_fisher", "ewc_batches"), "elastic weight consolidation", "such penalty"),
                 ("distill_weight", ("distill_temperature",), "similarity distillation", "teacher"),
@@ -169,9 +175,13 @@ def joint_options(joint_encoders):
     if joint_encoders is None:
         return {}, dict.fromkeys(JOINT_OWN_KEYS)
     je = dict(joint_encoders) if isinstance(joint_encoders, dict) else {"image_model": joint_encoders[0], "temperature": joint_encoders[1]}
-    unknown = [k for k in je if k not in JOINT_STEP_KEYS and k not in JOINT_OWN_KEYS]
+    unknown = [k for k in je if k not in JOINT_STEP_KEYS and k not in JOINT_OWN_KEYS and k not in JOINT_PROBE_KEYS]
     if unknown:
-        raise ValueError(f"joint_encoders: unknown key(s) {unknown}; the valid keys are {sorted([*JOINT_STEP_KEYS, *JOINT_OWN_KEYS])}")
+        raise ValueError(f"joint_encoders: unknown key(s) {unknown}; the valid keys are "
+                         f"{sorted([*JOINT_STEP_KEYS, *JOINT_OWN_KEYS, *JOINT_PROBE_KEYS])}")
+    if knn_options(je) is not None and je.get("image_model") is None:
+        raise ValueError("joint_encoders: 'knn' probes the image encoder of the joint-encoder step and needs joint mode (an "
+                         "'image_model'); the adapter schedules have no such encoder")
     for master, members, what, lacks in JOINT_GROUPS:
         given = [k for k in (master,) + members if je.get(k) is not None]
         if given and je.get("image_model") is None:
@@ -192,6 +202,26 @@ def joint_options(joint_encoders):
         kw.pop("augment", None)
         kw.pop("augment_seed", None)
     return kw, {k: je[k] if k == "image_model" else je.get(k) for k in JOINT_OWN_KEYS}     # (a dict without a model: KeyError)
+
+
+def knn_options(joint_encoders) -> Optional[dict]:
+    """the "knn" entry of `joint_encoders`: absent / None / False -> off (None); True -> the defaults; a dict with any of "k",
+    "temperature", "bank_batches" -> those over the defaults {"k": 20, "temperature": 0.07, "bank_batches": 8}, validated"""
+    opt = joint_encoders.get("knn") if isinstance(joint_encoders, dict) else None
+    if opt is None or opt is False:
+        return None
+    if opt is True:
+        opt = {}
+    if not isinstance(opt, dict):
+        raise ValueError(f"joint_encoders['knn'] must be True or a dict with 'k', 'temperature', 'bank_batches', got {opt!r}")
+    unknown = [k for k in opt if k not in ("k", "temperature", "bank_batches")]
+    if unknown:
+        raise ValueError(f"joint_encoders['knn']: unknown key(s) {unknown}; the valid keys are ['bank_batches', 'k', 'temperature']")
+    k, temperature = check_knn_options(opt.get("k", KNN_K), opt.get("temperature", KNN_TEMPERATURE))
+    nb = opt.get("bank_batches", KNN_BANK_BATCHES)
+    if isinstance(nb, bool) or not isinstance(nb, int) or nb < 1:
+        raise ValueError(f"joint_encoders['knn']['bank_batches'] must be an integer >= 1, got {nb!r}")
+    return {"k": k, "temperature": temperature, "bank_batches": nb}
 
 
 class Trainer:
@@ -243,6 +273,9 @@ class Trainer:
         self.image_model = None
         self._retrieval_ks = None          # joint_encoders={..., "retrieval": True | (k, ...)}: val / test add Retrieval/* metrics
         self._retrieval_result = None
+        self._knn = None                   # joint_encoders={..., "knn": True | {...}}: after `knn_bank`, val / test add kNN/* metrics
+        self._knn_bank = None
+        self._knn_result = None
         if joint_encoders is not None:
             self.image_model = own["image_model"]
             if OPTIM not in ("adam", "sgd"):
@@ -251,6 +284,7 @@ class Trainer:
             print("*** JOINT ENCODER TRAINING (%s over the global batch): no adapters ***"
                   % ("pairwise sigmoid loss" if self._joint.loss == "sigmoid" else "InfoNCE"))
             self._retrieval_ks = self._parse_retrieval(own["retrieval"])
+            self._knn = knn_options(joint_encoders)
         params = []
         if self._joint is not None:
             self.image_adapter = self.text_adapter = None
@@ -856,6 +890,65 @@ class Trainer:
                     self.writer.add_scalar(f"{val_test}/Retrieval/{direction} {k}", v, epoch)
         return m
 
+    # ------------------------------------------------------------------------------------------------ kNN label probe
+    @torch.no_grad()
+    def knn_bank(self, loaders) -> int:
+        """Fill the memory of the kNN probe (needs `joint_encoders={..., "knn": ...}`): re-embed up to "bank_batches" batches of each
+        loader in `loaders` (one loader or a sequence of them, yielding `(images, input_ids, attention_mask, labels)`) with the image
+        encoder on the weights `_eval_weights` chooses (so "ema_eval" applies), every rank its shard of each batch as `_joint_shard`
+        cuts it, then gather the rows and labels of all ranks (`KNNBank.finish`) -> the bank's rows.  It replaces an earlier bank.
+        From then on `val` / `test` add the kNN/* metrics.  No training state moves.  Every rank calls it."""
+        if self._joint is None or self._knn is None:
+            raise ValueError("Trainer.knn_bank needs joint_encoders={..., 'knn': True | {'k': ..., 'temperature': ..., 'bank_batches': ...}}")
+        def is_batch(b):
+            return isinstance(b, (list, tuple)) and len(b) > 0 and isinstance(b[0], torch.Tensor)
+
+        if not isinstance(loaders, (list, tuple)) or (len(loaders) > 0 and is_batch(loaders[0])):      # one loader (a list of batches is one)
+            loaders = (loaders,)
+        bank = KNNBank()
+        with self._eval_weights():
+            self._set_mode(False)
+            for loader in loaders:
+                for n, batch in enumerate(loader):
+                    if n >= self._knn["bank_batches"]:
+                        break
+                    if len(batch) < 4:
+                        raise ValueError("Trainer.knn_bank needs (images, input_ids, attention_mask, labels) batches, got a batch of "
+                                         f"{len(batch)} tensors")
+                    images = self._joint_shard(batch, "Trainer.knn_bank")[0]
+                    lo, hi = self._shard(batch[0].shape[0]) if self.world > 1 else (0, batch[0].shape[0])
+                    bank.add(self.image_model(images), batch[-1][lo:hi].to(self.device))
+            self._knn_bank = bank.finish(self._joint._dist_group())
+        return len(self._knn_bank)
+
+    def _knn_vote(self, new_embs, labels):
+        """the vote of one evaluation batch on the image embeddings `_eval_batches` already has -> host scores [B, C]"""
+        bank = self._knn_bank
+        if labels.dim() != 2 or labels.shape[1] != bank.width:
+            raise ValueError(f"kNN evaluation: the bank's labels are {bank.width} wide but the evaluation labels "
+                             f"{labels.shape[-1] if labels.dim() else 0} (build the bank from loaders of the same label set)")
+        return bank.predict(new_embs, self._knn["k"], self._knn["temperature"]).cpu().numpy()
+
+    def _add_knn(self, m, y_true, val_test, epoch):
+        """`kNN/Accuracy` ... `kNN/AUROC-weighted` of the last `_eval_loop`, computed as `evaluate_model` computes its own (a
+        prediction is score > 0.5), into the returned dict and the writer"""
+        score, self._knn_result = getattr(self, "_knn_result", None), None
+        if score is None:
+            return m
+        from sklearn.metrics import accuracy_score, f1_score, roc_auc_score
+        pred = (score > 0.5).astype(np.float32)
+        km = {"kNN/Accuracy": accuracy_score(y_true, pred), "kNN/F1-macro": f1_score(y_true, pred, average="macro", zero_division=0)}
+        try:
+            km["kNN/AUROC-macro"] = roc_auc_score(y_true, score, average="macro", multi_class="ovr")
+            km["kNN/AUROC-weighted"] = roc_auc_score(y_true, score, average="weighted", multi_class="ovr")
+        except ValueError:  # a class without both labels in a tiny synthetic split (or a NaN score)
+            pass
+        for k, v in km.items():
+            m[k] = v
+            if self.writer is not None:
+                self.writer.add_scalar(val_test + "/" + k, v, epoch)
+        return m
+
     @contextlib.contextmanager
     def _eval_weights(self):
         """the weights an evaluation reads: with `"ema_eval": True` the parameter average (`JointContrastiveTrainer.averaged()`,
@@ -882,6 +975,7 @@ class Trainer:
         y_true, y_pred, y_score = [], [], []
         batch_idx = 0
         acc = ([], [], []) if self._joint is not None and self._retrieval_ks is not None else None
+        knn = [] if getattr(self, "_knn_bank", None) is not None else None      # (a bank exists only in joint mode with "knn")
         for batch in loader:
             batch_idx += 1
             labels = batch[-1].to(self.device)
@@ -891,6 +985,8 @@ class Trainer:
                 new_embs = self.image_model(batch[0].to(self.device))   # (under no_grad: the whole loop is)
                 if acc is not None:
                     self._retrieval_collect(acc, batch, new_embs)
+                if knn is not None:
+                    knn.append(self._knn_vote(new_embs, labels))
             else:
                 embs = batch[0].to(self.device)
                 new_embs = self.image_adapter(embs) if self._has_img else embs
@@ -907,17 +1003,20 @@ class Trainer:
             y_pred.append(pred.cpu().numpy())
             y_score.append(score.cpu().numpy())
         self._retrieval_result = self._retrieval_finish(acc) if acc is not None else None
+        self._knn_result = np.concatenate(knn) if knn else None
         return np.concatenate(y_true), np.concatenate(y_pred), np.concatenate(y_score)
 
     def val(self, val_loader, criterion, epoch, epochs, mode="joint", tasks_order=None):
         """`Trainer.py:773-866`: scores (pos+1)/2 or (pos-neg+2)/4, predictions argmax([neg,pos]), BCE logged."""
         y_true, y_pred, y_score = self._eval_loop(val_loader, criterion, epoch, "val")
-        return self._add_retrieval(self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "val", epochs, tasks_order), "val", epoch)
+        m = self._add_retrieval(self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "val", epochs, tasks_order), "val", epoch)
+        return self._add_knn(m, y_true, "val", epoch)
 
     def test(self, test_loader, criterion, epoch, epochs, mode="joint", tasks_order=None, plot_tsne_array=None):
         """`Trainer.py:989-1062` (the t-SNE / heat-map plots that follow there are out of scope)."""
         y_true, y_pred, y_score = self._eval_loop(test_loader, None, epoch, None)
-        return self._add_retrieval(self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "test", epochs, tasks_order), "test", epoch)
+        m = self._add_retrieval(self.evaluate_model(y_true, y_pred, y_score, mode, epoch, "test", epochs, tasks_order), "test", epoch)
+        return self._add_knn(m, y_true, "test", epoch)
 
     @torch.no_grad()
     def evaluate_model(self, y_true, y_pred, y_score, mode, epoch, val_test, epochs, tasks_order):

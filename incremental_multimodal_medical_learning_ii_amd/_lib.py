@@ -104,6 +104,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "cxrk_group_mean_fwd": (I, [P, I, I, I, P, P]),
     "cxrk_group_mean_bwd": (I, [P, I, I, I, P, P]),
     "cxrk_retrieval_ranks": (I, [P, L, I, P, L, I, I, I, P, P, P, P, P, P]),
+    "cxrk_topk_neighbours_slab_bytes": (Z, [I, I, I]),
+    "cxrk_topk_neighbours": (I, [P, L, I, P, L, I, I, I, I, P, P, P, Z, P]),
+    "cxrk_knn_vote": (I, [P, P, I, I, P, L, I, I, F, P, P]),
     "cxrk_scale_mask": (I, [P, P, P, F, L, P, P]),
     "cxrk_mlm_mask_tokens": (I, [P, P, I, I, L, c_uint64, c_uint32, c_double, L, L, P, I, I, P, P, P, P, P, P, P]),
     "cxrk_mlm_gather_rows": (I, [P, L, I, P, P, I, P, L, P]),

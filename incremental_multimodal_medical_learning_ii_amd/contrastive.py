@@ -156,6 +156,90 @@ def keys_from_tokens(input_ids: torch.Tensor, attention_mask: torch.Tensor) -> t
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# kNN label probe
+# ----------------------------------------------------------------------------------------------------------------
+KNN_K, KNN_TEMPERATURE = 20, 0.07
+
+
+def check_knn_options(k, temperature) -> Tuple[int, float]:
+    """(k, temperature) of the kNN probe, validated: an int in [1, kernels.TOPK_MAX] and a finite float > 0"""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= K.TOPK_MAX:
+        raise ValueError(f"knn: k must be an int in [1, {K.TOPK_MAX}], got {k!r}")
+    if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not (0.0 < float(temperature) < math.inf):
+        raise ValueError(f"knn: temperature must be a finite number > 0, got {temperature!r}")
+    return k, float(temperature)
+
+
+class KNNBank:
+    """The memory of the kNN probe: [n, D] L2-normalised image embeddings and their [n, C] labels, on the device.
+
+    `add(emb, labels)` appends this rank's rows; `finish(group)` closes the bank -- under data parallelism one all-gather of the
+    rows and one of the labels (rank-major) after one MAX all-reduce over (count, -count) has checked that every rank holds the same
+    number of rows, as `JointContrastiveTrainer.remember` checks its memory; `predict(emb, k, temperature)` -> [B, C], the
+    weighted vote (`kernels.knn_vote`) of the k nearest bank rows of each embedding (`functional.topk_neighbours`): no [B, n]
+    score block, bit-reproducible, the same on every rank for the same queries."""
+
+    def __init__(self):
+        self._emb, self._lab = [], []
+        self.emb: Optional[torch.Tensor] = None
+        self.labels: Optional[torch.Tensor] = None
+
+    def __len__(self) -> int:
+        return self.emb.shape[0] if self.emb is not None else sum(e.shape[0] for e in self._emb)
+
+    @property
+    def width(self) -> Optional[int]:
+        """the label width C (None while the bank is empty)"""
+        if self.labels is not None:
+            return self.labels.shape[1]
+        return self._lab[0].shape[1] if self._lab else None
+
+    @torch.no_grad()
+    def add(self, emb: torch.Tensor, labels: torch.Tensor) -> None:
+        if self.emb is not None:
+            raise ValueError("KNNBank.add: the bank is finished")
+        if emb.dim() != 2 or labels.dim() != 2 or labels.shape[0] != emb.shape[0] or emb.shape[0] == 0:
+            raise ValueError(f"KNNBank.add: expected embeddings [B, D] and labels [B, C], got {tuple(emb.shape)} and {tuple(labels.shape)}")
+        if self._emb and (emb.shape[1] != self._emb[0].shape[1] or labels.shape[1] != self._lab[0].shape[1]):
+            raise ValueError(f"KNNBank.add: rows of width {emb.shape[1]} / labels of width {labels.shape[1]} after rows of width "
+                             f"{self._emb[0].shape[1]} / labels of width {self._lab[0].shape[1]}")
+        self._emb.append(Fh.K.l2norm_fwd(emb.detach().float().contiguous())[0])
+        self._lab.append(labels.detach().to(device=emb.device, dtype=torch.float32).contiguous())
+
+    @torch.no_grad()
+    def finish(self, group=None) -> "KNNBank":
+        if self.emb is not None:
+            raise ValueError("KNNBank.finish: the bank is finished")
+        if not self._emb:
+            raise ValueError("KNNBank.finish: the bank is empty")
+        emb, lab = torch.cat(self._emb).contiguous(), torch.cat(self._lab).contiguous()
+        if group is not None:
+            import torch.distributed as dist
+            n = emb.shape[0]
+            t = torch.tensor([n, -n], dtype=torch.int64, device=_host_collective_device(group))
+            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+            hi, lo = int(t[0]), -int(t[1])
+            if hi != lo:
+                raise RuntimeError(f"KNNBank.finish: the ranks hold between {lo} and {hi} bank rows (this one {n}); every rank must "
+                                   f"add the same number of rows")
+            emb, lab = Fh._all_gather_rows(emb, group), Fh._all_gather_rows(lab, group)
+        self.emb, self.labels = emb, lab
+        self._emb, self._lab = [], []
+        return self
+
+    @torch.no_grad()
+    def predict(self, emb: torch.Tensor, k: int = KNN_K, temperature: float = KNN_TEMPERATURE) -> torch.Tensor:
+        if self.emb is None:
+            raise ValueError("KNNBank.predict: call finish() first")
+        k, temperature = check_knn_options(k, temperature)
+        if emb.dim() != 2 or emb.shape[1] != self.emb.shape[1]:
+            raise ValueError(f"KNNBank.predict: expected embeddings [B, {self.emb.shape[1]}], got {tuple(emb.shape)}")
+        q = Fh.K.l2norm_fwd(emb.detach().float().contiguous())[0]
+        score, index = Fh.topk_neighbours(q, self.emb, k, normalize=False)
+        return Fh.K.knn_vote(score, index, self.labels, temperature)
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # retrieval evaluation (DESIGN.md §5.5)
 # ----------------------------------------------------------------------------------------------------------------
 RETRIEVAL_KS = (1, 5, 10)
@@ -1259,3 +1343,50 @@ class JointContrastiveTrainer:
         img, txt = torch.cat(imgs).contiguous(), torch.cat(txts).contiguous()
         metrics = retrieval_metrics(img, txt, torch.cat(keys).contiguous() if keys else None, ks, self._dist_group())
         return (metrics, img, txt) if return_embeddings else metrics
+
+    @torch.no_grad()
+    def embed_images(self, batches, max_batches: Optional[int] = None):
+        """(image embeddings [n, D], labels [n, C]) of `(images, ..., labels)` batches -- the labels are each batch's LAST tensor --
+        with the image encoder in eval mode under no_grad (no augmentation, no dropout; the modules' previous modes are restored).
+        At most `max_batches` batches are read.  Nothing of the training state moves."""
+        dev = next(self.image_model.parameters()).device
+        modes = [(m, m.training) for m in self.image_model.modules()]
+        embs, labs = [], []
+        try:
+            self.image_model.eval()
+            for n, batch in enumerate(batches):
+                if max_batches is not None and n >= max_batches:
+                    break
+                if len(batch) < 2 or batch[-1].dim() != 2:
+                    raise ValueError("kNN evaluation expects (images, ..., labels) batches with [B, C] labels last, got "
+                                     f"{len(batch)} tensors")
+                embs.append(self.image_model(batch[0].to(dev)))
+                labs.append(batch[-1].to(device=dev, dtype=torch.float32))
+        finally:
+            for m, flag in modes:
+                m.training = flag
+        if not embs:
+            raise ValueError("kNN evaluation: no batches")
+        return torch.cat(embs).contiguous(), torch.cat(labs).contiguous()
+
+    @torch.no_grad()
+    def build_knn_bank(self, batches, max_batches: Optional[int] = None) -> KNNBank:
+        """a finished `KNNBank` of the image embeddings of `batches` (this rank's shards; gathered over the trainer's group)"""
+        bank = KNNBank()
+        bank.add(*self.embed_images(batches, max_batches))
+        return bank.finish(self._dist_group())
+
+    @torch.no_grad()
+    def evaluate_knn(self, bank_batches, eval_batches, k: int = KNN_K, temperature: float = KNN_TEMPERATURE,
+                     max_bank_batches: Optional[int] = None) -> dict:
+        """kNN label probe of the frozen image encoder: embed up to `max_bank_batches` of `bank_batches` into a
+        `KNNBank`, then score every row of `eval_batches` by the weighted vote of its k nearest bank rows.  Both are
+        `(images, ..., labels)` batches, under data parallelism THIS rank's rows.  Returns {"scores": [N, C], "labels": [N, C]} on
+        the device for this rank's evaluation rows.  No text tower, no prompts, no trained head; the step counter, the dropout /
+        augment / MLM counters, the optimiser and the parameter average are left as they are."""
+        k, temperature = check_knn_options(k, temperature)
+        bank = self.build_knn_bank(bank_batches, max_bank_batches)
+        emb, labels = self.embed_images(eval_batches)
+        if labels.shape[1] != bank.width:
+            raise ValueError(f"evaluate_knn: the bank's labels are {bank.width} wide but the evaluation labels {labels.shape[1]}")
+        return {"scores": bank.predict(emb, k, temperature), "labels": labels}

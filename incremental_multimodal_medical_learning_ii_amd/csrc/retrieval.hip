@@ -1,35 +1,22 @@
 // Streaming retrieval ranks: for every query row the best positive score and the number of non-positive gallery rows that beat / tie
 // it, over the WHOLE gallery, without ever writing the [N][M] similarity block (include/cxrk.h, "retrieval_ranks").
 //
-// One tile code for everything: a 256-thread block forms 128 x 128 tiles of s(i,j) = sum_k Q[i][k] G[j][k] with the exact-fp32 MFMA
-// (v_mfma_f32_32x32x2_f32: bit for bit a k-ascending fmaf chain, so s(i,j) depends on row i of Q and row j of G only, never on the
-// tile, the block or the pass that formed it), K in chunks of 32 through one LDS buffer with the next chunk prefetched into registers.
-// The gallery rows are the A operand and the query rows the B operand: a lane then owns ONE query row per 32-column accumulator
-// (the C/D column = lane & 31) and its 16 registers are 16 gallery rows, so the per-row state is two registers per lane, not 32.
+// One tile code for everything (retrieval_tile.h, shared with topk.hip): 128 x 128 tiles of the exact-fp32 MFMA, so s(i,j) depends on
+// row i of Q and row j of G only.  A lane owns ONE query row per 32-column accumulator and its 16 registers are 16 gallery rows, so
+// the per-row state is two registers per lane, not 32.
 //   pass 0: the maximum of s over the positives, into `pos` as an order-preserving integer (atomicMax; NaN = INT_MAX wins);
 //   pass 1: per row, counts of non-positive columns with s > pos / s == pos, kept in registers over the block's column range and
 //           added with integer atomics; a NaN score in a non-positive column sets the sign bit of ties[i];
 //   finish: decode pos to fp32; rows with a NaN pos or the sign bit get greater = ties = -1.
 #include "cxrk.h"
 #include "cxrk_common.h"
+#include "retrieval_tile.h"
 
 using namespace cxrk;
 
 namespace {
 
-constexpr int RT = 128;        // tile edge (query rows per strip, gallery rows per tile)
-constexpr int RK = 32;         // K chunk
-constexpr int RLD = RT + 1;    // LDS row pitch of the [k][row] images
-constexpr int ENC_NEG_INF = (int)0x807fffffu;   // enc(-inf)
-constexpr int ENC_NAN = 0x7fffffff;
-
-// fp32 -> int32 with the same order (signed compare); every NaN maps to INT_MAX, which decodes to a NaN.
-__device__ __forceinline__ int enc(float s) {
-  if (s != s) return ENC_NAN;
-  const int b = __builtin_bit_cast(int, s);
-  return b >= 0 ? b : b ^ 0x7fffffff;
-}
-__device__ __forceinline__ float dec(int e) { return __builtin_bit_cast(float, e >= 0 ? e : e ^ 0x7fffffff); }
+using namespace cxrk::rtile;
 
 __global__ void retrieval_init_kernel(int* __restrict__ pos_enc, int* __restrict__ greater, int* __restrict__ ties, int N) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -53,8 +40,8 @@ __global__ __launch_bounds__(256) void retrieval_kernel(const float* __restrict_
                                                         const long long* __restrict__ keys_q, const long long* __restrict__ keys_g,
                                                         int* __restrict__ pos_enc, int* __restrict__ greater, int* __restrict__ ties,
                                                         int tiles_per_block) {
-  __shared__ float sQ[RK * RLD];
-  __shared__ float sG[RK * RLD];
+  __shared__ float sQ[STAGE_FLOATS];
+  __shared__ float sG[STAGE_FLOATS];
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1;   // gallery half / query half of the tile this wave owns (64 x 64)
@@ -64,8 +51,6 @@ __global__ __launch_bounds__(256) void retrieval_kernel(const float* __restrict_
   if (PASS == 0 && !KEYED) { jbeg = i0 + diag_off; jend = jbeg + RT < (long)M ? jbeg + RT : (long)M; }
   else { jbeg = (long)blockIdx.y * tiles_per_block * RT; jend = jbeg + (long)tiles_per_block * RT; if (jend > M) jend = M; }
   if (jbeg >= jend) return;   // block-uniform
-  const int ntiles = (int)((jend - jbeg + RT - 1) / RT);
-  const int nch = (D + RK - 1) / RK;
 
   // per-lane state of its two query rows
   long qi[2]; bool qv[2]; long long kq[2]; float p[2]; int best[2], gt[2], eq[2]; bool sawnan[2];
@@ -77,55 +62,7 @@ __global__ __launch_bounds__(256) void retrieval_kernel(const float* __restrict_
     best[n] = ENC_NEG_INF; gt[n] = 0; eq[n] = 0; sawnan[n] = false;
   }
 
-  // staging map: thread -> (k = tid & 31, rows (tid >> 5) + 8 u): a wave reads two 128-byte row pieces per load
-  const int kcol = tid & 31, rbase = tid >> 5;
-  float rq[16], rg[16];
-  const int nq = (int)((long)N - i0 < RT ? (long)N - i0 : RT) - rbase;   // this thread's rows rbase + 8 u are valid while 8 u < nq
-  const float* qbase = Q + (i0 + rbase) * ldq + kcol;
-  const long qstep = 8 * ldq, gstep = 8 * ldg;
-  auto fetch = [&](int tile, int ch) {
-    const long j0 = jbeg + (long)tile * RT;
-    const int ng = (int)(jend - j0 < RT ? jend - j0 : RT) - rbase;
-    const bool kv = ch * RK + kcol < D;
-    const float* qp = qbase + ch * RK;
-    const float* gp = G + (j0 + rbase) * ldg + ch * RK + kcol;
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {   // rows >= N, columns >= jend and k >= D are never read
-      rq[u] = (kv && 8 * u < nq) ? qp[u * qstep] : 0.f;
-      rg[u] = (kv && 8 * u < ng) ? gp[u * gstep] : 0.f;
-    }
-  };
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int m = 0; m < 2; ++m)
-#pragma unroll
-    for (int n = 0; n < 2; ++n)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[m][n][r] = 0.f;
-
-  const float* Ap = sG + 64 * wm + l31 + h * RLD;   // A[row = gallery][k = 2 kk + h]
-  const float* Bp = sQ + 64 * wn + l31 + h * RLD;   // B[k = 2 kk + h][col = query]
-
-  fetch(0, 0);
-  for (int tile = 0; tile < ntiles; ++tile) {
-    for (int ch = 0; ch < nch; ++ch) {
-      __syncthreads();   // the previous chunk's reads are done
-#pragma unroll
-      for (int u = 0; u < 16; ++u) { sQ[kcol * RLD + rbase + 8 * u] = rq[u]; sG[kcol * RLD + rbase + 8 * u] = rg[u]; }
-      __syncthreads();
-      if (ch + 1 < nch) fetch(tile, ch + 1);
-      else if (tile + 1 < ntiles) fetch(tile + 1, 0);
-#pragma unroll
-      for (int kk = 0; kk < RK / 2; ++kk) {   // k ascending: chunk, then kk, then the instruction's own k = 0, 1
-        const float a0 = Ap[2 * kk * RLD], a1 = Ap[2 * kk * RLD + 32];
-        const float b0 = Bp[2 * kk * RLD], b1 = Bp[2 * kk * RLD + 32];
-        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-      }
-    }
+  score_tiles(Q, ldq, N, G, ldg, D, i0, jbeg, jend, sQ, sG, [&](int tile, f32x16 (&acc)[2][2]) {
     // epilogue of this tile: C/D register r of accumulator (m, n) is gallery row 64 wm + 32 m + (r & 3) + 8 (r >> 2) + 4 h, query = lane
     // Columns are counted from this lane's first one, j0, so that the masks are 32-bit compares against per-tile values.
     const long j0 = jbeg + (long)tile * RT + 64 * wm + 4 * h;
@@ -152,7 +89,7 @@ __global__ __launch_bounds__(256) void retrieval_kernel(const float* __restrict_
         }
       }
     }
-  }
+  });
 
   // the two lane halves (and the two gallery-half waves, through the atomics) share a query row
 #pragma unroll
@@ -192,13 +129,9 @@ extern "C" int cxrk_retrieval_ranks(const float* Q, long ldq, int N, const float
   const bool keyed = keys_q != nullptr;
   if (!keyed) CXRK_CHECK_ARG(diag_off >= 0 && (long)diag_off + N <= (long)M);
 
-  const int strips = ceil_div(N, RT), tiles = ceil_div(M, RT);
-  // split the gallery over blockIdx.y so that a short query set still gives every CU (256) two blocks
-  int split = ceil_div(512, strips);
-  if (split > tiles) split = tiles;
-  const int tiles_per_block = ceil_div(tiles, split);
-  split = ceil_div(tiles, tiles_per_block);
-  const dim3 grid(strips, split);
+  const Split sp = gallery_split(N, M);
+  const int strips = sp.strips, tiles_per_block = sp.tiles_per_block;
+  const dim3 grid(strips, sp.split);
 
   hipLaunchKernelGGL(retrieval_init_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, stream, reinterpret_cast<int*>(pos), greater, ties, N);
   if (keyed) {

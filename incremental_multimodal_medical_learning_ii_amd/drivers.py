@@ -145,7 +145,8 @@ def joint_encoders_from_args(args, image_model, kind=None, train_loader=None) ->
             **mlm_from_args(args),
             **ema_from_args(args),
             "augment": augment_from_args(args),
-            "retrieval": retrieval_from_args(args)}
+            "retrieval": retrieval_from_args(args),
+            **knn_from_args(args)}
 
 
 def mlm_from_args(args) -> dict:
@@ -176,6 +177,26 @@ def retrieval_from_args(args):
     if ks is None:
         return None
     return True if len(ks) == 0 else tuple(ks)
+
+
+def knn_from_args(args) -> dict:
+    """`--knn [K] [--knn-temperature T] [--knn-bank-batches N]` -> the `joint_encoders` key of the kNN label probe (DESIGN.md 5.15);
+    without `--knn` an empty dict: the key exists only when its flag is given"""
+    k = getattr(args, "knn", None)
+    if k is None:
+        return {}
+    opt = {} if k is True else {"k": k}
+    if getattr(args, "knn_temperature", None) is not None:
+        opt["temperature"] = args.knn_temperature
+    if getattr(args, "knn_bank_batches", None) is not None:
+        opt["bank_batches"] = args.knn_bank_batches
+    return {"knn": opt or True}
+
+
+def knn_bank(trainer, args, loaders) -> None:
+    """`--knn`: refill the probe's memory from `loaders` just before a `val` / `test` pair; nothing without the flag"""
+    if getattr(args, "knn", None) is not None:
+        trainer.knn_bank(loaders)
 
 
 def run_steps(args, kind, train_loader) -> int:
@@ -253,9 +274,11 @@ def zero_joint_bounds(args):
         if args.epochs > 0:
             for epoch in range(1, args.epochs + 1):
                 trainer.train(train_loader, criterion, epoch, args.cl, args.threshold, actual_task=epoch)
+                knn_bank(trainer, args, train_loader)
                 trainer.val(val_loader, criterion, epoch, args.epochs, mode="joint", tasks_order=None)
                 metrics = trainer.test(test_loader, criterion, epoch, args.epochs, mode="joint", tasks_order=None)
         else:
+            knn_bank(trainer, args, train_loader)
             trainer.val(val_loader, criterion, 0, 0, mode="zero", tasks_order=None)
             metrics = trainer.test(test_loader, criterion, 0, 0, mode="zero", tasks_order=None)
     finally:
@@ -288,6 +311,7 @@ def class_incremental(args):
                     trainer.profIncremental(epoch, args.epochs, actual_task, threshold)
             if actual_task < len(tasks_order):      # --cl ewc | lwf | agem: what the finished task leaves for the next one
                 trainer.end_task(train_loader[actual_task - 1])
+            knn_bank(trainer, args, list(train_loader[:actual_task]))      # the tasks seen so far
             trainer.val(val_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
             metrics = trainer.test(test_loader, criterion, actual_task, args.epochs, mode=args.mode, tasks_order=tasks_order)
     finally:
@@ -315,6 +339,7 @@ def data_incremental(args):
                     trainer.profIncremental(epoch, args.epochs, part, threshold)
             if part < args.parts:
                 trainer.end_task(train_loader[part - 1])
+            knn_bank(trainer, args, train_loader[part - 1])
             train_loader[part - 1] = None
             trainer.val(val_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
             metrics = trainer.test(test_loader, criterion, part, args.parts, mode="data-inc", tasks_order=part)
@@ -376,6 +401,12 @@ def make_parser():
     ap.add_argument("--retrieval", type=int, nargs="*", default=None, metavar="K",
                     help="--joint: val / test also report image<->text retrieval over the whole split (Recall@K, median / mean rank, "
                          "both directions, DESIGN.md 5.5); without values K = 1 5 10")
+    ap.add_argument("--knn", type=int, nargs="?", const=True, default=None, metavar="K",
+                    help="--joint: val / test also report a kNN label probe of the image embeddings against a bank re-embedded from "
+                         "the training loaders (kNN/Accuracy, F1-macro, AUROC; DESIGN.md 5.15); without a value K = 20")
+    ap.add_argument("--knn-temperature", type=float, default=None, metavar="T", help="--knn: the temperature of the vote's weights (default 0.07)")
+    ap.add_argument("--knn-bank-batches", type=int, default=None, metavar="N",
+                    help="--knn: batches of each training loader that go into the bank (default 8)")
     ap.add_argument("--micro-batch", type=int, default=None, metavar="N",
                     help="--joint: run the encoders on at most N of a rank's rows at a time (gradient cache, DESIGN.md 5.7): the loss "
                          "and update of the whole batch at the peak memory of one chunk; default: the whole batch at once")
@@ -530,6 +561,11 @@ def main(argv=None):
     if args.retrieval is not None and not args.joint:
         raise SystemExit("--retrieval ranks the reports of the evaluation batches against their images and needs --joint (the adapter "
                          "schedules evaluate on pre-computed image embeddings without reports)")
+    if (args.knn is not None or args.knn_temperature is not None or args.knn_bank_batches is not None) and not args.joint:
+        raise SystemExit("--knn probes the image encoder of the north-star step and needs --joint (the adapter schedules evaluate on "
+                         "pre-computed image embeddings)")
+    if args.knn is None and (args.knn_temperature is not None or args.knn_bank_batches is not None):
+        raise SystemExit("--knn-temperature and --knn-bank-batches configure the kNN probe and need --knn")
     if args.micro_batch is not None and not args.joint:
         raise SystemExit("--micro-batch chunks the encoder calls of the north-star step and needs --joint (the adapter schedules "
                          "train on pre-computed embeddings)")

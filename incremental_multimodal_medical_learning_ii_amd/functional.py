@@ -760,6 +760,33 @@ def retrieval_ranks(queries: torch.Tensor, gallery: torch.Tensor, keys: Optional
 
 
 @torch.no_grad()
+def topk_neighbours(queries: torch.Tensor, gallery: torch.Tensor, k: int, normalize: bool = True, exclude_self: bool = False,
+                    group=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The `k` nearest gallery rows of this rank's `queries` [B,D] (include/cxrk.h, "topk_neighbours"): returns
+    (score fp32 [B,k], index int32 [B,k]), each row sorted by score descending (a NaN first), then index ascending, padded with
+    index -1 / score -inf when the gallery has fewer than k candidates.  The [B, M] score block is never formed.
+
+    `gallery` [Bg,D] holds this rank's rows.  With a process `group` the gallery rows of all ranks are gathered, rank-major, and the
+    indices refer to the gathered gallery: one [Bg,D] all-gather and nothing else.  `exclude_self` drops gallery row
+    `rank * B + i` from query i's candidates (leave-one-out of a set queried against itself); it needs `queries` and `gallery`
+    paired row by row as in `retrieval_ranks`.  `normalize`: L2-normalise both sides first (cosine scores).  No autograd."""
+    q, g = queries.detach().contiguous(), gallery.detach().contiguous()
+    if q.dim() != 2 or g.dim() != 2 or q.shape[1] != g.shape[1]:
+        raise ValueError(f"topk_neighbours: queries are {tuple(q.shape)} but the gallery rows {tuple(g.shape)}")
+    if exclude_self and tuple(g.shape) != tuple(q.shape):
+        raise ValueError(f"topk_neighbours: exclude_self needs queries and gallery paired row by row, got {tuple(q.shape)} and "
+                         f"{tuple(g.shape)}")
+    if normalize:
+        q, g = K.l2norm_fwd(q)[0], K.l2norm_fwd(g)[0]
+    off = 0
+    if group is not None:
+        import torch.distributed as dist
+        off = dist.get_rank(group) * q.shape[0]
+        g = _all_gather_rows(g, group)
+    return K.topk_neighbours(q, g, k, exclude_off=off if exclude_self else -1)
+
+
+@torch.no_grad()
 def augment_images(images: torch.Tensor, spec, seed: int, counter: int, row_offset: int = 0, cpad: int = 4) -> torch.Tensor:
     """Random affine + brightness / contrast augmentation on the device (include/cxrk.h, "augment"):
     images [N, 3 | 1, H, W] -> fp32 NHWC [N, Ho, Wo, cpad] (three channels, the padding zero), the tensor the ResNet stem reads.

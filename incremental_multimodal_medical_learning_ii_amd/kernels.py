@@ -1179,6 +1179,70 @@ def retrieval_ranks(Q, G, diag_off: int = 0, keys_q=None, keys_g=None):
     return pos, greater, ties
 
 
+TOPK_MAX = 64
+
+
+def _rows_ld(t, what):
+    """row pitch of a [n, w] tensor with contiguous columns and rows at least w apart"""
+    n, w = t.shape
+    if (w > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < w):
+        raise ValueError(f"{what}: columns must be contiguous and rows at least {w} apart, got strides {t.stride()}")
+    return t.stride(0) if n > 1 else max(w, t.stride(0))
+
+
+def topk_neighbours(Q, G, k: int, exclude_off: int = -1):
+    """(score fp32 [N,k], index int32 [N,k]): for every row of Q [N,D] the k best rows of G [M,D] by dot product, without the [N,M]
+    score block (include/cxrk.h, "topk_neighbours").  Rows are sorted by score descending (NaN first), then index ascending; with
+    fewer than k candidates the tail is index -1 / score -inf.  exclude_off >= 0: column i + exclude_off is no candidate of row i.
+    Exact fp32 whatever the precision mode, bit-reproducible.  Rows may be strided (stride(0) >= D)."""
+    lib = _lib.load()
+    _chk(Q, "topk.Q"), _chk(G, "topk.G")
+    if Q.dim() != 2 or G.dim() != 2 or Q.shape[1] != G.shape[1] or 0 in Q.shape or 0 in G.shape:
+        raise ValueError(f"topk_neighbours: expected non-empty Q [N,D] and G [M,D], got {tuple(Q.shape)} and {tuple(G.shape)}")
+    if G.device != Q.device:
+        raise ValueError(f"topk_neighbours: Q is on {Q.device} but G on {G.device}")
+    N, D = Q.shape
+    M = G.shape[0]
+    k, exclude_off = int(k), int(exclude_off)
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"topk_neighbours: k must be in [1, {TOPK_MAX}], got {k}")
+    if exclude_off < -1 or (exclude_off >= 0 and exclude_off + N > M):
+        raise ValueError(f"topk_neighbours: exclude_off {exclude_off} with {N} queries does not fit a gallery of {M} rows")
+    ldq, ldg = _rows_ld(Q, "topk.Q"), _rows_ld(G, "topk.G")
+    score = torch.empty(N, k, dtype=torch.float32, device=Q.device)
+    index = torch.empty(N, k, dtype=torch.int32, device=Q.device)
+    ws = workspace(lib.cxrk_topk_neighbours_slab_bytes(N, M, k), Q.device)
+    check(lib.cxrk_topk_neighbours(_p(Q), ldq, N, _p(G), ldg, M, D, k, exclude_off, _p(score), _p(index), _p(ws), ws.numel() * 4,
+                                   _stream()), "cxrk_topk_neighbours")
+    return score, index
+
+
+def knn_vote(score, index, labels, temperature: float):
+    """out [N,C] = the softmax((score - score[:, :1]) / temperature)-weighted mean of labels[index] over the k neighbours of each row
+    (include/cxrk.h, "knn_vote").  index -1 slots weigh nothing; a row with a NaN score or no neighbour gives NaN."""
+    lib = _lib.load()
+    _chk(score, "knn_vote.score"), _chk(index, "knn_vote.index", torch.int32), _chk(labels, "knn_vote.labels")
+    if score.dim() != 2 or tuple(index.shape) != tuple(score.shape) or not score.is_contiguous() or not index.is_contiguous() \
+            or 0 in score.shape:
+        raise ValueError(f"knn_vote: score and index must be contiguous non-empty [N,k] tensors, got {tuple(score.shape)} and "
+                         f"{tuple(index.shape)}")
+    if labels.dim() != 2 or 0 in labels.shape:
+        raise ValueError(f"knn_vote: labels must be a non-empty [M,C] tensor, got {tuple(labels.shape)}")
+    if index.device != score.device or labels.device != score.device:
+        raise ValueError(f"knn_vote: score is on {score.device}, index on {index.device}, labels on {labels.device}")
+    N, k = score.shape
+    M, C = labels.shape
+    if k > TOPK_MAX:
+        raise ValueError(f"knn_vote: k must be in [1, {TOPK_MAX}], got {k}")
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature != float("inf")):
+        raise ValueError(f"knn_vote: temperature must be finite and > 0, got {temperature!r}")
+    ldl = _rows_ld(labels, "knn_vote.labels")
+    out = torch.empty(N, C, dtype=torch.float32, device=score.device)
+    check(lib.cxrk_knn_vote(_p(score), _p(index), N, k, _p(labels), ldl, M, C, 1.0 / temperature, _p(out), _stream()), "cxrk_knn_vote")
+    return out
+
+
 def _log_scale(t):
     _chk(t, "log_scale")
     if t.numel() != 1 or t.dim() > 1:
