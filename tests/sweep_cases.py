@@ -6,7 +6,9 @@
                            planes_add_rows), "F" (image-side non-GEMM kernels: max-pool, layout, spatial mean, BatchNorm folding, the
                            train-mode BatchNorm chain), "G" (masked-language-modelling kernels: token masking, gather / scatter of
                            the selected rows, one chunked vocabulary sweep of the cross-entropy kernels, the whole head at
-                           H = 768); a pure function of (SEED, family, index)
+                           H = 768), "H32" / "HPL" (the convolutions on fp32 / planes operands, one of forward, data gradient and
+                           weight gradient per case: generators, references and bounds in tests/sweep_conv_cases.py, registered
+                           here); a pure function of (SEED, family, index)
   legal(case)              the rules the entry points check (include/cxrk.h), restated; every generated case satisfies them
   build(case)              CPU inputs (float32; masks int64, decision bits uint8, winners int32)
   evaluate(case, inp, dt)  the operation's defining formula in torch on the CPU in dtype `dt`
@@ -49,7 +51,7 @@ from typing import Dict, List, Tuple
 import torch
 
 SEED = 20261020
-NCASES = {"A": 105, "B32": 96, "BPL": 96, "C": 104, "D": 112, "E": 111, "F": 102, "G": 108}
+NCASES = {"A": 105, "B32": 96, "BPL": 96, "C": 104, "D": 112, "E": 111, "F": 102, "G": 108, "H32": 120, "HPL": 120}
 FLOOR_REL = 1e-3     # a row / column below 1e-3 of its tensor's scale is judged as if it were at 1e-3 (today's metric judges it at 1)
 U24 = 2.0 ** -24
 ERF_TOL = 2.0 ** -16      # test_gelu_epilogue_writers (exact_ref.assert_two_roundings): what the library promises around erf
@@ -1707,7 +1709,11 @@ def _check_g(case: MlmCase, ref, got, split, planes_out):
 
 
 # ================================================================================================================ one interface
-_GENS = {"A": _gen_a, "B32": _gen_b, "BPL": _gen_b, "C": _gen_c, "D": _gen_d, "E": _gen_e, "F": _gen_f, "G": _gen_g}
+import sweep_conv_cases as _H  # noqa: E402  (family H lives there; it uses the sampling and the comparators above)
+
+ConvCase = _H.ConvCase
+_GENS = {"A": _gen_a, "B32": _gen_b, "BPL": _gen_b, "C": _gen_c, "D": _gen_d, "E": _gen_e, "F": _gen_f, "G": _gen_g,
+         "H32": lambda i, sched: _H.gen(i, sched), "HPL": lambda i, sched: _H.gen(i, sched)}
 _CACHE: Dict[str, list] = {}
 
 
@@ -1725,17 +1731,18 @@ def family_of(case) -> str:
 def legal(case) -> bool:
     if isinstance(case, AttnCase):      # bert.hip:942,989: 4 <= dH <= 64, dH % 4 == 0, 1 <= L <= 512; bert.hip:973,1020: B, nH > 0
         return 4 <= case.dH <= 64 and case.dH % 4 == 0 and 1 <= case.L <= 512 and case.B > 0 and case.nH > 0
-    return {GemmCase: _legal_b, ColCase: _legal_c, HeadCase: _legal_d, RowCase: _legal_e, ImgCase: _legal_f, MlmCase: _legal_g}[type(case)](case)
+    return {GemmCase: _legal_b, ColCase: _legal_c, HeadCase: _legal_d, RowCase: _legal_e, ImgCase: _legal_f, MlmCase: _legal_g,
+            ConvCase: _H.legal}[type(case)](case)
 
 
 def build(case) -> Dict[str, torch.Tensor]:
     return {AttnCase: _build_a, GemmCase: _build_b, ColCase: _build_c, HeadCase: _build_d, RowCase: _build_e, ImgCase: _build_f,
-            MlmCase: _build_g}[type(case)](case)
+            MlmCase: _build_g, ConvCase: _H.build}[type(case)](case)
 
 
 def evaluate(case, inp, dt) -> Dict[str, torch.Tensor]:
     return {AttnCase: _eval_a, GemmCase: _eval_b, ColCase: _eval_c, HeadCase: _eval_d, RowCase: _eval_e, ImgCase: _eval_f,
-            MlmCase: _eval_g}[type(case)](case, inp, dt)
+            MlmCase: _eval_g, ConvCase: _H.evaluate}[type(case)](case, inp, dt)
 
 
 def reference(case, inp) -> Dict[str, torch.Tensor]:
@@ -1764,7 +1771,10 @@ def group(case, name: str) -> Tuple[str, str]:
 
 def floor_of(case, name: str, split: bool = False, planes_out: bool = False) -> float:
     """the project's existing bounds: 2e-5 forward, 5e-5 backward, 1e-6 for a column mean (test_train_mode_batchnorm_kernels), and
-    3e-4 for planes tensors / split-bf16 mode"""
+    3e-4 for planes tensors / split-bf16 mode; the convolutions' dgamma: 2e-3, and 2e-2 on planes operands / in split-bf16 mode
+    (tests/test_kernels_gpu.py, tests/test_conv_geometry_gpu.py)"""
+    if isinstance(case, ConvCase):
+        return _H.floor(case, name, split)
     col_mean = name == "mean" and (isinstance(case, ColCase) or getattr(case, "op", "") == "bn_train")
     f = 1e-6 if col_mean else 5e-5 if name in BACKWARD else 2e-5
     if isinstance(case, MlmCase):      # the cross-entropy kernels: this head's own floor; the head: a gradient is every output but the loss
@@ -2085,6 +2095,36 @@ E32: Dict[Tuple[str, str], float] = {
     ('G.xent.rowloss', 'pm80'): 5.9e-06,
     ('G.xent.rowloss', 'randn3'): 3.2e-07,
     ('G.xent.rowloss', 'ties'): 2.9e-06,
+    ('H32.dgrad.dx', 'chan_scaled'): 1.1e-07,
+    ('H32.dgrad.dx', 'randn'): 9.9e-08,
+    ('H32.dgrad.dx', 'relu_like'): 1.2e-07,
+    ('H32.dgrad.sums', 'chan_scaled'): 2e-06,
+    ('H32.dgrad.sums', 'randn'): 2.3e-05,
+    ('H32.dgrad.sums', 'relu_like'): 6.8e-05,
+    ('H32.fwd.y', 'chan_scaled'): 1.4e-07,
+    ('H32.fwd.y', 'randn'): 1.7e-07,
+    ('H32.fwd.y', 'relu_like'): 3.8e-07,
+    ('H32.wgrad.dgamma', 'chan_scaled'): 1.4e-05,
+    ('H32.wgrad.dgamma', 'randn'): 6.1e-06,
+    ('H32.wgrad.dgamma', 'relu_like'): 3.4e-05,
+    ('H32.wgrad.dw', 'chan_scaled'): 1.4e-07,
+    ('H32.wgrad.dw', 'randn'): 1.5e-07,
+    ('H32.wgrad.dw', 'relu_like'): 1.3e-07,
+    ('HPL.dgrad.dx', 'chan_scaled'): 1.3e-07,
+    ('HPL.dgrad.dx', 'randn'): 1.3e-07,
+    ('HPL.dgrad.dx', 'relu_like'): 1.1e-07,
+    ('HPL.dgrad.sums', 'chan_scaled'): 6.1e-06,
+    ('HPL.dgrad.sums', 'randn'): 2.8e-05,
+    ('HPL.dgrad.sums', 'relu_like'): 6e-05,
+    ('HPL.fwd.y', 'chan_scaled'): 1.5e-07,
+    ('HPL.fwd.y', 'randn'): 3.3e-07,
+    ('HPL.fwd.y', 'relu_like'): 1.5e-06,
+    ('HPL.wgrad.dgamma', 'chan_scaled'): 1.4e-05,
+    ('HPL.wgrad.dgamma', 'randn'): 4.7e-06,
+    ('HPL.wgrad.dgamma', 'relu_like'): 3.4e-05,
+    ('HPL.wgrad.dw', 'chan_scaled'): 1.6e-07,
+    ('HPL.wgrad.dw', 'randn'): 1.5e-07,
+    ('HPL.wgrad.dw', 'relu_like'): 1.3e-07,
 }
 
 
@@ -2118,6 +2158,8 @@ def check(case, ref, got, split: bool = False, planes_out=()) -> List[Tuple[str,
         return _check_ef(case, ref, got, split, planes_out)
     if isinstance(case, MlmCase):
         return _check_g(case, ref, got, split, planes_out)
+    if isinstance(case, ConvCase):
+        return _H.check(case, ref, got, split)
     cmp = comparator(case)
     res = []
     for name, g in got.items():
@@ -2135,12 +2177,16 @@ def uses_e32(case, name: str) -> bool:
     """outputs judged against max(floor, 8 e32): all of A, C, D; the "row" and "col" outputs of E, F and G, and G's gradient"""
     if name.startswith(("mag:", "aux:")):
         return False
+    if isinstance(case, ConvCase):      # H: the outputs with a precision level (dbeta is exact)
+        return name in _H.E32_OUTPUTS
     return not isinstance(case, (RowCase, ImgCase, MlmCase)) or kind_of(case, name) in ("row", "col", "grad")
 
 
 def compare(case, name: str, got, ref, refs=None) -> Tuple[float, tuple]:
     """the comparator's own figure (not yet divided by a bound) of one e32 output; refs: all outputs of the reference (G's gradient is
     measured in units of 2^-24 of its magnitudes)"""
+    if isinstance(case, ConvCase):
+        return _H.level(case, name, got, ref)
     if isinstance(case, MlmCase) and kind_of(case, name) == "grad":
         return forward_bound(got, ref, refs["mag:grad"], U24, grad_extra(refs, False))
     if isinstance(case, (RowCase, ImgCase, MlmCase)):

@@ -41,6 +41,12 @@ CHANNEL_EDGES = [
     (2, 7, 9, 5, 8, 32, 3, 3, 1, 1),
 ]
 
+# the (R, S, stride, pad) rows of the seeded sweep's convolution family (tests/sweep_conv_cases.py GEOMS_LANE) that no table above
+# holds, on the 7 x 9 image (9 x 11 where the 7 x 7 and 9 x 1 filters want room): the loop check below covers their references too
+SWEEP_GEOMETRIES = [(2, 7, 9, 32, 32, 1, 1, 1, 0), (2, 7, 9, 32, 32, 1, 1, 2, 0), (2, 7, 9, 32, 32, 3, 3, 1, 1), (2, 7, 9, 32, 32, 3, 3, 2, 1),
+                    (2, 7, 9, 32, 32, 3, 1, 2, 1), (2, 7, 9, 32, 32, 3, 2, 2, 1), (2, 7, 9, 32, 32, 2, 2, 2, 0), (2, 7, 9, 32, 32, 2, 2, 1, 1),
+                    (2, 7, 9, 32, 32, 5, 5, 1, 2), (2, 9, 11, 32, 32, 7, 7, 2, 3), (2, 9, 11, 32, 32, 9, 1, 1, 4)]
+
 # the data gradient with a COMPACT stride-2 residual (tests/test_kernels_gpu.py::test_planes_dgrad_compact_stride2_residual): N, H, W, C, Ko, R
 COMPACT_RESIDUAL = [(3, 13, 8, 64, 64, 3), (2, 8, 13, 128, 64, 1)]
 
@@ -130,7 +136,7 @@ def _small(cfg):
 
 def _all_geometries():
     seen = []
-    for cfg in COMPUTES + CHANNEL_EDGES + [(N, H, W, C, Ko, R, R, 1, R // 2) for N, H, W, C, Ko, R in COMPACT_RESIDUAL] + \
+    for cfg in COMPUTES + CHANNEL_EDGES + SWEEP_GEOMETRIES + [(N, H, W, C, Ko, R, R, 1, R // 2) for N, H, W, C, Ko, R in COMPACT_RESIDUAL] + \
             [(N, H, W, 2 * C, C, 1, 1, 2, 0) for N, H, W, C, Ko, R in COMPACT_RESIDUAL]:
         s = _small(cfg)
         if s not in seen:

@@ -10,7 +10,15 @@ Every input sits in a `memguard.Guarded` allocation and every output goes throug
 intact, every element written, bit-identical over an ordinary and a NaN-poisoned exact-size workspace, and a +-1e30 one where the
 call takes a workspace), so a stray access lands in memory the test owns.  Every generated case is legal under include/cxrk.h:
 nothing is skipped, and a refusal by a wrapper fails the test.  Each test id is a chunk of at most 16 cases and prints its worst
-error / bound per output before it asserts."""
+error / bound per output before it asserts.
+
+Family H (tests/sweep_conv_cases.py) is the convolutions, one operation per case: `test_conv_f32` the fp32 entry points and the stem's
+form of the planes forward, `test_conv_planes` the planes entry points under the library's tile policy and with the 256x256 tile
+forced.  Planes inputs keep tests/test_conv_geometry_gpu.py's gap between their planes.  Every output passes the elementwise derived
+bound AND the per-channel / per-filter level; after every call the library's launch count, label and split-K are held to the Python
+restatement of the dispatch (sweep_conv_cases.predict); decision bits, masked elements, the pixels of a stride-2 class that no tap
+reaches, dx with and without fused sums, and the window-resident weight gradient against its implicit-GEMM twin are compared bit for
+bit."""
 import ctypes
 
 import pytest
@@ -684,3 +692,146 @@ def test_grid_stride_wrap(op):
     ratio, at = S.forward_bound(got, ref, mag, cst * S.U24)
     print(f"{op} wrap: worst error / bound {ratio:.3g} over {pick.numel()} elements, {n - 8 * 256 * S.BN_GRID_CAP} past the cap")
     assert ratio <= 1.0, f"{op}: {ratio:.3g} x bound at flat index {int(pick[at[0]])}"
+
+
+# ================================================================================================================ H: convolutions
+import os  # noqa: E402
+
+import sweep_conv_cases as HC  # noqa: E402
+from test_conv_geometry_gpu import plane_gap  # noqa: E402
+
+
+@pytest.fixture
+def window_wgrad_switch():
+    """CXRK_HALO_WGRAD, read by the library on every call (as tests/test_exact_planes_gpu.py switches it)"""
+    old = os.environ.get("CXRK_HALO_WGRAD")
+
+    def set_(v):
+        if v is None:
+            os.environ.pop("CXRK_HALO_WGRAD", None)
+        else:
+            os.environ["CXRK_HALO_WGRAD"] = v
+    yield set_
+    set_(old)
+
+
+def _launched(c, pred, what=""):
+    """the Python restatement of the dispatch (sweep_conv_cases.predict) against what the library says it launched"""
+    lib = _cxr_lib.load()
+    got = (lib.cxrk_last_launch_label().decode(), lib.cxrk_last_launch_count(), lib.cxrk_last_launch_split_bf16())
+    want = (pred["label"], pred["count"], pred["split_bf16"])
+    assert got == want, f"{S.describe(c)}{what}: launched {got}, predicted {want}"
+
+
+def _zero_bits(g, sel):
+    """every bit of the selected pixels of a guarded [.., N, H, W, C] output is zero"""
+    b = g.bits()
+    b = b[(slice(None),) + sel] if g.dtype == BF else b[sel]
+    return not bool(b.any())
+
+
+def _conv(c, rep, wide=False, switch=None):
+    inp = S.build(c)
+    ref = S.reference(c, inp)
+    pred = HC.predict(c, wide)
+    pl = c.family == "HPL"
+    N, H, W, C, Cp, Ko, R, Sf, st, pad = c.N, c.H, c.W, c.C, c.Cpad, c.Ko, c.R, c.S, c.stride, c.pad
+    Ho, Wo = c.out_hw
+    geo = (N, H, W, Cp, Ko, R, Sf, st, pad)
+    G = Inputs()
+    planes = lambda t, n: G.planes(t, n, gap=plane_gap(t.shape))      # noqa: E731
+    put = planes if pl else G.put
+    form = f" [{c.op}:{pred['path']}]"
+    if c.op == "fwd":
+        x, w = put(inp["x"], "x"), put(inp["w"].reshape(Ko, -1) if pl else inp["w"], "w_scaled")
+        shift = G.put(inp["shift"], "shift") if c.shift else None
+        res = None if c.residual == "none" else G.put(inp["residual"], "residual") if c.form == "f32" else planes(inp["residual"], "residual")
+        if c.form == "f32":
+            o = run(lambda o: K.conv_fwd(x, w, shift, res, o["y"], *geo, c.relu), {"y": Out((N, Ho, Wo, Ko))}, False)
+        else:
+            spec = {"y": Out((2, N, Ho, Wo, Ko), BF)}
+            if c.bits:
+                spec["bits"] = Out((N * Ho * Wo, Ko // 8), U8)
+            o = run(lambda o: K.conv_fwd_pl(x, w, shift, res, K.Planes(o["y"]), o.get("bits"), *geo, c.relu), spec, False)
+        _launched(c, pred)
+        got = {"y": o["y"].value()}
+        if c.bits:      # the decisions of the values this launch stored
+            assert torch.equal(S.unpack_bits(o["bits"].t.cpu(), Ko), got["y"].reshape(-1, Ko) > 0), f"{S.describe(c)}: decision bits differ from the stored output"
+    elif c.op == "dgrad":
+        dy, w = put(inp["dy"], "dy"), put(inp["w"].reshape(Ko, -1) if pl else inp["w"], "w_scaled")
+        res = put(inp["residual"], "residual") if c.residual != "none" else None
+        side = G.put(inp["maskin" if pl else "relu_src"], "mask") if c.mask else None
+        dx = Out((2, N, H, W, Cp), BF) if pl else Out((N, H, W, Cp))
+
+        def call(o):
+            if pl:
+                K.conv_bwd_data_pl(dy, w, res, side, K.Planes(o["dx"]), *geo, sums=o.get("sums"), residual_s2=c.residual == "compact")
+            else:
+                K.conv_bwd_data(dy, w, res, side, o["dx"], *geo, sums=o.get("sums"))
+
+        o = run(call, {"dx": dx, "sums": Out((Cp,))} if c.sums else {"dx": dx}, c.sums)
+        _launched(c, pred)
+        got = {k: g.value() for k, g in o.items()}
+        if c.sums:      # the fused column sums leave dx alone
+            o2 = run(call, {"dx": dx}, False)
+            _launched(c, pred, " without sums")
+            assert torch.equal(o["dx"].bits(), o2["dx"].bits()), f"{S.describe(c)}: dx with sums differs from dx without"
+        keep = HC.dgrad_mask(c, inp)
+        if keep is not None:
+            assert not bool(got["dx"][~keep].any()), f"{S.describe(c)}: a masked element of dx is not zero"
+        if st == 2:     # the pixels of a class that no tap reaches: zero in every bit
+            for ph, pw, _, _, tr, ts in HC.s2_classes(c):
+                if not (tr and ts):
+                    sel = (slice(None), slice(ph, None, 2), slice(pw, None, 2))
+                    assert _zero_bits(o["dx"], sel), f"{S.describe(c)}: class ({ph}, {pw}) has no tap and is not zero"
+    else:
+        x, dy = put(inp["x"], "x"), put(inp["dy"], "dy")
+        wraw = G.put(inp["w"], "w")
+        scale = G.put(inp["scale"], "scale") if c.bn != "noscale" else None
+        rstd, rmean, sumdy = (G.put(inp[k], k) for k in ("rstd", "rmean", "sumdy"))
+        spec = {"dw": Out((Ko, R, Sf, C), init=inp.get("dw0"))}
+        if c.bn != "none":
+            spec.update(dgamma=Out((Ko,), init=inp.get("dgamma0")), dbeta=Out((Ko,), init=inp.get("dbeta0")))
+
+        def call(o):
+            if pl:
+                K.conv_bwd_params_pl(x, dy, wraw, scale, rstd, rmean, sumdy, o["dw"], o.get("dgamma"), o.get("dbeta"), c.accumulate, N, H, W, C, Ko,
+                                     R, Sf, st, pad)
+            else:
+                K.conv_bwd_params(x, dy, wraw, scale, rstd, rmean, sumdy, o["dw"], o.get("dgamma"), o.get("dbeta"), c.accumulate, N, H, W, C, Cp,
+                                  Ko, R, Sf, st, pad)
+
+        o = run(call, spec, True)
+        _launched(c, pred)
+        sk = _cxr_lib.load().cxrk_gemm_wgrad_splitk(Ko, R * Sf * Cp, N * Ho * Wo, int(pl))
+        assert sk == pred["splitk"], f"{S.describe(c)}: the library splits K by {sk}, the restated policy by {pred['splitk']}"
+        got = {k: g.value() for k, g in o.items()}
+        if pred["path"] == "window":      # include/cxrk.h: the implicit GEMM's slabs, bit-identical result
+            switch("0")
+            try:
+                o2 = run(call, spec, True)
+                _launched(c, HC.predict(c, wide, window_wgrad=False), " with CXRK_HALO_WGRAD=0")
+            finally:
+                switch(None)
+            for k in spec:
+                assert torch.equal(o[k].bits(), o2[k].bits()), f"{S.describe(c)}: {k} of the window kernel differs from the implicit GEMM's"
+    rep.add(c, S.check(c, ref, got, _split()), form)
+    G.check()
+
+
+@both_precisions
+@pytest.mark.parametrize("chunk", chunk_ids("H32"))
+def test_conv_f32(chunk):
+    rep = Report("conv fp32 " + chunk)
+    for c in chunk_cases("H32", chunk):
+        _conv(c, rep)
+    rep.finish()
+
+
+@both_precisions
+@pytest.mark.parametrize("chunk", chunk_ids("HPL"))
+def test_conv_planes(chunk, wide, window_wgrad_switch):
+    rep = Report(f"conv planes {chunk} [{wide}]")
+    for c in chunk_cases("HPL", chunk):
+        _conv(c, rep, wide == "wide", window_wgrad_switch)
+    rep.finish()

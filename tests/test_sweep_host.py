@@ -2,7 +2,13 @@
 kernels' dispatch thresholds; the float64 references agree with independent formulations; the table E32 is what this machine
 measures; and -- as tests/test_memguard_host.py does for the memory contract -- deliberately wrong CPU "kernels" run through the
 same comparators and bounds as the GPU tests: each is caught on at least one generated case (family G's: on exactly the cases that
-reach the path it breaks), the correct float32 evaluation passes on every case."""
+reach the path it breaks), the correct float32 evaluation passes on every case.
+
+Family H (the convolutions, tests/sweep_conv_cases.py): the strata and the special cases of its generator; the dispatch of
+csrc/conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip, gemm_dispatch.h and wgrad_splitk_policy restated in Python
+(sweep_conv_cases.predict), and every path of it reached by the generated lists; an evaluation by per-tap gathers, independent of
+F.conv2d / conv2d_input / conv2d_weight, that passes on every case, and ten wrong variations of it, each caught on the cases that
+reach its path and on no other; the lost lo hi plane term that today's tensor-wide metric cannot see."""
 import math
 import os
 import sys
@@ -554,7 +560,7 @@ def test_e32_table():
     the float32 matrix products of two hosts differ (E32_HOST_RATIO) the entry is the larger host's figure and the upper limit is wider
     by exactly the measured ratio between them."""
     measured = {}
-    for family in ("A", "C", "D", "E", "F", "G"):
+    for family in ("A", "C", "D", "E", "F", "G", "H32", "HPL"):
         measured.update(S.measure_e32(family))
     print("\n".join(f"{k}: measured {v:.3g}, table {S.E32.get(k)}" for k, v in sorted(measured.items())))
     assert set(measured) == set(S.E32), set(measured) ^ set(S.E32)
@@ -1157,3 +1163,268 @@ def test_wrapped_bias_passes_the_old_metric_and_fails_the_new():
                 old_pass_new_fail.append(c.index)
     assert caught == wide and len(wide) >= 5, (sorted(caught), sorted(wide))
     assert len(old_pass_new_fail) >= 5, "the wrapped bias index must pass today's metric and fail the elementwise bound"
+
+
+# ================================================================================================================ family H: convolutions
+import sweep_conv_cases as HC  # noqa: E402
+import test_conv_geometry_host as CG  # noqa: E402
+
+H_FAMILIES = ("H32", "HPL")
+
+
+def _h_ops(family):
+    return {op: [c for c in S.cases(family) if c.op == op] for op in HC.OPS}
+
+
+@pytest.mark.parametrize("family", H_FAMILIES)
+def test_conv_strata_are_hit(family):
+    """the independent dimensions (rows / reduction stratum, filter geometry, forward epilogue, fresh / accumulate, BatchNorm form,
+    profile) are covered by the first max(n) cases of every operation; the dimensions a cap or a fitting filter narrows (channels,
+    image sizes, the data gradient's form) by the operation's cases; and the special cases of the issue exist"""
+    pl = family == "HPL"
+    for op, cs in _h_ops(family).items():
+        assert len(cs) == dict(HC.COUNTS)[op] == 40
+        lane = family == "H32" and op != "dgrad"
+        geoms = HC.GEOMS_LANE if lane else HC.GEOMS
+        dims = {"rows": ([s[0] for s in (HC.RED if op == "wgrad" else HC.ROWS)], lambda c: c.rows), "geom": (geoms, lambda c: c.geom),
+                "profile": (HC.PROFILES, lambda c: c.profile)}
+        if op == "fwd":
+            dims["epi"] = (HC.FWD_EPI, lambda c: int(c.shift) + 2 * (c.residual != "none") + 4 * int(c.relu))
+        if op == "wgrad":
+            dims.update(accumulate=((False, True), lambda c: c.accumulate), bn=(HC.WGRAD_BN, lambda c: c.bn))
+        first = cs[:max(len(s) for s, _ in dims.values())]
+        assert len(first) <= 40 - HC.TRIO
+        for name, (strata, get) in dims.items():
+            missing = set(strata) - {get(c) for c in first}
+            assert not missing, f"{family}.{op}.{name}: {sorted(missing, key=str)} not among the first {len(first)} cases"
+        for name, strata, get in (("C", HC.C_STRATA[family, op], lambda c: c.Cpad), ("Ko", HC.KO_STRATA[family, op], lambda c: c.Ko),
+                                  ("H", HC.HW, lambda c: c.H), ("W", HC.HW, lambda c: c.W)):
+            assert set(strata) <= {get(c) for c in cs}, f"{family}.{op}.{name}"
+        # the rows land where their stratum says
+        for c in cs:
+            lo, hi = {s[0]: s[1:] for s in (HC.RED if op == "wgrad" else HC.ROWS)}[c.rows]
+            n = HC.contraction_length(c) if op == "wgrad" else HC.gemm_rows(c)
+            assert lo <= n <= hi and (c.rows != "257..511" or n % 256), S.describe(c)
+        if op != "wgrad":      # many tiny images: a 256-row tile spans dozens of them
+            per = lambda c: (c.H * c.W if op == "dgrad" else c.out_hw[0] * c.out_hw[1])      # noqa: E731
+            assert any(HC.gemm_rows(c) >= 257 and 256 // per(c) >= 24 for c in cs), f"{family}.{op}: no tile over dozens of images"
+        if pl:                 # the window-resident trio
+            trio = [c for c in cs if c.geom == (3, 3, 1, 1) and c.Cpad == c.Ko == 64]
+            assert sum(c.W <= 58 for c in trio) >= 6 and any(c.W == 58 for c in trio) and sum(c.W == 59 for c in trio) >= 1
+        padded = [c for c in cs if c.C < c.Cpad]
+        assert bool(padded) == (family == "H32" and op != "dgrad") and all((c.Cpad, c.C) in ((4, 3), (8, 5)) for c in padded)
+    ops = _h_ops(family)
+    forms = {(c.residual, c.mask, c.sums) for c in ops["dgrad"]}
+    assert {(r, m, s) for r in ("none", "dense") for m in (False, True) for s in (False, True)} <= forms
+    compact = [c for c in ops["dgrad"] if c.residual == "compact"]
+    assert (len([c for c in compact if c.H % 2 or c.W % 2]) >= 2 and {c.mask for c in compact} == {False, True}) if pl else not compact
+    for c in ops["dgrad"]:
+        if c.stride == 2 and not CG.dgrad_side_ok(c.H, c.W, c.R, c.S, 2, c.pad):
+            assert c.residual == "none" and not c.mask and not c.sums, S.describe(c)
+    assert any(c.stride == 2 and not CG.dgrad_side_ok(c.H, c.W, c.R, c.S, 2, c.pad) for c in ops["dgrad"])
+    if not pl:
+        assert {c.form for c in ops["fwd"]} == {"f32", "stem"} and any(c.bits for c in ops["fwd"])
+        src = [S.build(c)["relu_src"] for c in ops["dgrad"] if c.mask][:4]
+        assert src and all(bool(((t == 0) & ~torch.signbit(t)).any()) and bool(((t == 0) & torch.signbit(t)).any()) for t in src)
+    else:
+        assert any(c.bits for c in ops["fwd"]) and any(c.relu and not c.bits for c in ops["fwd"])
+
+
+def test_conv_dispatch_coverage():
+    """sweep_conv_cases.predict restates the host logic of csrc/conv_fwd.hip, conv_dgrad.hip, conv_wgrad.hip, gemm_dispatch.h and
+    wgrad_splitk_policy (tests/test_sweep_gpu.py holds it to the library: launch count, label, split-K); the generated lists reach
+    every path of it"""
+    h32, hpl = S.cases("H32"), S.cases("HPL")
+    p32 = [(c, HC.predict(c)) for c in h32]
+    ppl = [(c, HC.predict(c)) for c in hpl]
+    pw = [(c, HC.predict(c, wide=True)) for c in hpl]
+    fwd32 = [(c, p) for c, p in p32 if c.op == "fwd"]
+    assert {p["gather"] for _, p in fwd32} == {"tap", "lane"}
+    lane = [c for c, p in fwd32 if p["gather"] == "lane"]
+    assert any(c.R * c.S > 32 for c in lane) and any(c.R > 8 for c in lane) and any(c.Cpad % 32 for c in lane)
+    for fam in (p32, ppl):
+        assert {p["tile"] for _, p in fam} - {None} == {"128x128", "256x64", "64x256"}
+    assert {p["tile"] for _, p in pw} - {None} == {"256x256"} and all(p["split_bf16"] == 1 for _, p in ppl + pw)
+    assert all(p["split_bf16"] == 0 and "gemm_f32_kernel" in p["label"] for _, p in p32), "fp32 operands under 2^30: the exact mainloop"
+    for op, path in (("fwd", "halo"), ("dgrad", "halo"), ("wgrad", "window")):
+        trio = [(c, p) for c, p in ppl if c.op == op and c.geom == (3, 3, 1, 1) and c.Cpad == c.Ko == 64]
+        assert sum(p["path"] == path for _, p in trio) >= 6 and any(c.W == 58 and p["path"] == path for c, p in trio)
+        assert [p["path"] for c, p in trio if c.W == 59] == ["gemm"], "W = 59 takes the implicit GEMM"
+        if op != "wgrad":      # the forced 256x256 tile takes these layers back
+            assert all(p["path"] == "gemm" for c, p in pw if c.op == op)
+        if op == "wgrad":
+            assert all("DmaConvIm2colMC" in HC.predict(c, window_wgrad=False)["label"] for c, _ in trio)
+    for fam in (p32, ppl):
+        s2 = [(c, p) for c, p in fam if c.op == "dgrad" and c.stride == 2]
+        assert {p["count"] for _, p in s2} == {1, 2, 4} and any(p["zero_class"] for _, p in s2)
+        assert any(neg for _, p in s2 for _, _, neg in p["classes"]), "a negative tap offset (stride 2, pad 0, a 3-wide extent)"
+        wg = [p for c, p in fam if c.op == "wgrad"]
+        assert {p["sg_log2"] for p in wg} == {0, 2, 4} and {8 <= p["slabs"] < 64 for p in wg} == {False, True}
+        assert any(p["splitk"] > p["slabs"] for p in wg) or any(p["splitk"] == p["slabs"] > 1 for p in wg)
+    assert {p["sg_log2"] for c, p in pw if c.op == "wgrad"} == {0, 2, 4}
+    epi = {(p["epi"], p["kind_m1"]) for _, p in p32}
+    assert {"scalar", "vec", "fast"} == {e for e, _ in epi} and ("fast", True) in epi and ("fast", False) in epi
+    assert any(p["kind_m1"] for c, p in ppl if c.op == "wgrad") and all(p["epi"] == "fast" for _, p in ppl)
+    assert any(c.C < c.Cpad for c in h32 if c.op == "fwd") and any(c.C < c.Cpad for c in h32 if c.op == "wgrad")
+    # the split-K policy at the shapes the step takes (csrc/gemm_misc.hip): 64 x 576 over 56 x 56 x 8 pixels
+    assert HC.wgrad_splitk_policy(64, 576, 25088, True, 1) == 98 and HC.slabs_written(25088, 98) == 98
+
+
+# ---- wrong CPU convolutions: one gather per filter tap, so that each mistake of the issue's list can be made where a kernel makes it
+def _gather_x(x, Ho, Wo, st, pad, r, s, wrap=False):
+    """x[n, ho st - pad + r, wo st - pad + s, :] for every (ho, wo), zero outside the image.  wrap: a column outside the row is not
+    masked and reads the neighbouring row of the flattened image"""
+    N, H, W, C = x.shape
+    hi, wi = torch.arange(Ho) * st - pad + r, torch.arange(Wo) * st - pad + s
+    idx = hi[:, None] * W + wi[None, :]
+    ok = ((hi >= 0) & (hi < H))[:, None] & (((idx >= 0) & (idx < H * W)) if wrap else ((wi >= 0) & (wi < W))[None, :])
+    return x.reshape(N, H * W, C)[:, idx.clamp(0, H * W - 1)] * ok[None, :, :, None]
+
+
+def _gather_dy(dy, H, W, st, pad, r, s, prev_row=False):
+    """dy[n, (hi + pad - r) / st, (wi + pad - s) / st, :] for every (hi, wi), zero where the division leaves a rest or the pixel lies
+    outside.  prev_row: row -1 is not masked and reads the row in front of the image (the last row of the previous one)"""
+    N, Ho, Wo, Ko = dy.shape
+    a, b = torch.arange(H) + pad - r, torch.arange(W) + pad - s
+    ho, wo = torch.div(a, st, rounding_mode="floor"), torch.div(b, st, rounding_mode="floor")
+    okh, okw = (a % st == 0) & (ho >= (-1 if prev_row else 0)) & (ho < Ho), (b % st == 0) & (wo >= 0) & (wo < Wo)
+    rows = torch.arange(N)[:, None] * Ho + ho[None, :]                       # [N, H] rows of the flattened [N Ho, Wo, Ko]
+    live = okh[None, :] & (rows >= 0)
+    g = dy.reshape(N * Ho, Wo, Ko)[rows.clamp(0, N * Ho - 1)][:, :, wo.clamp(0, Wo - 1)]
+    return g * (live[:, :, None] & okw[None, None, :])[..., None]
+
+
+def _taps(c, a, b, pad=None, swap=False, wrap=False, prev_row=False):
+    pad = c.pad if pad is None else pad
+    R, Sf = (c.S, c.R) if swap else (c.R, c.S)
+    Ho, Wo = c.out_hw
+    if c.op == "wgrad":
+        out = torch.zeros(c.Ko, R, Sf, c.Cpad, dtype=a.dtype)
+        for r in range(R):
+            for s in range(Sf):
+                out[:, r, s] = b.reshape(-1, c.Ko).T @ _gather_x(a, Ho, Wo, c.stride, pad, r, s).reshape(-1, c.Cpad)
+        return out.reshape(c.Ko, c.R, c.S, c.Cpad)
+    w = b.reshape(c.Ko, R, Sf, c.Cpad)
+    if c.op == "fwd":
+        return sum(_gather_x(a, Ho, Wo, c.stride, pad, r, s, wrap) @ w[:, r, s].T for r in range(R) for s in range(Sf))
+    return sum(_gather_dy(a, c.H, c.W, c.stride, pad, r, s, prev_row) @ w[:, r, s] for r in range(R) for s in range(Sf))
+
+
+def _conv32(c, inp, drop_lo_hi_at=None, epi=None, **bug):
+    """the case by tap gathers, float64 accumulation rounded once, float32 epilogue; `bug`: one of the mistakes below"""
+    a, b = HC.operands(c, inp)
+    if c.family == "H32":
+        acc = _taps(c, a.double(), b.double(), **bug)
+    else:
+        (ah, al), (bh, bl) = ((t.double() for t in S.canonical_planes(v.contiguous())) for v in (a, b))
+        lo_hi = _taps(c, al, bh, **bug)
+        if drop_lo_hi_at is not None and c.op == "fwd":
+            lo_hi[..., drop_lo_hi_at] = 0
+        acc = _taps(c, ah, bh + bl, **bug) + lo_hi
+    out = HC.epilogue(c, inp, acc, torch.zeros_like(acc), F32, **(epi or {}))
+    return {k: v for k, v in out.items() if not k.startswith("mag:")}
+
+
+def _drop_tail_pixels(c, inp):
+    if c.op != "wgrad":
+        return _conv32(c, inp)
+    dy = inp["dy"].clone()
+    n = HC.contraction_length(c)
+    dy.view(-1, c.Ko)[n - n % 32:] = 0
+    return _conv32(c, dict(inp, dy=dy))
+
+
+def _dw_with_cpad(c, inp):
+    out = _conv32(c, inp)
+    if c.op != "wgrad":
+        return out
+    buf = torch.full((c.Ko * c.R * c.S * c.Cpad,), float("nan"))
+    buf.view(c.Ko, c.R, c.S, c.Cpad)[..., :c.C] = out["dw"]      # rows written Cpad apart
+    out["dw"] = buf[:out["dw"].numel()].view(out["dw"].shape)     # and read C apart
+    return out
+
+
+def _wrap_reaches(c):
+    hi = torch.arange(c.out_hw[0])[:, None, None, None] * c.stride - c.pad + torch.arange(c.R)[None, None, :, None]
+    wi = torch.arange(c.out_hw[1])[None, :, None, None] * c.stride - c.pad + torch.arange(c.S)[None, None, None, :]
+    idx = hi * c.W + wi
+    return bool(((hi >= 0) & (hi < c.H) & ((wi < 0) | (wi >= c.W)) & (idx >= 0) & (idx < c.H * c.W)).any())
+
+
+def _compact_moves(c):
+    n, h, w = torch.arange(c.N)[:, None, None], torch.arange(0, c.H, 2)[None, :, None], torch.arange(0, c.W, 2)[None, None, :]
+    He, We, last = (c.H + 1) // 2, (c.W + 1) // 2, c.N * ((c.H + 1) // 2) * ((c.W + 1) // 2) - 1
+    return not torch.equal((n * He + h // 2) * We + w // 2, ((n * (c.H // 2) + h // 2) * (c.W // 2) + w // 2).clamp(max=last))
+
+
+# (name, the wrong kernel, the cases that reach the path it breaks)
+CONV_FAKES = (
+    ("a: stride-2 / pad-0 dgrad reads the previous image's last row as row -1", lambda c, i: _conv32(c, i, prev_row=c.stride == 2),
+     lambda c: c.op == "dgrad" and c.stride == 2 and c.pad == 0 and c.R == 3 and c.N > 1),
+    ("b: a border tap wraps into the neighbouring image row", lambda c, i: _conv32(c, i, wrap=True), lambda c: c.op == "fwd" and _wrap_reaches(c)),
+    ("c: pad taken as R // 2", lambda c, i: _conv32(c, i, pad=c.R // 2), lambda c: c.pad != c.R // 2),
+    ("d: R and S swapped", lambda c, i: _conv32(c, i, swap=True), lambda c: c.R != c.S),
+    ("e: the weight gradient drops the pixels behind the last whole K-tile", _drop_tail_pixels,
+     lambda c: c.op == "wgrad" and HC.contraction_length(c) % 32 != 0),
+    ("f1: dgamma from the scaled filter", lambda c, i: _conv32(c, i, epi={"dgamma": "scaled_filter"}), lambda c: c.op == "wgrad" and c.bn == "full"),
+    ("f2: dgamma without mean sumdy", lambda c, i: _conv32(c, i, epi={"dgamma": "no_mean"}), lambda c: c.op == "wgrad" and c.bn != "none"),
+    ("g: dw indexed with Cpad", _dw_with_cpad, lambda c: c.op == "wgrad" and c.C < c.Cpad),
+    ("h: the compact residual indexed with H // 2, W // 2", lambda c, i: _conv32(c, i, epi={"He": max(c.H // 2, 0) or -1, "We": max(c.W // 2, 0) or -1}),
+     lambda c: c.residual == "compact" and _compact_moves(c)),
+    ("j: the lo hi term lost on one output channel", lambda c, i: _conv32(c, i, drop_lo_hi_at=c.Ko // 2), lambda c: c.family == "HPL" and c.op == "fwd"),
+)
+# a, b, c and g are caught on exactly the cases that reach them.  The others are caught on no other case and on nine in ten of theirs:
+# on a one-pixel image a 1 x 3 and a 3 x 1 filter read the same tap, a dropped pixel may lie on a border that no tap reads, a scale
+# may be 1 to within the bound -- and the lost plane term (j) stays inside the elementwise bound from K of about 2000 on (the bound
+# grows with K, the term with its square root), so half of its cases are asked for
+CONV_FAKES_EXACT = "abcg"
+
+
+@pytest.mark.parametrize("family", H_FAMILIES)
+def test_fake_conv_kernels_are_caught(family):
+    """one pass over the family: the reference of a case is built once, the correct tap-gather evaluation passes on it (which also
+    holds F.conv2d / conv2d_input / conv2d_weight to an independent form at EVERY generated case), then every wrong kernel runs"""
+    caught = {name: set() for name, _, _ in CONV_FAKES}
+    reach = {name: {c.index for c in S.cases(family) if pred(c)} for name, _, pred in CONV_FAKES}
+    bad = lambda res: any(not r <= 1.0 for _, r, _ in res)      # noqa: E731
+    for c in S.cases(family):
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        res = S.check(c, ref, _conv32(c, inp))
+        assert not bad(res), "the tap-gather evaluation the fakes are variations of must pass: " + S.failures(c, res)
+        for name, kernel, pred in CONV_FAKES:
+            if pred(c) or c.index % 3 == 0:      # and a third of the other cases: nothing is caught off its path
+                if bad(S.check(c, ref, kernel(c, inp))):
+                    caught[name].add(c.index)
+    for name, _, _ in CONV_FAKES:
+        got, want = caught[name], reach[name]
+        print(f"{family} {name}: caught {len(got)} of {len(want)}")
+        if name[0] in {"H32": "hj", "HPL": "g"}[family]:      # the compact residual and the plane terms are HPL's, C < Cpad is H32's
+            assert not want and not got
+            continue
+        assert want and got <= want, (name, sorted(got - want))
+        missed = len(want) - len(got)      # nine in ten; of a handful of cases, all but one
+        assert got == want if name[0] in CONV_FAKES_EXACT else missed <= (0.5 if name[0] == "j" else 0.1) * len(want) or missed <= 1, (name, sorted(want - got))
+
+
+def test_lost_plane_term_passes_the_old_metric_and_fails_the_new():
+    """the lo hi plane term lost on ONE output channel of a planes forward (fake j), on the chan_scaled cases, the channel being the
+    one of the smallest scale.  Against today's metric (max |got - ref| / max |ref| < 2e-4, tests/test_kernels_gpu.py's planes forward)
+    the loss is invisible wherever that channel lies decades below the widest one; per output channel it is not."""
+    old_pass_new_fail, shown = [], 0
+    for c in S.cases("HPL"):
+        if c.op != "fwd" or c.profile != "chan_scaled":
+            continue
+        inp = S.build(c)
+        ref = S.reference(c, inp)
+        ch = int(ref["y"].reshape(-1, c.Ko).abs().max(0).values.clamp_min(1e-30).argmin()) if c.relu else \
+            int(inp["w"].reshape(c.Ko, -1).abs().max(1).values.argmin())
+        got = _conv32(c, inp, drop_lo_hi_at=ch)
+        res = dict((n, r) for n, r, _ in S.check(c, ref, got))
+        old = S.tensor_wide(got["y"], ref["y"])
+        shown += 1
+        print(f"case {c.index} (K = {HC.contraction_length(c)}, channel {ch} of {c.Ko}): tensor-wide {old:.2e}, elementwise {res['y']:.3g} x bound, "
+              f"per channel {res['y/level']:.3g} x bound")
+        if old < 2e-4 and max(res["y"], res["y/level"]) > 1.0:
+            old_pass_new_fail.append(c.index)
+    assert shown >= 8 and len(old_pass_new_fail) >= 3, "the lost plane term must pass today's metric and fail the new comparators"
